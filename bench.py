@@ -8,7 +8,12 @@ output; pinned, enqueued on the root's stream, complete at the step's closing sy
 Rays = closest-hit queries issued by RayColor (one per bounce level with depth > 0),
 counted by the kernel. The scene program is resident in HBM before timing starts.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; `roofline`, `cpu_baseline`
+and the isolated gather timings are null in it. `--full` adds them (the counting pass and the PMC
+profile lookup of the roofline, the oracle's CPU sample, GATHER_REPS gathers on an idle GPU).
+`--dump-outputs DIR` writes the image the last timed step handed to the host as DIR/image.npy (float32).
 
 Multi-GPU goes through the C ABI (include/rt2.h), not torch:
   * under torch.distributed.run (WORLD_SIZE = N): one process per GPU, rt2_tracer_join (partition +
@@ -19,7 +24,7 @@ Multi-GPU goes through the C ABI (include/rt2.h), not torch:
   * --emulate-world N [--emulate-rank r|all]: diagnostic, one GPU renders rank r's bands of an N-way
     split (all: every rank in turn); no gather.
 
-Rank 0 prints one JSON line (contract in the task statement) with a `roofline` object for the render
+Rank 0 prints one JSON line (contract in the task statement), under --full with a `roofline` object for the render
 kernel (frac: SURVEY §8(d)'s useful fp32 flops per ray x the live rays / the launches' own GPU time, over
 the fp32 vector peak; the VALU and scalar issue fractions from a committed PMC profile of this kernel
 build and config as named companions) and a `cpu_baseline` object (the oracle restatement on every
@@ -98,7 +103,28 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--stats-frames", type=int, default=8)
     ap.add_argument("--out-image", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (counting pass + PMC profile), the CPU baseline and the isolated gather "
+                         "timings (a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to the host as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: bound on everything written
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy in float32. An array over its share of DUMP_MAX_BYTES is written as a fixed sample:
+    the elements at sorted flat indices drawn from numpy's default_rng(0), the same in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if arr.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, arr.size, share // 4))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 def host_cores():
@@ -384,14 +410,26 @@ def main():
                 ps = tr.part_stats(g)
                 per_rank[-1]["gpus"].append({"gpu": g, "rays": ps["rays"], "kernel_ms": ps["kernel_ms"],
                                              "enqueue_ms": ps["enqueue_ms"], "launches": ps["launches"]})
-    # The exchange itself, timed on an otherwise idle GPU: in a run of back-to-back steps the gather's
+    # What the last timed step handed to its caller: the root's host copy of the gathered image
+    # (NonConvertedPixels), or, where the timed path has no gather, this GPU's accumulation.
+    if rank == 0 and a.dump_outputs:
+        if readback is not None:
+            last = readback.array
+        elif host_gather is not None:
+            last = host_gather.image.numpy()
+        elif mode in ("ranks", "multi"):
+            last = tr.image_non_converted_pixels()
+        else:
+            last = tr.Accumulation()
+        dump_outputs(a.dump_outputs, {"image": last})
+    # The exchange itself (--full), timed on an otherwise idle GPU: in a run of back-to-back steps the gather's
     # small kernels (the RCCL gather, the de-interleave) wait for CUs behind the next step's render,
     # whose persistent waves hold them, so the event pair around a step's gather spans that queue time
     # (gather_span_ms_per_step). gather_ms_per_step is the mean over GATHER_REPS isolated gathers
     # (HIP events on the root stream around ncclGather + de-interleave); gather_readback_ms_isolated
     # is the host wall time of one gather + NonConvertedPixels() readback.
     gather_iso_ms = gather_ms_iso = None
-    if mode in ("ranks", "multi") and host_gather is None:
+    if a.full and mode in ("ranks", "multi") and host_gather is None:
         g0 = tr.stats()
         for _ in range(GATHER_REPS):
             sync_all()
@@ -439,7 +477,7 @@ def main():
     key = {"workload": workload, "partition": partition, "kernel_sha": lib_sha}
     roofline = None
     cpu = None
-    if rank == 0:
+    if rank == 0 and a.full:
         if mode == "emulate":  # the slowest rank's partition
             tr.set_partition(a.band_h, me["rank"], a.emulate_world)
         mine = me if mode != "ranks" else per_rank[0]

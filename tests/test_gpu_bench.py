@@ -15,6 +15,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -48,7 +49,9 @@ def _run(tmp_path, name, env_extra, nproc=None, extra=()):
 
 @pytest.fixture(scope="module")
 def plain(tmp_path_factory, have_gpu):
-    return _run(tmp_path_factory.mktemp("bench"), "plain", {}, extra=["--plain"])
+    d = tmp_path_factory.mktemp("bench")
+    return (*_run(d, "plain", {}, extra=["--plain", "--dump-outputs", str(d / "dump")]),
+            np.load(d / "dump" / "image.npy"))
 
 
 def _check_line(d, n):
@@ -59,6 +62,31 @@ def _check_line(d, n):
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["scaling"] == "strong"
     assert d["config"]["workload"].startswith("cornell_box_original.json 96x80 @ 16 spp")
     assert sum(r["rows"] for r in d["detail"]["per_rank"]) == 80 and len(d["detail"]["per_rank"]) == (n if n > 1 else 1)
+    assert d["dtype"] == "f32"
+
+
+def test_bench_full_and_dump_outputs(tmp_path, plain):
+    """A plain run leaves the roofline, the CPU baseline and the isolated gathers out; --full has them.
+    --dump-outputs writes the last step's host image (NonConvertedPixels = accumulation / spp, the
+    IEEE quotient), which the one-GPU tracer's dumped accumulation reproduces exactly."""
+    assert plain[0]["roofline"] is None and plain[0]["cpu_baseline"] is None
+    assert plain[0]["detail"]["gather_ms_per_step"] is None
+    assert plain[2].dtype == np.float32 and plain[2].shape == (80, 96, 3)
+    i = ARGS.index("--no-cpu")
+    full = [*ARGS[:i], "--cpu-frames", "1", *ARGS[i + 1:]]
+    img = str(tmp_path / "full.png")
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", *full, "--out-image", img,
+           "--full", "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    _check_line(d, 1)
+    assert d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0
+    assert d["detail"]["gather_ms_per_step"] > 0 and d["detail"]["gather_readback_ms_isolated"] > 0
+    image = np.load(tmp_path / "dump" / "image.npy")
+    assert image.dtype == np.float32 and image.shape == (80, 96, 3)
+    assert np.array_equal(image, plain[2] / np.float32(16))
+    assert open(img, "rb").read() == plain[1]
 
 
 def test_bench_single_process(tmp_path, plain):

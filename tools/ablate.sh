@@ -16,6 +16,7 @@ if [ "$MODE" = build ]; then
   ls $R/raytrace2_amd/lib/ablate; exit 0
 fi
 mkdir -p $R/gpurun_out
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the roofline's launch time is printed below
 for v in $VARIANTS; do
   name=${v%%:*}
   RT2_LIB=$R/raytrace2_amd/lib/ablate/$name.so timeout -k 10 200 python $R/bench.py --no-cpu --steps 2 --warmup 1 ${BENCH_ARGS:-} > $R/gpurun_out/ablate_$name.log 2>&1

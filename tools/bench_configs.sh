@@ -7,6 +7,7 @@ mkdir -p gpurun_out
 : > gpurun_out/configs.jsonl
 run() {  # label, args...
   local label=$1; shift
+  set -- --full "$@"  # each line carries its roofline
   timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --no-cpu --steps 1 --warmup 1 --stats-frames 2 "$@" > gpurun_out/cfg.log 2>&1
   local rc=$?
   local line=$(grep '^{' gpurun_out/cfg.log)

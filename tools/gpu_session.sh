@@ -4,7 +4,7 @@
 # failure, so nothing more touches the GPU after a fault, abort or time limit:
 #   tools/gpu_session.sh tests [bench] [bench20] [configs] [profile] [ab] [lines]
 #     tests     -m gpu suite (TESTS="tests/x.py ..." for a subset; PYTEST_TIMEOUT for the whole step)
-#     bench     bench.py --steps 3 (BENCH_ARGS appended)
+#     bench     bench.py --full --steps 3 (BENCH_ARGS appended)
 #     bench20   the driver's command: bench.py --gpus 1 --steps 20 --warmup 5 (BENCH_ARGS appended)
 #     configs   every BASELINE config + emulated splits (tools/bench_configs.sh -> configs.jsonl)
 #     profile   rocprofv3 trace + PMC passes of every config (tools/profile_all.sh)
@@ -24,7 +24,7 @@ for step in "$@"; do
       echo "pytest rc=$rc"; grep -E "passed|failed|error" gpurun_out/pytest_gpu.log | tail -3
       if [ $rc -ne 0 ]; then grep -E "^(FAILED|ERROR)|Error|assert" gpurun_out/pytest_gpu.log | head -20; stop tests $rc; fi ;;
     bench|bench20)
-      if [ $step = bench ]; then a="--steps 3 --warmup 1"; else a="--gpus 1 --steps 20 --warmup 5"; fi
+      if [ $step = bench ]; then a="--full --steps 3 --warmup 1"; else a="--gpus 1 --steps 20 --warmup 5"; fi
       timeout -k 10 ${BENCH_TIMEOUT:-400} python -u bench.py $a ${BENCH_ARGS:-} > gpurun_out/$step.log 2>&1
       rc=$?
       echo "$step rc=$rc"; grep '^{' gpurun_out/$step.log | cut -c1-1500

@@ -12,6 +12,7 @@ if [ -z "${NO_TESTS:-}" ]; then
   if [ $rc -ne 0 ]; then exit $rc; fi
 fi
 for args in "$@"; do
+  args="--full $args"  # the roofline's launch time is printed below
   timeout -k 10 300 python bench.py --no-cpu --steps ${STEPS:-2} --warmup 1 $args > gpurun_out/sweep_one.log 2>&1
   rc=$?
   line=$(grep '^{' gpurun_out/sweep_one.log)

@@ -7,6 +7,7 @@ LINES=gpurun_out/${LINES_NAME:-sweep}.jsonl
 : > $LINES
 for spec in "$@"; do
   envs="${spec%%--*}"; args="${spec#*--}"
+  args="--full $args"  # the roofline's launch time is printed below
   env $envs timeout -k 10 ${BENCH_TIMEOUT:-300} python -u bench.py --no-cpu $args > gpurun_out/sweep_one.log 2>&1
   rc=$?
   line=$(grep '^{' gpurun_out/sweep_one.log)
