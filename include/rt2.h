@@ -63,6 +63,10 @@ typedef struct {
                              * +-2^64 (rectangle quads, box boundaries, transforms about y); a launch
                              * refuses a camera beyond that (RT2_ERR_INVALID). 0: any camera renders */
   int box_steps;            /* MakeBox runs and MakeBox medium boundaries given the box-level test */
+  int hit_table_bytes;      /* size of the scene's hit table (the shading records of its threaded program's
+                             * quads, one flat record each, which the Cornell-box kernel stages in LDS); 0:
+                             * none (RT2_HIT_TABLE=0 at load, nested transforms, no quad, or a table too
+                             * large to stage without lowering the kernel's occupancy) */
 } rt2_scene_info;
 RT2_API int rt2_scene_get_info(const rt2_scene* scene, rt2_scene_info* out);
 /* Material table, 8 floats per material: type, albedo.xyz, fuzz, refraction_index, tex_idx, 0.
@@ -269,6 +273,10 @@ typedef struct {
    * fall back to the six-face run), wave visits of a flagged run and those in which the wave ran the six
    * faces for its uncertified lanes */
   uint64_t box_tests, box_certified, box_wave_visits, box_wave_runs;
+  /* bytes of the scene's hit table the last render launch staged in LDS; 0: that launch read the records
+   * from global memory (no table, a kernel that takes none, such as the counting kernels, or a table that
+   * would have lowered the kernel's occupancy) */
+  uint64_t hit_table_bytes;
 } rt2_stats;
 RT2_API int rt2_tracer_get_stats(rt2_tracer* tr, rt2_stats* out);
 /* The stats of GPU `part` of a multi-GPU tracer (part 0 of a one-GPU tracer is itself). */

@@ -31,6 +31,7 @@ int RenderBlockSize();
 int RenderVariant(uint32_t features);
 uint32_t RenderVariantFeatures(int v);
 size_t RenderLdsBytes(const RenderParams& p);
+bool RenderTakesHitTable(int variant, int mode, bool stats);
 bool WriteImage(const float* pixels, int w, int h, const std::string& path, bool png, std::string& err);
 hipError_t LaunchDeinterleave(const float* stacks, float* image, float* image_nc, uint8_t* pixels, int width, int height, int band_h,
                               int world, int max_rows, int frame_idx, hipStream_t stream);
@@ -62,6 +63,11 @@ struct rt2_tracer {
   void* d_lin = nullptr;
   void* d_lin_wide = nullptr;
   void* d_lind = nullptr;
+  void* d_hit = nullptr;        // hit table (rt2_layout.h HIT), hit_bytes long; null: the scene has none
+  uint32_t hit_bytes = 0;
+  int hit_key = -1;             // cached: the kernel variant asked whether the table keeps its occupancy
+  bool hit_fits = false;
+  uint32_t last_hit_bytes = 0;  // the table the last launch staged in LDS (0: none)
   uint32_t lin_len = 0;
   bool use_linear = true;
   uint32_t root = kRefNone;
@@ -436,6 +442,7 @@ int rt2_scene_get_info(const rt2_scene* s, rt2_scene_info* o) {
   o->linear_steps = (int)(c.lin.size() / 4);
   o->origins_bounded = c.origins_bounded ? 1 : 0;
   o->box_steps = c.box_steps;
+  o->hit_table_bytes = (int)(c.hit.size() * sizeof(float));
   return RT2_OK;
 }
 
@@ -606,6 +613,10 @@ int rt2_tracer_create(const rt2_scene* s, int device, rt2_tracer** out) {
     if ((rc = Upload(&t->d_lin_wide, c.lin_wide.data(), c.lin_wide.size() * sizeof(uint32_t))) != RT2_OK) return rc;
     if ((rc = Upload(&t->d_lind, c.lind.data(), c.lind.size() * sizeof(float))) != RT2_OK) return rc;
     t->lin_len = (uint32_t)(c.lin.size() / 4);
+    if (!c.hit.empty()) {
+      if ((rc = Upload(&t->d_hit, c.hit.data(), c.hit.size() * sizeof(float))) != RT2_OK) return rc;
+      t->hit_bytes = (uint32_t)(c.hit.size() * sizeof(float));
+    }
   }
   HIP_TRY(hipMalloc(&t->d_work, 128));
   HIP_TRY(hipMalloc(&t->d_clock, 2 * sizeof(unsigned long long) * kClockRing));
@@ -621,7 +632,7 @@ int rt2_tracer_create(const rt2_scene* s, int device, rt2_tracer** out) {
   t->scene_bytes = c.nodes.size() * sizeof(float) + std::max<size_t>(mats.size(), 8) * sizeof(float) +
                    c.textures.size() * sizeof(float) + c.perlin_vec.size() * sizeof(float) +
                    c.perlin_perm.size() * sizeof(int) + c.lin.size() * sizeof(uint32_t) +
-                   c.lin_wide.size() * sizeof(uint32_t) + c.lind.size() * sizeof(float) + 128 +
+                   c.lin_wide.size() * sizeof(uint32_t) + c.lind.size() * sizeof(float) + t->hit_bytes + 128 +
                    2 * sizeof(unsigned long long) * kClockRing + kStatsSlots * sizeof(unsigned long long);
   t->root = c.root;
   t->node_records = (uint32_t)(c.nodes.size() / 4);
@@ -688,6 +699,7 @@ void rt2_tracer_destroy(rt2_tracer* t) {
   (void)hipFree(t->d_lin);
   (void)hipFree(t->d_lin_wide);
   (void)hipFree(t->d_lind);
+  (void)hipFree(t->d_hit);
   (void)hipFree(t->d_work);
   (void)hipFree(t->d_stats);
   for (auto& sl : t->slots) {
@@ -1113,6 +1125,20 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
   }
   p.lds_nodes = lds ? t->node_records : hot;
   p.lds_partial = (!lds && hot) ? 1u : 0u;
+  // The hit table in LDS, for the kernels that take it (render.hip HitTable()), when the kernel keeps
+  // the occupancy it has without the table: the runtime is asked with and without it
+  if (p.lin_len && t->d_hit && t->flat_xforms && RenderTakesHitTable(variant, kModeLinear, counting)) {
+    if (t->hit_key != variant) {
+      t->hit_fits = RenderBlocksPerCU(variant, kModeLinear, counting, t->hit_bytes) >=
+                    RenderBlocksPerCU(variant, kModeLinear, counting, 0);
+      t->hit_key = variant;
+    }
+    if (t->hit_fits) {
+      p.hit_table = t->d_hit;
+      p.hit_bytes = t->hit_bytes;
+    }
+  }
+  t->last_hit_bytes = p.hit_bytes;
   // resident lanes of this kernel instantiation (occupancy query cached: it costs far more than
   // a one-frame launch)
   const size_t lds_bytes = RenderLdsBytes(p);
@@ -1607,6 +1633,7 @@ int rt2_tracer_get_stats(rt2_tracer* t, rt2_stats* o) {
       sum.box_certified += s.box_certified;
       sum.box_wave_visits += s.box_wave_visits;
       sum.box_wave_runs += s.box_wave_runs;
+      sum.hit_table_bytes = std::max(sum.hit_table_bytes, s.hit_table_bytes);
       sum.launches = std::max(sum.launches, s.launches);
       sum.kernel_ms = std::max(sum.kernel_ms, s.kernel_ms);
       sum.launch_ms_sum = std::max(sum.launch_ms_sum, s.launch_ms_sum);
@@ -1644,6 +1671,7 @@ int rt2_tracer_get_stats(rt2_tracer* t, rt2_stats* o) {
   o->box_certified = s[StatsCounters::kBoxCertified];
   o->box_wave_visits = s[StatsCounters::kBoxWaveVisits];
   o->box_wave_runs = s[StatsCounters::kBoxWaveRuns];
+  o->hit_table_bytes = t->last_hit_bytes;
   for (int k = 0; k < 4; k++) o->stamps[k] = s[StatsCounters::kStamps + k];
   for (int k = 0; k < 8; k++) o->diag[k] = s[StatsCounters::kDiag + k];
   o->launches = t->launches;

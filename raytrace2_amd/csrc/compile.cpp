@@ -843,6 +843,67 @@ void PackMaterials(const Scene& s, CompiledScene& out) {
   }
 }
 
+// The hit table of the threaded program (rt2_layout.h HIT): bit copies of the words resolve_hit,
+// the material fetch and a solid texture's tex_value read for each quad step's primitive, at the
+// primitive's own record offset, and every XFORM record as it stands. Leaves out.hit empty when the
+// scene gets none: no program, nested transforms, no quad, a table above kHitTableBytesMax, or
+// RT2_HIT_TABLE=0 in the environment.
+void BuildHitTable(CompiledScene& out) {
+  out.hit.clear();
+  const char* e = getenv("RT2_HIT_TABLE");
+  if ((e && atoi(e) == 0) || out.lin.empty() || out.lin_xform_depth > 1) return;
+  if (out.lind.size() * sizeof(float) > kHitTableBytesMax) return;
+  std::vector<float> hit(out.lind.size(), 0.0f);
+  const size_t n = out.lin.size() / 4, n_mat = out.materials.size() / 8, n_tex = out.textures.size() / 12;
+  bool any = false;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t kind = out.lin[4 * i];
+    const size_t off = 4 * (size_t)out.lin[4 * i + 2];
+    if (kind == kXform)
+      std::copy(out.lind.begin() + (long)off, out.lind.begin() + (long)off + 4 * kXformRecords, hit.begin() + (long)off);
+    if (kind == kQuad) {
+      // (a quad step's skip word starts with its own axis code: the codes of the run that begins there)
+      const uint32_t code = out.lin[4 * i + 1] & 7u;
+      const float* r = &out.lind[off];
+      float* h = &hit[off];
+      uint32_t mat, flags = 0;
+      if (code >= 4 && code <= 6) {  // QUADAA
+        std::copy(r + 8, r + 11, h);
+        h[3] = r[17];
+        uint32_t xf;
+        memcpy(&xf, &r[17], 4);
+        if (xf != kRefNone) {
+          std::copy(r + 12, r + 15, h + 4);
+          flags |= kHitWorldNormal;
+        }
+        memcpy(&mat, &r[15], 4);
+      } else {  // QUAD
+        std::copy(r, r + 3, h);
+        h[3] = r[15];
+        memcpy(&mat, &r[7], 4);
+      }
+      if (mat >= n_mat) return;
+      const float* m = &out.materials[8 * (size_t)mat];
+      std::copy(m, m + 8, h + 8);
+      uint32_t type, tex;
+      memcpy(&type, &m[0], 4);
+      memcpy(&tex, &m[6], 4);
+      if ((type == kMatTexture || type == kMatDiffuseLight || type == kMatIsotropic) && tex < n_tex) {
+        const float* t = &out.textures[12 * (size_t)tex];
+        uint32_t ttype;
+        memcpy(&ttype, &t[0], 4);
+        if (ttype == kTexSolid) {
+          std::copy(t, t + 4, h + 16);
+          flags |= kHitSolid;
+        }
+      }
+      memcpy(&h[7], &flags, 4);
+      any = true;
+    }
+  }
+  if (any) out.hit.swap(hit);
+}
+
 void PackTextures(const Scene& s, CompiledScene& out) {
   for (const TextureDesc& t : s.textures) {
     uint32_t u[12] = {0};
@@ -1034,6 +1095,7 @@ bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool
   }
   PackMaterials(s, out);
   PackTextures(s, out);
+  BuildHitTable(out);
   if (out.spheres) out.features |= kFeatSphere;
   for (const Obj& o : s.objs)
     if (o.kind == kSphere && !(o.disp.x == 0.0f && o.disp.y == 0.0f && o.disp.z == 0.0f)) out.features |= kFeatMotion;

@@ -87,7 +87,8 @@ constexpr int kBlock = 256;
 #define RT2_MIN_WAVES_PER_EU 0  // 0: per-variant occupancy targets (kMinWaves below)
 #endif
 
-extern __shared__ float4 s_dyn[];  // [lds_nodes scene records][stack_depth * kBlock stack words]
+extern __shared__ float4 s_dyn[];  // [lds_nodes scene records][stack_depth * kBlock stack words], or
+                                   // (threaded kernels with HitTable()) the launch's hit table
 
 struct f3 {
   float x, y, z;
@@ -272,6 +273,15 @@ __device__ __forceinline__ u32x4 karg4() {
   static_assert(kOff % 4 == 0, "dword-aligned");
   u32x4 v;
   asm volatile("s_load_dwordx4 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
+               : "=s"(v)
+               : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(kOff));
+  return v;
+}
+template <uint32_t kOff>
+__device__ __forceinline__ uint32_t karg1() {
+  static_assert(kOff % 4 == 0, "dword-aligned");
+  uint32_t v;
+  asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
                : "=s"(v)
                : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(kOff));
   return v;
@@ -1372,6 +1382,9 @@ struct HitShade {
   bool front;
   float4 m0, m1;
   uint32_t type;
+  // m0.yzw is the colour of the material's solid texture instead of its albedo (a hit resolved from
+  // the hit table, rt2_layout.h kHitSolid: such a material never reads its albedo): no tex_value
+  bool solid;
 };
 
 struct HitRef {
@@ -1555,7 +1568,7 @@ constexpr bool BoxOn() {
 }
 template <uint32_t F, bool kStats, class W, class G>
 __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wray, float time, G& path, HitRef& h,
-                                             lds_u32* cand, lds_u32* xray, Counters& cnt) {
+                                             lds_u32* cand, lds_u32* xray, Counters& cnt, bool tab = false) {
   const Nodes<kModeLinear> N{reinterpret_cast<const float4*>(P.lind)};  // boundaries / nested xforms
   const void* recs = P.lind;
   // the world ray's reciprocal stays in registers for the transforms' exits to world space (three
@@ -1949,8 +1962,14 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   h.t = tmax;
   h.prim = prim;
   if constexpr (Has<F, kFeatXform>()) {
-    if (prim != kRefNone && (prim >> 28) == kQuad) h.xf = N.word((prim & kOffsetMask) + 3u, 3);
-    if (prim != kRefNone && (prim >> 28) == kQuadAA) h.xf = N.word((prim & kOffsetMask) + 4u, 1);
+    // (tab, wave-uniform: the hit is resolved from the hit table, whose record holds the transform)
+    if (!tab) {
+      if (prim != kRefNone && (prim >> 28) == kQuad) h.xf = N.word((prim & kOffsetMask) + 3u, 3);
+      if (prim != kRefNone && (prim >> 28) == kQuadAA) h.xf = N.word((prim & kOffsetMask) + 4u, 1);
+    }
+#if RT2_HIT_TABLE_KERNEL == 2  // stage A probe: the transform's ref is a hop of its own, as in the chain
+    else if (prim != kRefNone) h.xf = bits(s_dyn[prim & kOffsetMask].w);
+#endif
   }
   return prim != kRefNone;
 }
@@ -2026,6 +2045,65 @@ __device__ __forceinline__ void resolve_hit(const Nodes<kMode>& N, const HitRef&
       x = bits(c1.w);  // the parent transform
     }
   }
+}
+
+// resolve_hit and the material fetch for a quad hit from the hit table staged in LDS (rt2_layout.h HIT;
+// kernels with HitTable(), whose transforms do not nest and whose trace kept the hit's model-space
+// ray): one address, the hit's record offset, and five 16-byte LDS reads at constant offsets give the
+// normals, the transform's ref, the material's two records and its solid texture's colour; the
+// transform's entry is one more address. The global-memory path reaches the same words through four
+// dependent loads (the transform's ref in the trace's tail, the quad's records, the material, the
+// texture). The same float operations in the same order as resolve_hit.
+template <uint32_t F>
+__device__ __forceinline__ HitShade resolve_hit_tab(const HitRef& h, f3 wo, f3 wd, const lds_u32* xray) {
+  const float4* R = s_dyn + (h.prim & kOffsetMask);
+#if RT2_HIT_TABLE_KERNEL == 2
+  // Stage A probe: the chain's structure kept in LDS. The transform's ref came with the
+  // trace's tail, the material's records are read at an address that waits for the quad's record and
+  // the texture's at one that waits for the material, as the tables' indices would make them.
+  const float4 r0 = R[0], r1 = R[1];
+  uint32_t dep = bits(r1.w);
+  asm volatile("v_and_b32 %0, 0, %0" : "+v"(dep));
+  const float4* M = R + dep;
+  const float4 m0 = M[2], m1 = M[3];
+  uint32_t dep2 = bits(m1.z);
+  asm volatile("v_and_b32 %0, 0, %0" : "+v"(dep2));
+  const float4 t0 = (M + dep2)[4];
+  const uint32_t xf = h.xf, flags = bits(r1.w);
+#else
+  const float4 r0 = R[0], r1 = R[1], m0 = R[2], m1 = R[3], t0 = R[4];
+  const uint32_t xf = bits(r0.w), flags = bits(r1.w);
+#endif
+  f3 o = wo, d = wd;
+  if (xf != kRefNone) {  // the trace kept the hit's model-space ray
+    o = pk_ld3(xray, 0u);
+    d = pk_ld3(xray, 3u);
+  }
+  f3 p = o + d * h.t;
+  const f3 qn = xyz(r0);
+  const bool front = dot(d, qn) < 0.0f;
+  f3 n = front ? qn : -qn;
+  if (xf != kRefNone) {  // back through the one enclosing transform (Transform.cpp:85-86)
+    const float4* X = s_dyn + (xf & kOffsetMask);
+    const float4 c2 = X[2], a0 = X[4], a1 = X[5], a2 = X[6], a3 = X[7];
+    if (bits(c2.w) == kXformYAxis) {  // M's +-0 products left out
+      p = mk(a0.x * p.x + (a2.x * p.z + a3.x), a1.y * p.y + a3.y, a0.z * p.x + (a2.z * p.z + a3.z));
+    } else {
+      p = mk((a0.x * p.x + a1.x * p.y) + (a2.x * p.z + a3.x), (a0.y * p.x + a1.y * p.y) + (a2.y * p.z + a3.y),
+             (a0.z * p.x + a1.z * p.y) + (a2.z * p.z + a3.z));
+    }
+    if (flags & kHitWorldNormal) {  // the quad's world normal from the record (compile.cpp WorldNormal)
+      const f3 wn = xyz(r1);
+      n = front ? wn : -wn;
+    } else {
+      const float4 c0 = X[0], c1 = X[1];
+      n = normalize(mk(c0.x * n.x + c0.y * n.y + c0.z * n.z, c1.x * n.x + c1.y * n.y + c1.z * n.z,
+                       c2.x * n.x + c2.y * n.y + c2.z * n.z));
+    }
+  }
+  const bool solid = (flags & kHitSolid) != 0u;
+  return HitShade{p, n, front, make_float4(m0.x, solid ? t0.y : m0.y, solid ? t0.z : m0.z, solid ? t0.w : m0.w),
+                  m1, bits(m0.x), solid};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2210,6 +2288,19 @@ template <uint32_t F, int kMode, bool kStats>
 constexpr bool Ring() {
   return LdsRng<F, kMode, kStats>() && !Park<F, kMode, kStats>() && !BoxPair<F, kMode>();
 }
+// Kernels that stage the launch's hit table (rt2_layout.h HIT) in dynamic LDS and resolve hits from it
+// (resolve_hit_tab): the ring kernels with transforms, i.e. the Cornell box kernel, whose trace keeps
+// the hit's model-space ray. The Cornell volume kernel has no LDS room for it, and the sphere kernels
+// spend under 1 % of their time resolving hits. A launch without a table (RenderParams::hit_bytes 0)
+// takes the global-memory path in these kernels too.
+#ifndef RT2_HIT_TABLE_KERNEL
+#define RT2_HIT_TABLE_KERNEL 1  // 0: no kernel takes the table; 2: the stage A probe (resolve_hit_tab)
+#endif
+template <uint32_t F, int kMode, bool kStats>
+constexpr bool HitTable() {
+  return RT2_HIT_TABLE_KERNEL && Ring<F, kMode, kStats>() && Has<F, kFeatXform>() &&
+         !Has<F, kFeatSphere | kFeatMedium>();
+}
 template <uint32_t F, int kMode, bool kStats>
 constexpr uint32_t StageGroup() {
   if (kMode != kModeLinear || kStats || Park<F, kMode, kStats>()) return 0u;
@@ -2231,6 +2322,14 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
     const float4* src = reinterpret_cast<const float4*>(P.nodes);
     for (uint32_t i = threadIdx.x; i < P.lds_nodes; i += kBlock) s_dyn[i] = src[i];
     __syncthreads();
+  }
+  constexpr bool kHitTab = HitTable<F, kMode, kStats>();
+  if constexpr (kHitTab) {
+    if (P.hit_bytes != 0u) {  // wave-uniform; the table is whole float4 records (RenderLdsBytes)
+      const float4* src = reinterpret_cast<const float4*>(P.hit_table);
+      for (uint32_t i = threadIdx.x; i < P.hit_bytes / 16u; i += kBlock) s_dyn[i] = src[i];
+      __syncthreads();
+    }
   }
   uint32_t* stk = reinterpret_cast<uint32_t*>(s_dyn + (kLds ? P.lds_nodes : 0u)) + threadIdx.x;
   const int lane = (int)__lane_id();
@@ -2406,6 +2505,20 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
         bool front;
         uint32_t mat;
         if constexpr (kMode == kModeLinear) {
+          if constexpr (kHitTab) {
+            if (karg1<RT2_KOFF(hit_bytes)>() != 0u) {  // wave-uniform: the hit table is in LDS
+#if RT2_EXP_TWICE & 1
+              {
+                f3 ro2 = ro;
+                asm volatile("" : "+v"(ro2.x), "+v"(ro2.y), "+v"(ro2.z));
+                const HitShade h2 = resolve_hit_tab<F>(h, ro2, rd, lp + 64u * kXrayP);
+                asm volatile("" ::"v"(h2.hp.x), "v"(h2.hp.y), "v"(h2.hp.z), "v"(h2.hn.x), "v"(h2.hn.y), "v"(h2.hn.z),
+                             "v"(h2.type), "v"((int)h2.front));
+              }
+#endif
+              return resolve_hit_tab<F>(h, ro, rd, lp + 64u * kXrayP);
+            }
+          }
           resolve_hit<F>(Nodes<kModeLinear>{reinterpret_cast<const float4*>(P.lind)}, h, ro, rd, rtime, hp, hn, front,
                          mat, kXray ? lp + 64u * kXrayP : nullptr, kXray && P.flat_xforms != 0u);
 #if RT2_EXP_TWICE & 1
@@ -2424,7 +2537,7 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
           resolve_hit<F>(N, h, ro, rd, rtime, hp, hn, front, mat);
         }
         const float4 m0 = S.materials[2 * mat], m1 = S.materials[2 * mat + 1];
-        return HitShade{hp, hn, front, m0, m1, bits(m0.x)};
+        return HitShade{hp, hn, front, m0, m1, bits(m0.x), false};
     };
     auto shade = [&](const HitShade& hs, const ShadeArgs& S) {
         const f3 hp = hs.hp, hn = hs.hn;
@@ -2432,7 +2545,7 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
         const float4 m0 = hs.m0, m1 = hs.m1;
         const uint32_t type = hs.type;
         if (type == kMatDiffuseLight) {
-          color = thr * tex_value<F>(S, bits(m1.z), hp);
+          color = thr * (hs.solid ? mk(m0.y, m0.z, m0.w) : tex_value<F>(S, bits(m1.z), hp));
           done = true;
         } else {
           f3 att, dir;
@@ -2469,11 +2582,11 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
             dir = refl ? reflect(ud, hn) : refract(ud, hn, ri);
           } else if (Has<F, kFeatMedium>() && type == kMatIsotropic) {
             dir = ru;
-            att = tex_value<F>(S, bits(m1.z), hp);
+            att = hs.solid ? mk(m0.y, m0.z, m0.w) : tex_value<F>(S, bits(m1.z), hp);
           } else {  // Lambertian / Texture
             dir = hn + ru;
             if (near_zero(dir)) dir = hn;
-            att = (type == kMatLambertian) ? mk(m0.y, m0.z, m0.w) : tex_value<F>(S, bits(m1.z), hp);
+            att = (type == kMatLambertian || hs.solid) ? mk(m0.y, m0.z, m0.w) : tex_value<F>(S, bits(m1.z), hp);
           }
           thr = thr * att;
           ro = hp;
@@ -2506,7 +2619,8 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
         rd = pk_ld3(pk, kPkD);
       } else if constexpr (kMode == kModeLinear) {
         hit = trace_linear<F, kStats>(P, RegRay{ro, rd}, rtime, path, h, lp + 64u * kCandP,
-                                      kXray ? lp + 64u * kXrayP : nullptr, cnt);
+                                      kXray ? lp + 64u * kXrayP : nullptr, cnt,
+                                      kHitTab && karg1<RT2_KOFF(hit_bytes)>() != 0u);
 #if RT2_EXP_TRACE_TWICE
         {
           f3 ro2 = ro;
@@ -2535,7 +2649,7 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
       // the hit lanes' records and materials first, so the bounce's one Philox site (PathT kRing)
       // knows which lanes scatter and which start their next frame
       HitShade hs{mk(0, 0, 0), mk(0, 0, 0), false, make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0),
-                  kMatDiffuseLight};
+                  kMatDiffuseLight, false};
       const ShadeArgs S = shade_args();
       if (hit) hs = resolve(S);
       const bool scatter = hit && hs.type != kMatDiffuseLight;
@@ -3001,8 +3115,20 @@ int RenderMode(const RenderParams& p) {
   return p.lds_partial ? kModeStackHybrid : kModeStackLds;
 }
 
+bool RenderTakesHitTable(int variant, int mode, bool stats) {
+  if (variant < 0 || variant >= dev::kNumVariants || mode != kModeLinear || stats) return false;
+  switch (variant) {
+    case 0: return dev::HitTable<dev::kVariants[0], kModeLinear, false>();
+    case 1: return dev::HitTable<dev::kVariants[1], kModeLinear, false>();
+    case 2: return dev::HitTable<dev::kVariants[2], kModeLinear, false>();
+    case 3: return dev::HitTable<dev::kVariants[3], kModeLinear, false>();
+    case 4: return dev::HitTable<dev::kVariants[4], kModeLinear, false>();
+  }
+  return false;
+}
+
 size_t RenderLdsBytes(const RenderParams& p) {
-  if (p.lin_len) return 0;
+  if (p.lin_len) return p.hit_bytes;  // the hit table (capi.cpp sets it only for kernels that take it)
   return (size_t)p.lds_nodes * 16 + (size_t)p.stack_depth * dev::kBlock * 4;
 }
 

@@ -123,6 +123,34 @@ constexpr uint32_t kBoundaryAAMax = 6;
 
 constexpr int kBvhRecords = 2, kQuadRecords = 5, kSphereRecords = 2, kXformRecords = 8, kMediumRecords = 1;
 
+// Hit table (threaded programs; CompiledScene::hit, RenderParams::hit_table): what the shading of a
+// closest hit reads, flattened per primitive, for the kernels that stage it in LDS (render.hip
+// HitTable()). It has the shape of the record stream `lind`: a hit record is as long as a quad's
+// record (kQuadRecords float4), so the record offset a hit carries addresses the table as it stands
+// (the index map from record offsets to slots is the identity: no load of its own), and a transform's
+// entry is its XFORM record. Every word is a bit copy of a word the global-memory path reads:
+//  HIT   : at the offset of each QUAD / QUADAA record of a quad step
+//          (n.xyz, xform ref bits)       the model normal; the enclosing XFORM's lind ref or kRefNone
+//          (world n.xyz, flags bits)     QUADAA words 12-14 (compile.cpp WorldNormal) with kHitWorldNormal
+//                                        for a QUADAA quad under a transform, else zeros
+//          (type bits, albedo.xyz)       the material's first record
+//          (fuzz, ri, tex_idx bits, 1/ri) and its second
+//          (tex type bits, colour.xyz)   with kHitSolid: the first record of the material's texture,
+//                                        which is solid, for a material that reads its texture
+//                                        (texture, diffuse light, isotropic); else zeros
+//  XFORM : at the offset of each XFORM record, the 8 records as they stand (invM's columns with the
+//          parent ref and the pattern, M's columns)
+// Every other word is 0. SPHERE and MEDIUM records get no hit record: the kernels that read the table
+// have neither. Built only for programs whose transforms do not nest (RenderParams::flat_xforms) and
+// whose table is at most kHitTableBytesMax; RT2_HIT_TABLE=0 at scene load builds none.
+constexpr uint32_t kHitWorldNormal = 1u, kHitSolid = 2u;
+constexpr int kHitRecords = kQuadRecords;
+// The LDS a 256-thread workgroup of the kernels that take the table can spare at 8 workgroups per CU
+// beside their 14 wave planes (160 KB / 8 - 14 KB): no larger table could be staged without lowering
+// the occupancy, so none is built or uploaded. A launch still asks the runtime whether the table it
+// has keeps the kernel's occupancy and goes without it otherwise (capi.cpp LaunchFrames).
+constexpr uint32_t kHitTableBytesMax = 6144;
+
 // Materials: 2 records each: (type bits, albedo.xyz) (fuzz, refraction_index, tex_idx bits, 1/ri)
 enum MaterialType : uint32_t {
   kMatMetal = 0,
@@ -291,6 +319,11 @@ struct RenderParams {
   // time is then measured from its first wave to its last one, whatever it waited for in its queue
   // (with two launch slots the next launch is queued while the previous one still holds the CUs).
   unsigned long long* launch_clock;
+  // The hit table (above) and its size in bytes for this launch: the kernels that take it copy it into
+  // dynamic LDS and resolve hits from there. 0: none (no table, or it would lower the occupancy); the
+  // kernel reads the records from lind, materials and textures.
+  const void* hit_table;
+  uint32_t hit_bytes;
 };
 constexpr int kClockRing = 512;  // launch-clock pairs per tracer (drained at half)
 

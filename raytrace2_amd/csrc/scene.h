@@ -157,6 +157,7 @@ struct CompiledScene {
   std::vector<float> lind;        // records of the program's steps, in program order (float4)
   std::vector<uint32_t> lin_wide; // 16 words per step: the lin entry + the first 12 words of its record,
                                   // then one kProgramEnd entry
+  std::vector<float> hit;         // hit table (rt2_layout.h HIT), as long as lind; empty: none
 };
 // accelerate_lists = false keeps every list a linear child loop (the reference's own order).
 bool CompileScene(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists = true);
