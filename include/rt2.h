@@ -283,6 +283,48 @@ RT2_API int rt2_tracer_get_stats(rt2_tracer* tr, rt2_stats* out);
 RT2_API int rt2_tracer_part_stats(rt2_tracer* tr, int part, rt2_stats* out);
 RT2_API int rt2_tracer_reset_stats(rt2_tracer* tr);
 
+/* ---- Noise estimate and render-until-converged (DESIGN.md "Noise estimate") ----
+ * Opt-in "moments": with them on, the pass that sums a launch's samples in frame order also sums
+ * their squares (float32, q = q + s * s per channel, each operation rounded on its own), so both sums
+ * are defined in frame order and do not depend on how frames were split into launches. With moments
+ * off nothing changes. From n = FrameIdx() >= 2 frames and a pixel's sums a_c (accumulation) and q_c
+ * (moment2), in double with every operation rounded on its own:
+ *   mean_c = a_c / n;  ss_c = q_c - a_c * mean_c, 0 unless > 0
+ *   sem_c  = (float) sqrt(ss_c / ((double)n * (n - 1)))          standard error of the mean
+ *   err    = sqrt((sem_r^2 + sem_g^2 + sem_b^2) / 3) / max(1, (mean_r + mean_g + mean_b) / 3)
+ * A pixel with a non-finite a_c or q_c has sem = err = +inf; it counts as `nonfinite`, never as
+ * `below`, and is left out of sum_sq and max_err. The scalars are reduced without atomics in a fixed
+ * order: the same image gives the same bytes every time.
+ * enable_moments: like enable_ray_counts it synchronises, reallocates and resets the frame index and
+ *   the accumulation. Reset / OnResize zero the sums of squares too.
+ * moments / standard_error / noise: readbacks (they launch queued frames and synchronise);
+ *   RT2_ERR_INVALID with moments off, and for standard_error / noise with fewer than 2 frames.
+ * render_until: renders in steps of `check_every` frames (0: one stratum sweep, sqrt_spp^2 frames; the
+ *   last step shortened to land on max_frames) while FrameIdx() < max_frames; after each step with
+ *   FrameIdx() >= max(min_frames, 2) it takes the noise (threshold = target_rms) and stops when
+ *   rms <= target_rms and nonfinite == 0. FrameIdx() counts from the last reset, so an accumulation
+ *   already begun is continued. `out` receives the last estimate (frames = 0: none could be taken).
+ *   The image afterwards is, bit for bit, that of Render(FrameIdx()).
+ * Multi-GPU: a create_multi tracer forwards enable_moments; moments / standard_error return the full
+ *   image (each GPU's rows placed on the host, as ray_counts); noise adds the GPUs' pixels, below,
+ *   nonfinite and sum_sq, takes the largest max_err and recomputes rms. A joined tracer (one process
+ *   per GPU) reports its own bands: the additive fields are what the caller all-reduces. */
+typedef struct {
+  int64_t frames;     /* n the estimate rests on */
+  uint64_t pixels;    /* local pixels (a multi-GPU tracer: the whole image) */
+  uint64_t below;     /* pixels with err <= threshold */
+  uint64_t nonfinite;
+  double sum_sq;      /* sum of err^2 over the finite pixels */
+  float max_err;      /* largest finite err */
+  float rms;          /* sqrt(sum_sq / (pixels - nonfinite)), 0 when that is 0 */
+} rt2_noise;
+RT2_API int rt2_tracer_enable_moments(rt2_tracer* tr, int on);
+RT2_API int rt2_tracer_moments(rt2_tracer* tr, float* out);        /* raw float3 sums of squares, local pixels */
+RT2_API int rt2_tracer_standard_error(rt2_tracer* tr, float* out); /* float3 sem per local pixel */
+RT2_API int rt2_tracer_noise(rt2_tracer* tr, float threshold, rt2_noise* out);
+RT2_API int rt2_tracer_render_until(rt2_tracer* tr, float target_rms, int min_frames, int max_frames, int check_every,
+                                    rt2_noise* out);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -212,6 +212,33 @@ class RayTracer {
   Camera* camera = nullptr;
   size_t max_depth = 50;
 
+  // Noise estimate (rt2.h "Noise estimate and render-until-converged"): sums of the samples' squares
+  // beside the accumulation, the standard error per pixel, the image's noise scalars, and rendering
+  // until the rms noise is at most a target. EnableMoments resets the frame like OnResize.
+  void EnableMoments(bool on = true) { Check(rt2_tracer_enable_moments(t_.get(), on ? 1 : 0)); }
+  [[nodiscard]] std::vector<vec3> Moments() const {
+    std::vector<vec3> out((size_t)dims_.x * LocalRows());
+    Check(rt2_tracer_moments(t_.get(), reinterpret_cast<float*>(out.data())));
+    return out;
+  }
+  [[nodiscard]] std::vector<vec3> StandardError() const {
+    std::vector<vec3> out((size_t)dims_.x * LocalRows());
+    Check(rt2_tracer_standard_error(t_.get(), reinterpret_cast<float*>(out.data())));
+    return out;
+  }
+  [[nodiscard]] rt2_noise Noise(float threshold = 0.f) const {
+    rt2_noise n{};
+    Check(rt2_tracer_noise(t_.get(), threshold, &n));
+    return n;
+  }
+  rt2_noise RenderUntil(const Scene& /*scene*/, float target_rms, int max_frames, int min_frames = 0,
+                        int check_every = 0) {
+    Sync();
+    rt2_noise n{};
+    Check(rt2_tracer_render_until(t_.get(), target_rms, min_frames, max_frames, check_every, &n));
+    return n;
+  }
+
   rt2_tracer* handle() const { return t_.get(); }
   [[nodiscard]] int NumGpus() const { return rt2_tracer_n_gpus(t_.get()); }
 

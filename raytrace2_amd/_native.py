@@ -82,6 +82,18 @@ class Stats(ctypes.Structure):
         return d
 
 
+class Noise(ctypes.Structure):
+    """rt2_noise."""
+    _fields_ = [("frames", ctypes.c_int64), ("pixels", ctypes.c_uint64), ("below", ctypes.c_uint64),
+                ("nonfinite", ctypes.c_uint64), ("sum_sq", ctypes.c_double), ("max_err", ctypes.c_float),
+                ("rms", ctypes.c_float)]
+
+    def as_dict(self):
+        return {"frames": int(self.frames), "pixels": int(self.pixels), "below": int(self.below),
+                "nonfinite": int(self.nonfinite), "sum_sq": float(self.sum_sq), "max_err": float(self.max_err),
+                "rms": float(self.rms)}
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Every RT2_API function name declared in include/rt2.h."""
     txt = open(header).read()
@@ -173,6 +185,11 @@ def _load():
         "rt2_band_rows_max": (i32, [i32, i32, i32]),
         "rt2_deinterleave_host": (i32, [fp, fp, i32, i32, i32, i32, i32, i32]),
         "rt2_runtime_info": (i32, [ctypes.c_char_p, ctypes.c_size_t]),
+        "rt2_tracer_enable_moments": (i32, [vp, i32]),
+        "rt2_tracer_moments": (i32, [vp, fp]),
+        "rt2_tracer_standard_error": (i32, [vp, fp]),
+        "rt2_tracer_noise": (i32, [vp, f32, ctypes.POINTER(Noise)]),
+        "rt2_tracer_render_until": (i32, [vp, f32, i32, i32, i32, ctypes.POINTER(Noise)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error
@@ -187,7 +204,6 @@ def _load():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
-    del f32
     return L
 
 

@@ -18,13 +18,17 @@
 #include <vector>
 
 #include "../../include/rt2.h"
+#include "noise.h"
 #include "scene.h"
 
 namespace rt2 {
 hipError_t LaunchRender(const RenderParams& p, int variant, bool stats, int grid, hipStream_t stream);
 int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes);
-hipError_t LaunchAccumulate(const float* samples, float* accum, uint8_t* pixels, uint32_t npix, int n_frames,
-                            int frame_idx, hipStream_t stream);
+hipError_t LaunchAccumulate(const float* samples, float* accum, float* moment2, uint8_t* pixels, uint32_t npix,
+                            int n_frames, int frame_idx, hipStream_t stream);
+uint32_t NoiseBlocks(uint32_t npix);
+hipError_t LaunchNoise(const float* accum, const float* moment2, float* sem, NoisePartial* partials, uint32_t npix,
+                       int64_t n_frames, float threshold, hipStream_t stream);
 hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsigned long long* d_out, hipStream_t stream);
 int RenderMode(const RenderParams& p);
 int RenderBlockSize();
@@ -95,6 +99,12 @@ struct rt2_tracer {
   uint8_t* d_pixels = nullptr;
   uint32_t* d_ray_counts = nullptr;
   bool ray_counts_on = false;
+  // moments (rt2_tracer_enable_moments): float3 sums of the samples' squares per local pixel, summed in
+  // frame order by the accumulate pass; d_noise holds the noise kernel's per-workgroup partials
+  float* d_moment2 = nullptr;
+  bool moments_on = false;
+  NoisePartial* d_noise = nullptr;
+  size_t noise_blocks = 0;
   uint32_t* d_work = nullptr;  // one work counter per launch slot (words 0 and 16)
   unsigned long long* d_stats = nullptr;
   bool stats_on = false;
@@ -259,9 +269,14 @@ void FreeFrame(rt2_tracer* t) {
   (void)hipFree(t->d_accum);
   (void)hipFree(t->d_pixels);
   (void)hipFree(t->d_ray_counts);
+  (void)hipFree(t->d_moment2);
+  (void)hipFree(t->d_noise);
   t->d_accum = nullptr;
   t->d_pixels = nullptr;
   t->d_ray_counts = nullptr;
+  t->d_moment2 = nullptr;
+  t->d_noise = nullptr;
+  t->noise_blocks = 0;
   FreeImage(t);
 }
 
@@ -269,7 +284,8 @@ void FreeFrame(rt2_tracer* t) {
 // launch slots' sample buffers and chunk tables, and a root's gathered image.
 size_t DeviceBytes(const rt2_tracer* t) {
   const size_t n = (size_t)t->width * (size_t)AllocRows(t);
-  size_t b = t->scene_bytes + (t->d_accum ? n * 12 : 0) + (t->d_pixels ? n * 4 : 0) + (t->d_ray_counts ? n * 4 : 0);
+  size_t b = t->scene_bytes + (t->d_accum ? n * 12 : 0) + (t->d_pixels ? n * 4 : 0) + (t->d_ray_counts ? n * 4 : 0) +
+             (t->d_moment2 ? n * 12 : 0) + t->noise_blocks * sizeof(NoisePartial);
   for (const auto& sl : t->slots) b += sl.samples_bytes + sl.chunks_bytes;
   if (t->d_image) b += t->stacks_bytes + t->image_pixels * (12 + 12 + 4);
   return b;
@@ -284,6 +300,7 @@ int Realloc(rt2_tracer* t) {
   HIP_TRY(hipMalloc(&t->d_accum, n * 3 * sizeof(float)));
   HIP_TRY(hipMalloc(&t->d_pixels, n * 4));
   if (t->ray_counts_on) HIP_TRY(hipMalloc(&t->d_ray_counts, n * sizeof(uint32_t)));
+  if (t->moments_on) HIP_TRY(hipMalloc(&t->d_moment2, n * 3 * sizeof(float)));
   NoteDeviceBytes(t);
   return RT2_OK;
 }
@@ -298,6 +315,7 @@ int ResetFrame(rt2_tracer* t) {
   HIP_TRY(hipMemsetAsync(t->d_accum, 0, n * 3 * sizeof(float), t->stream));
   HIP_TRY(hipMemsetAsync(t->d_pixels, 0, n * 4, t->stream));
   if (t->d_ray_counts) HIP_TRY(hipMemsetAsync(t->d_ray_counts, 0, n * sizeof(uint32_t), t->stream));
+  if (t->d_moment2) HIP_TRY(hipMemsetAsync(t->d_moment2, 0, n * 3 * sizeof(float), t->stream));
   return RT2_OK;
 }
 
@@ -1246,7 +1264,7 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
     // accumulate in frame order on the tracer stream, after this launch (RayTracer.cpp:64)
     HIP_TRY(hipEventRecord(sl.rendered, sl.stream));
     HIP_TRY(hipStreamWaitEvent(t->stream, sl.rendered, 0));
-    HIP_TRY(LaunchAccumulate(sl.samples, t->d_accum, t->d_pixels, p.local_pixels, p.n_frames,
+    HIP_TRY(LaunchAccumulate(sl.samples, t->d_accum, t->d_moment2, t->d_pixels, p.local_pixels, p.n_frames,
                              p.frame_begin + p.n_frames, t->stream));
     HIP_TRY(hipEventRecord(sl.consumed, t->stream));
     sl.consumed_set = true;
@@ -1382,6 +1400,81 @@ int ImageRoot(rt2_tracer* t, rt2_tracer** root) {
   int rc = Sync(r);
   if (rc != RT2_OK) return rc;
   *root = r;
+  return RT2_OK;
+}
+
+// A per-pixel readback of a multi tracer that needs no gather (diagnostics): read(part, rows) fills each
+// GPU's local rows (`ch` values of T per pixel), which are placed in image order on the host.
+template <typename T, typename Fn>
+int PlacePartRows(rt2_tracer* t, T* out, int ch, Fn&& read) {
+  std::vector<T> part;
+  for (rt2_tracer* p : t->parts) {
+    const size_t row = (size_t)p->width * (size_t)ch;
+    part.resize(row * (size_t)p->local_rows);
+    int rc = read(p, part.data());
+    if (rc != RT2_OK) return rc;
+    const int bh = BandH(p);
+    for (int r = 0; r < p->local_rows; r++) {
+      const int period = r / bh;  // the rank's band of this period (rt2_layout.h BandRank)
+      const int phase = ((p->rank - period) % p->world + p->world) % p->world;
+      const int y = (period * p->world + phase) * bh + r % bh;
+      memcpy(out + (size_t)y * row, part.data() + (size_t)r * row, row * sizeof(T));
+    }
+  }
+  return RT2_OK;
+}
+
+float NoiseRms(const rt2_noise& o) {
+  const uint64_t finite = o.pixels - o.nonfinite;
+  return finite ? (float)std::sqrt(o.sum_sq / (double)finite) : 0.0f;
+}
+
+// The noise kernel over a one-GPU tracer's local pixels: the float3 standard error into sem_host
+// (or null) and the scalars into out (or null). The partials are added up in block order.
+int NoiseLocal(rt2_tracer* t, float threshold, float* sem_host, rt2_noise* out) {
+  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "moments not enabled (rt2_tracer_enable_moments)");
+  int rc = Sync(t);
+  if (rc != RT2_OK) return rc;
+  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "the noise estimate needs at least 2 frames");
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  rt2_noise o;
+  memset(&o, 0, sizeof(o));
+  o.frames = t->frame_idx;
+  o.pixels = n;
+  if (n) {
+    HIP_TRY(hipSetDevice(t->device));
+    const size_t blocks = NoiseBlocks((uint32_t)n);
+    if (blocks > t->noise_blocks) {
+      (void)hipFree(t->d_noise);
+      t->d_noise = nullptr;
+      t->noise_blocks = 0;
+      HIP_TRY(hipMalloc(&t->d_noise, blocks * sizeof(NoisePartial)));
+      t->noise_blocks = blocks;
+      NoteDeviceBytes(t);
+    }
+    float* d_sem = nullptr;
+    if (sem_host) HIP_TRY(hipMalloc(&d_sem, n * 3 * sizeof(float)));
+    std::vector<NoisePartial> parts(blocks);
+    hipError_t e = LaunchNoise(t->d_accum, t->d_moment2, d_sem, t->d_noise, (uint32_t)n, t->frame_idx, threshold, t->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(parts.data(), t->d_noise, blocks * sizeof(NoisePartial), hipMemcpyDeviceToHost, t->stream);
+    if (e == hipSuccess && sem_host)
+      e = hipMemcpyAsync(sem_host, d_sem, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+    t->host_waits++;
+    (void)hipFree(d_sem);
+    if (e != hipSuccess) return HipFail(e, "noise estimate");
+    double mx = 0.0;
+    for (const NoisePartial& p : parts) {
+      o.sum_sq = o.sum_sq + p.sum_sq;
+      mx = p.max_err > mx ? p.max_err : mx;
+      o.below += p.below;
+      o.nonfinite += p.nonfinite;
+    }
+    o.max_err = (float)mx;
+  }
+  o.rms = NoiseRms(o);
+  if (out) *out = o;
   return RT2_OK;
 }
 }  // namespace
@@ -1578,27 +1671,93 @@ int rt2_tracer_enable_ray_counts(rt2_tracer* t, int on) {
 
 int rt2_tracer_ray_counts(rt2_tracer* t, uint32_t* out) {
   if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
-  if (IsMulti(t)) {  // a diagnostic: each GPU's rows read back and placed on the host
-    std::vector<uint32_t> part;
-    for (rt2_tracer* p : t->parts) {
-      part.resize((size_t)p->width * (size_t)p->local_rows);
-      int rc = rt2_tracer_ray_counts(p, part.data());
-      if (rc != RT2_OK) return rc;
-      const int bh = BandH(p);
-      for (int r = 0; r < p->local_rows; r++) {
-        const int period = r / bh;  // the rank's band of this period (rt2_layout.h BandRank)
-        const int phase = ((p->rank - period) % p->world + p->world) % p->world;
-        const int y = (period * p->world + phase) * bh + r % bh;
-        memcpy(out + (size_t)y * p->width, part.data() + (size_t)r * p->width, (size_t)p->width * sizeof(uint32_t));
-      }
-    }
-    return RT2_OK;
-  }
+  if (IsMulti(t))  // a diagnostic: each GPU's rows read back and placed on the host
+    return PlacePartRows(t, out, 1, [](rt2_tracer* p, uint32_t* rows) { return rt2_tracer_ray_counts(p, rows); });
   if (!t->d_ray_counts) return Fail(RT2_ERR_INVALID, "ray counts not enabled");
   int rc = Sync(t);
   if (rc != RT2_OK) return rc;
   size_t n = (size_t)t->width * (size_t)t->local_rows;
   if (n) HIP_TRY(hipMemcpy(out, t->d_ray_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+
+// ---- noise estimate (rt2.h "Noise estimate and render-until-converged") ----
+int rt2_tracer_enable_moments(rt2_tracer* t, int on) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  RT2_FORWARD(t, rt2_tracer_enable_moments(p, on));
+  int rc = Sync(t);
+  if (rc != RT2_OK) return rc;
+  t->moments_on = on != 0;
+  if ((rc = Realloc(t)) != RT2_OK) return rc;
+  return ResetFrame(t);
+}
+
+int rt2_tracer_moments(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t))
+    return PlacePartRows(t, out, 3, [](rt2_tracer* p, float* rows) { return rt2_tracer_moments(p, rows); });
+  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "moments not enabled (rt2_tracer_enable_moments)");
+  int rc = Sync(t);
+  if (rc != RT2_OK) return rc;
+  size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n) HIP_TRY(hipMemcpy(out, t->d_moment2, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+
+int rt2_tracer_standard_error(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t))
+    return PlacePartRows(t, out, 3, [](rt2_tracer* p, float* rows) { return rt2_tracer_standard_error(p, rows); });
+  return NoiseLocal(t, 0.0f, out, nullptr);
+}
+
+int rt2_tracer_noise(rt2_tracer* t, float threshold, rt2_noise* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (!IsMulti(t)) return NoiseLocal(t, threshold, nullptr, out);
+  rt2_noise sum;
+  memset(&sum, 0, sizeof(sum));
+  for (rt2_tracer* p : t->parts) {
+    rt2_noise o;
+    int rc = NoiseLocal(p, threshold, nullptr, &o);
+    if (rc != RT2_OK) return rc;
+    sum.frames = o.frames;
+    sum.pixels += o.pixels;
+    sum.below += o.below;
+    sum.nonfinite += o.nonfinite;
+    sum.sum_sq = sum.sum_sq + o.sum_sq;
+    sum.max_err = std::max(sum.max_err, o.max_err);
+  }
+  sum.rms = NoiseRms(sum);
+  *out = sum;
+  return RT2_OK;
+}
+
+int rt2_tracer_render_until(rt2_tracer* t, float target_rms, int min_frames, int max_frames, int check_every,
+                            rt2_noise* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (!(target_rms >= 0.0f) || min_frames < 0 || max_frames < 0 || check_every < 0)
+    return Fail(RT2_ERR_INVALID, "render_until: need target_rms >= 0, min_frames, max_frames, check_every >= 0");
+  rt2_tracer* first = IsMulti(t) ? t->parts[0] : t;
+  if (!first->moments_on) return Fail(RT2_ERR_INVALID, "moments not enabled (rt2_tracer_enable_moments)");
+  int step = check_every;
+  if (step == 0) {  // one sweep of the sqrt_spp x sqrt_spp strata (RayTracer.cpp:59-60)
+    const int sq = first->camera.Params().sqrt_spp;
+    if (sq <= 0) return Fail(RT2_ERR_INVALID, "samples_per_pixel gives sqrt_spp = 0");
+    step = (int)std::min<int64_t>((int64_t)sq * sq, 0x7FFFFFFF);
+  }
+  const int64_t first_check = std::max(min_frames, 2);
+  memset(out, 0, sizeof(*out));
+  int64_t f = rt2_tracer_frame_idx(t);
+  while (f < max_frames) {
+    int rc = rt2_tracer_render(t, (int)std::min<int64_t>(step, max_frames - f));
+    if (rc != RT2_OK) return rc;
+    f = rt2_tracer_frame_idx(t);
+    if (f < first_check) continue;
+    if ((rc = rt2_tracer_noise(t, target_rms, out)) != RT2_OK) return rc;
+    if (out->rms <= target_rms && out->nonfinite == 0) return RT2_OK;
+  }
+  // no step ended in a check (max_frames reached before, or below min_frames): the image as it stands
+  if (out->frames != f && f >= 2) return rt2_tracer_noise(t, target_rms, out);
   return RT2_OK;
 }
 

@@ -4,10 +4,14 @@
 // boundary (tests/test_gpu_headless.py runs it and compares its PNG with the Python path's).
 //
 //   rt2_headless <scene.json> <out.png> [--settings settings.json] [--samples N] [--size WxH] [--gpus N]
+//                [--noise-target X [--max-samples N]]
 //
 // Without --settings the reference's Settings.hpp defaults apply (num_samples 1, max_depth 50);
 // --samples / --size override num_samples and the output dims (App.cpp:115-124: scene dims, else
 // 1600x900). --gpus N renders on GPUs 0..N-1 (row bands + RCCL gather, rt2_tracer_create_multi).
+// --noise-target X renders until the image's rms noise estimate is at most X instead of a fixed count
+// (RenderUntil with moments on, one check per stratum sweep), at most N = --max-samples frames (default:
+// num_samples), with samples_per_pixel = N; it prints "frames <n> rms <x>" on stderr.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -18,7 +22,8 @@
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s <scene.json> <out.png> [--settings f] [--samples N] [--size WxH]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <scene.json> <out.png> [--settings f] [--samples N] [--size WxH] [--gpus N] "
+                         "[--noise-target X [--max-samples N]]\n", argv[0]);
     return 2;
   }
   const std::string scene_path = argv[1], out_path = argv[2];
@@ -26,6 +31,8 @@ int main(int argc, char** argv) {
   long samples = -1;
   rt2::ivec2 size{0, 0};
   int gpus = 0;  // 0: the one-GPU tracer; N >= 1: rt2_tracer_create_multi over GPUs 0..N-1
+  float noise_target = -1.f;  // >= 0: render until converged
+  long max_samples = -1;
   try {
     for (int i = 3; i + 1 < argc; i += 2) {
       if (!std::strcmp(argv[i], "--settings")) {
@@ -34,6 +41,11 @@ int main(int argc, char** argv) {
         samples = std::atol(argv[i + 1]);
       } else if (!std::strcmp(argv[i], "--gpus")) {
         gpus = std::atoi(argv[i + 1]);
+      } else if (!std::strcmp(argv[i], "--noise-target")) {
+        noise_target = std::strtof(argv[i + 1], nullptr);
+        if (!(noise_target >= 0.f)) return 2;
+      } else if (!std::strcmp(argv[i], "--max-samples")) {
+        max_samples = std::atol(argv[i + 1]);
       } else if (!std::strcmp(argv[i], "--size")) {
         if (std::sscanf(argv[i + 1], "%dx%d", &size.x, &size.y) != 2) return 2;
       } else {
@@ -42,6 +54,8 @@ int main(int argc, char** argv) {
       }
     }
     if (samples > 0) settings.num_samples = (size_t)samples;
+    const bool until = noise_target >= 0.f;
+    if (until && max_samples > 0) settings.num_samples = (size_t)max_samples;  // the bound, and the strata
 
     rt2::serialize::SceneLoader loader;
     auto scene_opt = loader.LoadScene(scene_path);
@@ -59,9 +73,15 @@ int main(int argc, char** argv) {
     scene.cam.SetSamplesPerPixel((int)settings.num_samples);
     tracer.camera = &scene.cam;
     tracer.OnResize(dims);
+    if (until) tracer.EnableMoments();
 
     const auto t0 = std::chrono::steady_clock::now();
-    for (size_t i = 0; i < settings.num_samples; i++) tracer.Update(scene);
+    if (until) {
+      const rt2_noise nz = tracer.RenderUntil(scene, noise_target, (int)settings.num_samples);
+      std::fprintf(stderr, "frames %zu rms %.9g\n", (size_t)tracer.FrameIdx(), (double)nz.rms);
+    } else {
+      for (size_t i = 0; i < settings.num_samples; i++) tracer.Update(scene);
+    }
     const auto pixels = tracer.NonConvertedPixels();  // runs the queued frames
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     rt2::util::WriteImage(pixels, tracer.Dims().x, tracer.Dims().y, out_path);
@@ -72,6 +92,7 @@ int main(int argc, char** argv) {
                 "\"mray_s\": %.1f, \"launches\": %llu, \"gpus\": %d}\n",
                 (size_t)tracer.FrameIdx(), dims.x, dims.y, (unsigned long long)st.rays, s, st.rays / s / 1e6,
                 (unsigned long long)st.launches, tracer.NumGpus());
+    if (until) return tracer.FrameIdx() >= 1 && tracer.FrameIdx() <= settings.num_samples ? 0 : 3;
     return tracer.FrameIdx() == settings.num_samples ? 0 : 3;
   } catch (const rt2::Error& e) {
     std::fprintf(stderr, "rt2 error %d: %s\n", e.code, e.what());

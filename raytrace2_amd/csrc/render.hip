@@ -2805,13 +2805,19 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
 // of the reference's per-Update accumulation, bit for bit), then the live display value
 // pixels[i] = ToColor(clamp(accum[i] / frame_idx, 0, 1)). One thread per local pixel reading its
 // octets (96 contiguous bytes, six 16-B loads; neighbouring threads' octets are adjacent), so the
-// kernel streams the sample buffer once at HBM rate.
+// kernel streams the sample buffer once at HBM rate. kMoments (rt2_tracer_enable_moments): the same
+// pass also sums the samples' squares in frame order, moment2[i] = moment2[i] + s * s per channel (one
+// multiply and one add, each rounded on its own), for the noise estimate (noise.h); it reads no
+// extra sample bytes.
+template <bool kMoments>
 __global__ __launch_bounds__(256) void accumulate_kernel(const float* __restrict__ samples, float* __restrict__ accum,
-                                                         uint32_t* __restrict__ pixels, uint32_t npix, int n_frames,
-                                                         int frame_idx) {
+                                                         float* __restrict__ moment2, uint32_t* __restrict__ pixels,
+                                                         uint32_t npix, int n_frames, int frame_idx) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= npix) return;
   float a0 = accum[3 * i], a1 = accum[3 * i + 1], a2 = accum[3 * i + 2];
+  float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f;
+  if constexpr (kMoments) q0 = moment2[3 * i], q1 = moment2[3 * i + 1], q2 = moment2[3 * i + 2];
   const float4* s = reinterpret_cast<const float4*>(samples) + 6ull * i;
   const unsigned long long stride = 6ull * npix;  // float4s per octet plane
   for (int f = 0; f < n_frames; f += (int)kOctet, s += stride) {
@@ -2828,12 +2834,18 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const float* __restrict
         a0 += x[3 * k];
         a1 += x[3 * k + 1];
         a2 += x[3 * k + 2];
+        if constexpr (kMoments) {
+          q0 = q0 + x[3 * k] * x[3 * k];
+          q1 = q1 + x[3 * k + 1] * x[3 * k + 1];
+          q2 = q2 + x[3 * k + 2] * x[3 * k + 2];
+        }
       }
     }
   }
   accum[3 * i] = a0;
   accum[3 * i + 1] = a1;
   accum[3 * i + 2] = a2;
+  if constexpr (kMoments) moment2[3 * i] = q0, moment2[3 * i + 1] = q1, moment2[3 * i + 2] = q2;
   if (pixels) {
     const float fi = (float)frame_idx;
     const float cc[3] = {a0 / fi, a1 / fi, a2 / fi};
@@ -3140,10 +3152,12 @@ hipError_t LaunchRender(const RenderParams& p, int variant, bool stats, int grid
   return hipGetLastError();
 }
 
-hipError_t LaunchAccumulate(const float* samples, float* accum, uint8_t* pixels, uint32_t npix, int n_frames,
-                            int frame_idx, hipStream_t stream) {
+// moment2 null: the accumulation alone; else the sums of squares too (accumulate_kernel<true>).
+hipError_t LaunchAccumulate(const float* samples, float* accum, float* moment2, uint8_t* pixels, uint32_t npix,
+                            int n_frames, int frame_idx, hipStream_t stream) {
   if (npix == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::accumulate_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, stream, samples, accum,
+  auto* fn = moment2 ? dev::accumulate_kernel<true> : dev::accumulate_kernel<false>;
+  hipLaunchKernelGGL(fn, dim3((npix + 255u) / 256u), dim3(256), 0, stream, samples, accum, moment2,
                      reinterpret_cast<uint32_t*>(pixels), npix, n_frames, frame_idx);
   return hipGetLastError();
 }

@@ -44,6 +44,29 @@ def source_rows(height: int, band_h: int, world: int) -> np.ndarray:
     return deinterleave(ids, height, band_h)[:, 0, 0].astype(np.int64)
 
 
+def combine_noise(parts) -> dict:
+    """Merges the noise() dicts of tracers that each hold a part of one image (one process per GPU: the
+    ranks' row bands) as a multi-GPU tracer's rt2_tracer_noise does, on the host: pixels, below,
+    nonfinite and sum_sq add up (in list order), max_err is the largest, rms is recomputed as
+    float32(sqrt(sum_sq / (pixels - nonfinite))), 0 when no pixel is finite. The parts must rest on the
+    same frame count."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_noise: no parts")
+    frames = {int(p["frames"]) for p in parts}
+    if len(frames) != 1:
+        raise ValueError(f"combine_noise: the parts rest on different frame counts {sorted(frames)}")
+    out = {"frames": frames.pop(), "pixels": 0, "below": 0, "nonfinite": 0, "sum_sq": 0.0, "max_err": 0.0}
+    for p in parts:
+        for k in ("pixels", "below", "nonfinite"):
+            out[k] += int(p[k])
+        out["sum_sq"] = out["sum_sq"] + float(p["sum_sq"])
+        out["max_err"] = max(out["max_err"], float(p["max_err"]))
+    finite = out["pixels"] - out["nonfinite"]
+    out["rms"] = float(np.float32(np.sqrt(np.float64(out["sum_sq"]) / np.float64(finite)))) if finite else 0.0
+    return out
+
+
 class BandGather:
     """Gathers (rows_r, W, C) float32 band stacks of every rank into one (H, W, C) image on rank 0:
     every rank sends its padded stack (band_rows_max rows) with one torch.distributed gather into a

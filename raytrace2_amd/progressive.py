@@ -42,10 +42,17 @@ class PinnedBuffer:
 
 
 class ProgressiveLoop:
-    """Ticks of `frames_per_tick` frames, adapted so that a tick takes about `budget_ms`."""
+    """Ticks of `frames_per_tick` frames, adapted so that a tick takes about `budget_ms`. With
+    `target_rms` (the tracer must have moments enabled) every tick also takes the noise estimate
+    (`self.noise`, RayTracer.noise), and the loop is done once its rms is at most the target."""
 
     def __init__(self, tracer, total_frames: int, budget_ms: float = 16.0, first_frames: int = 1,
-                 max_frames_per_tick: int = 4096):
+                 max_frames_per_tick: int = 4096, target_rms: Optional[float] = None):
+        if target_rms is not None and not getattr(tracer, "_moments", False):
+            raise ValueError("ProgressiveLoop: target_rms needs tracer.enable_moments()")
+        self.target_rms = None if target_rms is None else float(target_rms)
+        self.noise: Optional[dict] = None
+        self.converged = False
         self.tr = tracer
         w, _ = tracer.Dims()
         self.pixels = PinnedBuffer((tracer.local_rows(), w, 4))
@@ -57,7 +64,7 @@ class ProgressiveLoop:
         self.frames_done = 0
 
     def done(self) -> bool:
-        return self.frames_done >= self.total
+        return self.frames_done >= self.total or self.converged
 
     def tick(self) -> Optional[np.ndarray]:
         """Renders the next frames of the budget, returns Pixels() after them (None when done)."""
@@ -69,6 +76,9 @@ class ProgressiveLoop:
         check(lib.rt2_tracer_pixels_async(self.tr._h, self.pixels.array.ctypes.data_as(
             ctypes.POINTER(ctypes.c_uint8))))
         self.tr.synchronize()
+        if self.target_rms is not None and self.tr.FrameIdx() >= 2:
+            self.noise = self.tr.noise(self.target_rms)
+            self.converged = self.noise["rms"] <= self.target_rms and self.noise["nonfinite"] == 0
         dt_ms = (time.perf_counter() - t0) * 1e3
         self.frames_done += n
         self.ticks += 1

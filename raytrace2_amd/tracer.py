@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._native import AppSettings as _AppSettings
-from ._native import UNIQUE_ID_BYTES, CameraDesc, SceneInfo, Stats, check, lib
+from ._native import UNIQUE_ID_BYTES, CameraDesc, Noise, SceneInfo, Stats, check, lib
 
 DEFAULT_SEED = 0x5EED2024
 
@@ -223,6 +223,7 @@ class RayTracer:
         self._h = h
         self.device = self.devices[0]
         self._max_depth = 50
+        self._moments = False
         self.camera: Optional[Camera] = None
 
     def close(self):
@@ -391,6 +392,41 @@ class RayTracer:
         out = np.zeros((self.local_rows(), w), np.uint32)
         check(lib.rt2_tracer_ray_counts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
         return out
+
+    # -- noise estimate (rt2.h "Noise estimate and render-until-converged") -------------------
+    def enable_moments(self, on: bool = True) -> None:
+        """Sums of the samples' squares beside the accumulation, in frame order (resets the frame)."""
+        check(lib.rt2_tracer_enable_moments(self._h, 1 if on else 0))
+        self._moments = bool(on)
+
+    def moments(self) -> np.ndarray:
+        """Raw float3 sums of squares per local pixel (a multi-GPU tracer: the full image)."""
+        w, _ = self.Dims()
+        out = np.zeros((self.local_rows(), w, 3), np.float32)
+        check(lib.rt2_tracer_moments(self._h, _fp(out)))
+        return out
+
+    def standard_error(self) -> np.ndarray:
+        """Float3 standard error of the mean per local pixel (needs FrameIdx() >= 2)."""
+        w, _ = self.Dims()
+        out = np.zeros((self.local_rows(), w, 3), np.float32)
+        check(lib.rt2_tracer_standard_error(self._h, _fp(out)))
+        return out
+
+    def noise(self, threshold: float = 0.0) -> dict:
+        """rt2_noise as a dict: frames, pixels, below (err <= threshold), nonfinite, sum_sq, max_err, rms."""
+        n = Noise()
+        check(lib.rt2_tracer_noise(self._h, float(threshold), ctypes.byref(n)))
+        return n.as_dict()
+
+    def render_until(self, target_rms: float, max_frames: int, min_frames: int = 0, check_every: int = 0) -> dict:
+        """Renders in steps of check_every frames (0: one stratum sweep) until the image's rms noise is at
+        most target_rms or FrameIdx() reaches max_frames; returns the last estimate (noise())."""
+        self._push_camera()
+        n = Noise()
+        check(lib.rt2_tracer_render_until(self._h, float(target_rms), int(min_frames), int(max_frames),
+                                          int(check_every), ctypes.byref(n)))
+        return n.as_dict()
 
     def enable_stats(self, on: bool = True) -> None:
         check(lib.rt2_tracer_enable_stats(self._h, 1 if on else 0))
