@@ -325,6 +325,59 @@ RT2_API int rt2_tracer_noise(rt2_tracer* tr, float threshold, rt2_noise* out);
 RT2_API int rt2_tracer_render_until(rt2_tracer* tr, float target_rms, int min_frames, int max_frames, int check_every,
                                     rt2_noise* out);
 
+/* ---- Adaptive sampling (DESIGN.md "Adaptive sampling") ----
+ * Opt-in, needs moments on; with it off nothing changes. Pixels whose noise estimate has met a threshold
+ * retire and later launches trace only the rest. Sample streams are keyed by (seed, global pixel, frame)
+ * and summed in frame order, so a pixel that stops after n frames holds exactly the sums of Render(n).
+ * State per local pixel: a sample count n_p (uint32) and an active flag.
+ * enable_adaptive: like enable_moments it synchronises, reallocates and resets the frame index and the
+ *   sums; afterwards every pixel is active and n_p = 0. Reset / OnResize / set_partition reactivate every
+ *   pixel and zero the counts.
+ * Rendering: Update() / Render(n) advance FrameIdx() by n as always. The frames [F, F + n) are traced
+ *   only for the active pixels: a += s, q += s * s, n_p += n. An active pixel always has n_p ==
+ *   FrameIdx(); a retired pixel keeps the count and the sums it had when it retired. While every pixel
+ *   is active a launch is the launch it always was; with none active nothing is launched and the frame
+ *   index still advances.
+ * adaptive_check(threshold, window): needs FrameIdx() >= 2; launches queued frames first. For every local
+ *   pixel err_p = the noise estimate above from (a_p, q_p, n_p), and over_p = !(finite_p && err_p <=
+ *   (double)threshold): a non-finite pixel is always over. An active pixel at column x stays active iff
+ *   some pixel of the same row in the columns [x - window, x + window] within [0, width) is over;
+ *   otherwise it retires and stays retired until the next reset. 0 <= window <= 64. The window runs
+ *   along the row only: partitions hold whole rows, so the decision needs no other GPU's pixels and is the
+ *   same under any set_partition. (Why a window: a pixel that has seen only black samples so far has
+ *   err exactly 0; window 0 would freeze it black, window 1 keeps it going while a neighbour is noisy.)
+ * render_adaptive: renders in steps of `check_every` frames (0: one stratum sweep; the last step
+ *   shortened to land on max_frames) while FrameIdx() < max_frames; after each step with FrameIdx() >=
+ *   max(min_frames, 2), the last one included, it runs a check and stops when no pixel is active. `out`
+ *   receives the last check (frames = 0: no step ended in one).
+ * Readbacks with adaptive on: sample_counts returns n_p per local pixel; non_converted_pixels and the
+ *   RGBA pixels divide by (float)n_p instead of the frame index; standard_error and noise use each
+ *   pixel's own n_p (rt2_noise.frames stays FrameIdx()); accumulation, moments and ray_counts are the raw
+ *   sums as always (a pixel's ray count is that of its first n_p frames).
+ * Contract: for every pixel (a_p, q_p) equal, bit for bit, what a tracer without adaptive sampling holds
+ *   after Render(n_p).
+ * Caveat: stopping on a pixel's own variance estimate is biased — an unlucky pixel whose first samples
+ *   happen to agree looks converged and freezes. `window` and `min_frames` are the guards.
+ * RT2_ERR_INVALID: enable_adaptive with moments off, or on a create_multi or joined tracer (their gathered
+ *   image divides by one common frame index; set_partition tracers work); enable_moments(0) and join while
+ *   adaptive is on; sample_counts / adaptive_check / render_adaptive with adaptive off; a check with
+ *   fewer than 2 frames; a window outside [0, 64] or a threshold that is negative or NaN; enable_adaptive
+ *   on a tracer that renders without the threaded traversal (the list kernels exist for that mode only).
+ * Every field of rt2_adaptive but `frames` is additive over partitions. */
+typedef struct {
+  int64_t frames;     /* FrameIdx() at the check */
+  uint64_t pixels;    /* local pixels */
+  uint64_t active;    /* pixels still active after this check */
+  uint64_t retired;   /* pixels this check retired */
+  uint64_t samples;   /* sum of n_p */
+  uint64_t nonfinite; /* pixels with a non-finite sum (never retired) */
+} rt2_adaptive;
+RT2_API int rt2_tracer_enable_adaptive(rt2_tracer* tr, int on);
+RT2_API int rt2_tracer_sample_counts(rt2_tracer* tr, uint32_t* out); /* n_p per local pixel */
+RT2_API int rt2_tracer_adaptive_check(rt2_tracer* tr, float threshold, int window, rt2_adaptive* out);
+RT2_API int rt2_tracer_render_adaptive(rt2_tracer* tr, float threshold, int window, int min_frames, int max_frames,
+                                       int check_every, rt2_adaptive* out);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -239,6 +239,27 @@ class RayTracer {
     return n;
   }
 
+  // Adaptive sampling (rt2.h "Adaptive sampling"): converged pixels retire at a check and later launches
+  // trace only the rest. Needs EnableMoments; EnableAdaptive resets the frame like OnResize.
+  void EnableAdaptive(bool on = true) { Check(rt2_tracer_enable_adaptive(t_.get(), on ? 1 : 0)); }
+  [[nodiscard]] std::vector<uint32_t> SampleCounts() const {
+    std::vector<uint32_t> out((size_t)dims_.x * LocalRows());
+    Check(rt2_tracer_sample_counts(t_.get(), out.data()));
+    return out;
+  }
+  rt2_adaptive AdaptiveCheck(float threshold, int window = 1) {
+    rt2_adaptive a{};
+    Check(rt2_tracer_adaptive_check(t_.get(), threshold, window, &a));
+    return a;
+  }
+  rt2_adaptive RenderAdaptive(const Scene& /*scene*/, float threshold, int max_frames, int window = 1,
+                              int min_frames = 0, int check_every = 0) {
+    Sync();
+    rt2_adaptive a{};
+    Check(rt2_tracer_render_adaptive(t_.get(), threshold, window, min_frames, max_frames, check_every, &a));
+    return a;
+  }
+
   rt2_tracer* handle() const { return t_.get(); }
   [[nodiscard]] int NumGpus() const { return rt2_tracer_n_gpus(t_.get()); }
 

@@ -94,6 +94,15 @@ class Noise(ctypes.Structure):
                 "rms": float(self.rms)}
 
 
+class Adaptive(ctypes.Structure):
+    """rt2_adaptive."""
+    _fields_ = [("frames", ctypes.c_int64), ("pixels", ctypes.c_uint64), ("active", ctypes.c_uint64),
+                ("retired", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Every RT2_API function name declared in include/rt2.h."""
     txt = open(header).read()
@@ -190,6 +199,10 @@ def _load():
         "rt2_tracer_standard_error": (i32, [vp, fp]),
         "rt2_tracer_noise": (i32, [vp, f32, ctypes.POINTER(Noise)]),
         "rt2_tracer_render_until": (i32, [vp, f32, i32, i32, i32, ctypes.POINTER(Noise)]),
+        "rt2_tracer_enable_adaptive": (i32, [vp, i32]),
+        "rt2_tracer_sample_counts": (i32, [vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "rt2_tracer_adaptive_check": (i32, [vp, f32, i32, ctypes.POINTER(Adaptive)]),
+        "rt2_tracer_render_adaptive": (i32, [vp, f32, i32, i32, i32, i32, ctypes.POINTER(Adaptive)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

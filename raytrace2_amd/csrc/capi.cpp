@@ -18,17 +18,26 @@
 #include <vector>
 
 #include "../../include/rt2.h"
+#include "adaptive.h"
 #include "noise.h"
 #include "scene.h"
 
 namespace rt2 {
 hipError_t LaunchRender(const RenderParams& p, int variant, bool stats, int grid, hipStream_t stream);
-int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes);
+int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes, bool list = false);
+hipError_t LaunchAccumulateList(const float* samples, const uint32_t* list, float* accum, float* moment2,
+                                uint32_t* counts, uint8_t* pixels, uint32_t nslots, int n_frames, hipStream_t stream);
+uint32_t AdaptiveBlocks(uint32_t npix);
+uint32_t AdaptiveTiles(int width, int rows);
+hipError_t LaunchAdaptiveCheck(const float* accum, const float* moment2, const uint32_t* counts, uint8_t* over,
+                               uint8_t* active, uint32_t* list, uint32_t* slot_of, void* wg_counts, uint32_t* wg_offsets,
+                               AdaptivePartial* partials, AdaptiveTotals* totals, int width, int rows, float threshold,
+                               int window, hipStream_t stream);
 hipError_t LaunchAccumulate(const float* samples, float* accum, float* moment2, uint8_t* pixels, uint32_t npix,
                             int n_frames, int frame_idx, hipStream_t stream);
 uint32_t NoiseBlocks(uint32_t npix);
-hipError_t LaunchNoise(const float* accum, const float* moment2, float* sem, NoisePartial* partials, uint32_t npix,
-                       int64_t n_frames, float threshold, hipStream_t stream);
+hipError_t LaunchNoise(const float* accum, const float* moment2, const uint32_t* counts, float* sem,
+                       NoisePartial* partials, uint32_t npix, int64_t n_frames, float threshold, hipStream_t stream);
 hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsigned long long* d_out, hipStream_t stream);
 int RenderMode(const RenderParams& p);
 int RenderBlockSize();
@@ -105,6 +114,19 @@ struct rt2_tracer {
   bool moments_on = false;
   NoisePartial* d_noise = nullptr;
   size_t noise_blocks = 0;
+  // adaptive sampling (rt2_tracer_enable_adaptive; needs moments): per local pixel its sample count n_p
+  // and active flag, the check's `over` flags, the list of the active pixels (tile-major, padded to 64:
+  // adaptive.hip) and each pixel's slot in it, and the check's per-workgroup scratch. n_active is what
+  // the last check left (all local pixels after a reset); launches take the list once a pixel has retired.
+  bool adaptive_on = false;
+  uint32_t* d_counts = nullptr;
+  uint8_t* d_active = nullptr;
+  uint8_t* d_over = nullptr;
+  uint32_t* d_list = nullptr;
+  uint32_t* d_slot_of = nullptr;
+  void* d_ad_scratch = nullptr;  // wg counts (uint2), wg offsets, classify partials, totals
+  size_t ad_scratch_bytes = 0;
+  uint32_t n_active = 0;
   uint32_t* d_work = nullptr;  // one work counter per launch slot (words 0 and 16)
   unsigned long long* d_stats = nullptr;
   bool stats_on = false;
@@ -271,6 +293,19 @@ void FreeFrame(rt2_tracer* t) {
   (void)hipFree(t->d_ray_counts);
   (void)hipFree(t->d_moment2);
   (void)hipFree(t->d_noise);
+  (void)hipFree(t->d_counts);
+  (void)hipFree(t->d_active);
+  (void)hipFree(t->d_over);
+  (void)hipFree(t->d_list);
+  (void)hipFree(t->d_slot_of);
+  (void)hipFree(t->d_ad_scratch);
+  t->d_counts = nullptr;
+  t->d_active = nullptr;
+  t->d_over = nullptr;
+  t->d_list = nullptr;
+  t->d_slot_of = nullptr;
+  t->d_ad_scratch = nullptr;
+  t->ad_scratch_bytes = 0;
   t->d_accum = nullptr;
   t->d_pixels = nullptr;
   t->d_ray_counts = nullptr;
@@ -285,7 +320,8 @@ void FreeFrame(rt2_tracer* t) {
 size_t DeviceBytes(const rt2_tracer* t) {
   const size_t n = (size_t)t->width * (size_t)AllocRows(t);
   size_t b = t->scene_bytes + (t->d_accum ? n * 12 : 0) + (t->d_pixels ? n * 4 : 0) + (t->d_ray_counts ? n * 4 : 0) +
-             (t->d_moment2 ? n * 12 : 0) + t->noise_blocks * sizeof(NoisePartial);
+             (t->d_moment2 ? n * 12 : 0) + t->noise_blocks * sizeof(NoisePartial) +
+             (t->d_counts ? n * (4 + 1 + 1 + 4 + 4) + 64 * 4 : 0) + t->ad_scratch_bytes;
   for (const auto& sl : t->slots) b += sl.samples_bytes + sl.chunks_bytes;
   if (t->d_image) b += t->stacks_bytes + t->image_pixels * (12 + 12 + 4);
   return b;
@@ -301,6 +337,17 @@ int Realloc(rt2_tracer* t) {
   HIP_TRY(hipMalloc(&t->d_pixels, n * 4));
   if (t->ray_counts_on) HIP_TRY(hipMalloc(&t->d_ray_counts, n * sizeof(uint32_t)));
   if (t->moments_on) HIP_TRY(hipMalloc(&t->d_moment2, n * 3 * sizeof(float)));
+  if (t->adaptive_on) {
+    const size_t tiles = AdaptiveTiles(t->width, std::max(t->local_rows, 1));
+    const size_t blocks = AdaptiveBlocks((uint32_t)n);
+    HIP_TRY(hipMalloc(&t->d_counts, n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&t->d_active, n));
+    HIP_TRY(hipMalloc(&t->d_over, n));
+    HIP_TRY(hipMalloc(&t->d_list, (n + 64) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&t->d_slot_of, n * sizeof(uint32_t)));
+    t->ad_scratch_bytes = tiles * 12 + 4 + blocks * sizeof(AdaptivePartial) + sizeof(AdaptiveTotals) + 16;
+    HIP_TRY(hipMalloc(&t->d_ad_scratch, t->ad_scratch_bytes));
+  }
   NoteDeviceBytes(t);
   return RT2_OK;
 }
@@ -310,12 +357,17 @@ int ResetFrame(rt2_tracer* t) {
   t->frame_idx = 0;
   t->queued = 0;  // queued frames would only be accumulated and zeroed again
   t->image_frame = -1;
+  t->n_active = (uint32_t)((size_t)t->width * (size_t)t->local_rows);  // adaptive: every pixel active again
   if (n == 0) return RT2_OK;
   HIP_TRY(hipSetDevice(t->device));
   HIP_TRY(hipMemsetAsync(t->d_accum, 0, n * 3 * sizeof(float), t->stream));
   HIP_TRY(hipMemsetAsync(t->d_pixels, 0, n * 4, t->stream));
   if (t->d_ray_counts) HIP_TRY(hipMemsetAsync(t->d_ray_counts, 0, n * sizeof(uint32_t), t->stream));
   if (t->d_moment2) HIP_TRY(hipMemsetAsync(t->d_moment2, 0, n * 3 * sizeof(float), t->stream));
+  if (t->d_counts) {
+    HIP_TRY(hipMemsetAsync(t->d_counts, 0, n * sizeof(uint32_t), t->stream));
+    HIP_TRY(hipMemsetAsync(t->d_active, 1, n, t->stream));
+  }
   return RT2_OK;
 }
 
@@ -413,7 +465,7 @@ const char* rt2_last_error(void) { return g_err.c_str(); }
 #ifndef RT2_KERNEL_SHA
 #define RT2_KERNEL_SHA "unknown"
 #endif
-// "rt2-mi355x 0.1 (gfx950) kernel <sha1 of render.hip + rt2_layout.h, 12 hex digits>"
+// "rt2-mi355x 0.1 (gfx950) kernel <sha1 of the render kernel's sources (Makefile KERNEL_SHA), 12 hex digits>"
 const char* rt2_version(void) { return "rt2-mi355x 0.1 (gfx950) kernel " RT2_KERNEL_SHA; }
 
 int rt2_scene_load(const char* path, uint64_t seed, rt2_scene** out) {
@@ -1045,6 +1097,15 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
     t->frame_idx += n_frames;
     return RT2_OK;
   }
+  // Adaptive sampling: once a pixel has retired the launch runs over the list of the active pixels
+  // (n_slots of them); with none left there is nothing to trace and only the frame index advances.
+  const uint32_t all_pixels = (uint32_t)t->width * (uint32_t)t->local_rows;
+  const bool listed = t->adaptive_on && t->n_active < all_pixels;
+  if (listed && t->n_active == 0) {
+    t->frame_idx += n_frames;
+    return RT2_OK;
+  }
+  const uint32_t n_slots = listed ? t->n_active : all_pixels;
   HIP_TRY(hipSetDevice(t->device));
   RenderParams p;
   memset(&p, 0, sizeof(p));
@@ -1075,7 +1136,13 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
   p.div_band_h = MakeMagic((uint32_t)p.band_h);
   p.div_band_w = MakeMagic((uint32_t)p.band_h * (uint32_t)p.world);
   p.div_world = MakeMagic((uint32_t)p.world);
-  p.local_pixels = (uint32_t)t->width * (uint32_t)t->local_rows;
+  p.local_pixels = n_slots;  // the sample buffer's pixels: all of them, or the list's slots
+  if (listed) {  // items run over the slots padded to whole waves (RenderParams::active_list)
+    p.tile_items = (n_slots + 63u) & ~63u;
+    p.div_tile_items = MakeMagic(p.tile_items);
+    p.active_list = t->d_list;
+    p.slot_of = t->d_slot_of;
+  }
   if (p.tile_items > 0x7FFFFFFFu)  // work items (and pixel indices) must stay below 2^31
     return Fail(RT2_ERR_INVALID, "image too large for one GPU (more than 2^31 pixels in a partition)");
   p.max_depth = t->max_depth;
@@ -1108,6 +1175,8 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
   if ((uint64_t)p.local_pixels * 64u > 0x7FFFFFFFull) t->frame_tiles = false;
   uint32_t feats = t->features | (p.cam.defocus_angle > 0.0f ? (uint32_t)kFeatDefocus : 0u);
   int variant = RenderVariant(feats);
+  if (listed && !p.lin_len)  // the list kernels exist for the threaded traversal, the default mode
+    return Fail(RT2_ERR_INVALID, "adaptive sampling needs the threaded traversal (the scene has none, or RT2_NO_LINEAR)");
   // per-record counters and per-pixel ray counts come from the counting kernel instantiation (same
   // arithmetic, extra counters); the product kernel keeps only the wave ray totals
   const bool counting = t->stats_on || t->ray_counts_on;
@@ -1146,10 +1215,11 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
   // The hit table in LDS, for the kernels that take it (render.hip HitTable()), when the kernel keeps
   // the occupancy it has without the table: the runtime is asked with and without it
   if (p.lin_len && t->d_hit && t->flat_xforms && RenderTakesHitTable(variant, kModeLinear, counting)) {
-    if (t->hit_key != variant) {
-      t->hit_fits = RenderBlocksPerCU(variant, kModeLinear, counting, t->hit_bytes) >=
-                    RenderBlocksPerCU(variant, kModeLinear, counting, 0);
-      t->hit_key = variant;
+    const int hkey = variant * 2 + (listed ? 1 : 0);  // (the list kernel is asked about itself)
+    if (t->hit_key != hkey) {
+      t->hit_fits = RenderBlocksPerCU(variant, kModeLinear, counting, t->hit_bytes, listed) >=
+                    RenderBlocksPerCU(variant, kModeLinear, counting, 0, listed);
+      t->hit_key = hkey;
     }
     if (t->hit_fits) {
       p.hit_table = t->d_hit;
@@ -1160,9 +1230,9 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
   // resident lanes of this kernel instantiation (occupancy query cached: it costs far more than
   // a one-frame launch)
   const size_t lds_bytes = RenderLdsBytes(p);
-  const int okey = variant * 16 + RenderMode(p) * 2 + (counting ? 1 : 0);
+  const int okey = variant * 16 + RenderMode(p) * 2 + (counting ? 1 : 0) + (listed ? 8 : 0);
   if (t->occ_key != okey || t->occ_lds != lds_bytes) {
-    t->occ_blocks = RenderBlocksPerCU(variant, RenderMode(p), counting, lds_bytes);
+    t->occ_blocks = RenderBlocksPerCU(variant, RenderMode(p), counting, lds_bytes, listed);
     t->occ_key = okey;
     t->occ_lds = lds_bytes;
   }
@@ -1264,8 +1334,13 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
     // accumulate in frame order on the tracer stream, after this launch (RayTracer.cpp:64)
     HIP_TRY(hipEventRecord(sl.rendered, sl.stream));
     HIP_TRY(hipStreamWaitEvent(t->stream, sl.rendered, 0));
-    HIP_TRY(LaunchAccumulate(sl.samples, t->d_accum, t->d_moment2, t->d_pixels, p.local_pixels, p.n_frames,
-                             p.frame_begin + p.n_frames, t->stream));
+    if (t->adaptive_on) {
+      HIP_TRY(LaunchAccumulateList(sl.samples, listed ? t->d_list : nullptr, t->d_accum, t->d_moment2, t->d_counts,
+                                   t->d_pixels, n_slots, p.n_frames, t->stream));
+    } else {
+      HIP_TRY(LaunchAccumulate(sl.samples, t->d_accum, t->d_moment2, t->d_pixels, p.local_pixels, p.n_frames,
+                               p.frame_begin + p.n_frames, t->stream));
+    }
     HIP_TRY(hipEventRecord(sl.consumed, t->stream));
     sl.consumed_set = true;
     t->launches++;
@@ -1455,7 +1530,9 @@ int NoiseLocal(rt2_tracer* t, float threshold, float* sem_host, rt2_noise* out) 
     float* d_sem = nullptr;
     if (sem_host) HIP_TRY(hipMalloc(&d_sem, n * 3 * sizeof(float)));
     std::vector<NoisePartial> parts(blocks);
-    hipError_t e = LaunchNoise(t->d_accum, t->d_moment2, d_sem, t->d_noise, (uint32_t)n, t->frame_idx, threshold, t->stream);
+    // (adaptive sampling: each pixel's estimate rests on its own sample count)
+    hipError_t e = LaunchNoise(t->d_accum, t->d_moment2, t->adaptive_on ? t->d_counts : nullptr, d_sem, t->d_noise,
+                               (uint32_t)n, t->frame_idx, threshold, t->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(parts.data(), t->d_noise, blocks * sizeof(NoisePartial), hipMemcpyDeviceToHost, t->stream);
     if (e == hipSuccess && sem_host)
@@ -1561,6 +1638,12 @@ int rt2_tracer_non_converted_pixels(rt2_tracer* t, float* out) {
   int rc = rt2_tracer_accumulation(t, out);
   if (rc != RT2_OK) return rc;
   size_t n = (size_t)t->width * (size_t)rt2_tracer_local_rows(t) * 3;
+  if (t->adaptive_on) {  // adaptive sampling: each pixel's sum over its own sample count
+    std::vector<uint32_t> np(n / 3);
+    if ((rc = rt2_tracer_sample_counts(t, np.data())) != RT2_OK) return rc;
+    for (size_t i = 0; i < n; i++) out[i] = out[i] / (float)np[i / 3];
+    return RT2_OK;
+  }
   float f = (float)rt2_tracer_frame_idx(t);  // accumulation / frame_idx_ (RayTracer.cpp:108-109)
   for (size_t i = 0; i < n; i++) out[i] = out[i] / f;
   return RT2_OK;
@@ -1685,6 +1768,7 @@ int rt2_tracer_ray_counts(rt2_tracer* t, uint32_t* out) {
 int rt2_tracer_enable_moments(rt2_tracer* t, int on) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
   RT2_FORWARD(t, rt2_tracer_enable_moments(p, on));
+  if (!on && t->adaptive_on) return Fail(RT2_ERR_INVALID, "enable_moments(0): adaptive sampling is on and needs the moments");
   int rc = Sync(t);
   if (rc != RT2_OK) return rc;
   t->moments_on = on != 0;
@@ -1758,6 +1842,105 @@ int rt2_tracer_render_until(rt2_tracer* t, float target_rms, int min_frames, int
   }
   // no step ended in a check (max_frames reached before, or below min_frames): the image as it stands
   if (out->frames != f && f >= 2) return rt2_tracer_noise(t, target_rms, out);
+  return RT2_OK;
+}
+
+// ---- adaptive sampling (rt2.h "Adaptive sampling") ----
+int rt2_tracer_enable_adaptive(rt2_tracer* t, int on) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t) || t->comm)
+    return Fail(RT2_ERR_INVALID, "enable_adaptive: not on a multi-GPU or joined tracer (their gathered image divides by "
+                                 "one frame index); a set_partition tracer works");
+  if (on && !t->moments_on) return Fail(RT2_ERR_INVALID, "enable_adaptive: moments not enabled (rt2_tracer_enable_moments)");
+  // the kernels over an active list exist for the threaded traversal, the default mode: refused here, not
+  // at the first launch after a pixel has retired
+  if (on && (!t->use_linear || !t->lin_len))
+    return Fail(RT2_ERR_INVALID, "enable_adaptive: needs the threaded traversal (the scene has none, or RT2_NO_LINEAR)");
+  int rc = Sync(t);
+  if (rc != RT2_OK) return rc;
+  t->adaptive_on = on != 0;
+  if ((rc = Realloc(t)) != RT2_OK) return rc;
+  return ResetFrame(t);
+}
+
+int rt2_tracer_sample_counts(rt2_tracer* t, uint32_t* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || !t->adaptive_on) return Fail(RT2_ERR_INVALID, "adaptive sampling not enabled (rt2_tracer_enable_adaptive)");
+  int rc = Sync(t);
+  if (rc != RT2_OK) return rc;
+  size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n) HIP_TRY(hipMemcpy(out, t->d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+
+int rt2_tracer_adaptive_check(rt2_tracer* t, float threshold, int window, rt2_adaptive* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || !t->adaptive_on) return Fail(RT2_ERR_INVALID, "adaptive sampling not enabled (rt2_tracer_enable_adaptive)");
+  if (!(threshold >= 0.0f)) return Fail(RT2_ERR_INVALID, "adaptive_check: threshold must be >= 0");
+  if (window < 0 || window > kAdaptiveWindowMax) return Fail(RT2_ERR_INVALID, "adaptive_check: need 0 <= window <= 64");
+  int rc = Sync(t);
+  if (rc != RT2_OK) return rc;
+  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "adaptive_check needs at least 2 frames");
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  rt2_adaptive o;
+  memset(&o, 0, sizeof(o));
+  o.frames = t->frame_idx;
+  o.pixels = n;
+  if (n) {
+    HIP_TRY(hipSetDevice(t->device));
+    // the check's scratch: [tiles] uint2 counts, [tiles] offsets, then (8-byte aligned) partials and totals
+    const size_t tiles = AdaptiveTiles(t->width, t->local_rows), blocks = AdaptiveBlocks((uint32_t)n);
+    char* base = static_cast<char*>(t->d_ad_scratch);
+    uint32_t* offsets = reinterpret_cast<uint32_t*>(base + tiles * 8);
+    const size_t part_at = (tiles * 12 + 7) / 8 * 8;
+    AdaptivePartial* partials = reinterpret_cast<AdaptivePartial*>(base + part_at);
+    AdaptiveTotals* totals = reinterpret_cast<AdaptiveTotals*>(base + part_at + blocks * sizeof(AdaptivePartial));
+    if (part_at + blocks * sizeof(AdaptivePartial) + sizeof(AdaptiveTotals) > t->ad_scratch_bytes)
+      return Fail(RT2_ERR_INVALID, "adaptive_check: scratch buffer too small");
+    AdaptiveTotals h;
+    hipError_t e = LaunchAdaptiveCheck(t->d_accum, t->d_moment2, t->d_counts, t->d_over, t->d_active, t->d_list,
+                                       t->d_slot_of, base, offsets, partials, totals, t->width, t->local_rows, threshold,
+                                       window, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, totals, sizeof(h), hipMemcpyDeviceToHost, t->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+    t->host_waits++;
+    if (e != hipSuccess) return HipFail(e, "adaptive check");
+    if (h.active > n) return Fail(RT2_ERR_HIP, "adaptive check: active count out of range");
+    t->n_active = (uint32_t)h.active;
+    o.active = h.active;
+    o.retired = h.retired;
+    o.samples = h.samples;
+    o.nonfinite = h.nonfinite;
+  }
+  *out = o;
+  return RT2_OK;
+}
+
+int rt2_tracer_render_adaptive(rt2_tracer* t, float threshold, int window, int min_frames, int max_frames,
+                               int check_every, rt2_adaptive* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || !t->adaptive_on) return Fail(RT2_ERR_INVALID, "adaptive sampling not enabled (rt2_tracer_enable_adaptive)");
+  if (!(threshold >= 0.0f) || window < 0 || window > kAdaptiveWindowMax || min_frames < 0 || max_frames < 0 ||
+      check_every < 0)
+    return Fail(RT2_ERR_INVALID, "render_adaptive: need threshold >= 0, 0 <= window <= 64, min_frames, max_frames, "
+                                 "check_every >= 0");
+  int step = check_every;
+  if (step == 0) {  // one sweep of the sqrt_spp x sqrt_spp strata (RayTracer.cpp:59-60)
+    const int sq = t->camera.Params().sqrt_spp;
+    if (sq <= 0) return Fail(RT2_ERR_INVALID, "samples_per_pixel gives sqrt_spp = 0");
+    step = (int)std::min<int64_t>((int64_t)sq * sq, 0x7FFFFFFF);
+  }
+  const int64_t first_check = std::max(min_frames, 2);
+  memset(out, 0, sizeof(*out));
+  int64_t f = rt2_tracer_frame_idx(t);
+  while (f < max_frames) {
+    int rc = rt2_tracer_render(t, (int)std::min<int64_t>(step, max_frames - f));
+    if (rc != RT2_OK) return rc;
+    f = rt2_tracer_frame_idx(t);
+    if (f < first_check) continue;
+    if ((rc = rt2_tracer_adaptive_check(t, threshold, window, out)) != RT2_OK) return rc;
+    if (out->active == 0) return RT2_OK;
+  }
   return RT2_OK;
 }
 
@@ -1934,6 +2117,7 @@ int rt2_tracer_join(rt2_tracer* t, const uint8_t* unique_id, int world, int rank
   if (!t || !unique_id) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: null argument");
   if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: a multi-GPU tracer has its own communicators");
   if (t->comm) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: already joined");
+  if (t->adaptive_on) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: adaptive sampling is on (one-GPU tracers only)");
   int rc = rt2_tracer_set_partition(t, band_h > 0 ? band_h : kDefaultBandH, rank, world);
   if (rc != RT2_OK) return rc;
   ncclUniqueId id;

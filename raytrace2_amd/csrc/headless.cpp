@@ -4,7 +4,7 @@
 // boundary (tests/test_gpu_headless.py runs it and compares its PNG with the Python path's).
 //
 //   rt2_headless <scene.json> <out.png> [--settings settings.json] [--samples N] [--size WxH] [--gpus N]
-//                [--noise-target X [--max-samples N]]
+//                [--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]]
 //
 // Without --settings the reference's Settings.hpp defaults apply (num_samples 1, max_depth 50);
 // --samples / --size override num_samples and the output dims (App.cpp:115-124: scene dims, else
@@ -12,6 +12,9 @@
 // --noise-target X renders until the image's rms noise estimate is at most X instead of a fixed count
 // (RenderUntil with moments on, one check per stratum sweep), at most N = --max-samples frames (default:
 // num_samples), with samples_per_pixel = N; it prints "frames <n> rms <x>" on stderr.
+// --adaptive THRESHOLD renders with adaptive sampling (RenderAdaptive with moments on, one check per
+// stratum sweep, --window N columns, default 1): pixels whose noise estimate is at most THRESHOLD retire,
+// at most N = --max-samples frames (default: num_samples); it prints "frames <f> active <a> samples <s>".
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -23,7 +26,7 @@
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene.json> <out.png> [--settings f] [--samples N] [--size WxH] [--gpus N] "
-                         "[--noise-target X [--max-samples N]]\n", argv[0]);
+                         "[--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]]\n", argv[0]);
     return 2;
   }
   const std::string scene_path = argv[1], out_path = argv[2];
@@ -33,6 +36,8 @@ int main(int argc, char** argv) {
   int gpus = 0;  // 0: the one-GPU tracer; N >= 1: rt2_tracer_create_multi over GPUs 0..N-1
   float noise_target = -1.f;  // >= 0: render until converged
   long max_samples = -1;
+  float adaptive = -1.f;  // >= 0: adaptive sampling with this threshold
+  int window = 1;
   try {
     for (int i = 3; i + 1 < argc; i += 2) {
       if (!std::strcmp(argv[i], "--settings")) {
@@ -44,6 +49,17 @@ int main(int argc, char** argv) {
       } else if (!std::strcmp(argv[i], "--noise-target")) {
         noise_target = std::strtof(argv[i + 1], nullptr);
         if (!(noise_target >= 0.f)) return 2;
+      } else if (!std::strcmp(argv[i], "--adaptive")) {
+        adaptive = std::strtof(argv[i + 1], nullptr);
+        if (!(adaptive >= 0.f)) return 2;
+      } else if (!std::strcmp(argv[i], "--window")) {
+        char* end = nullptr;
+        const long v = std::strtol(argv[i + 1], &end, 10);
+        if (end == argv[i + 1] || *end != '\0' || v < 0 || v > 64) {
+          std::fprintf(stderr, "--window needs an integer in [0, 64]\n");
+          return 2;
+        }
+        window = (int)v;
       } else if (!std::strcmp(argv[i], "--max-samples")) {
         max_samples = std::atol(argv[i + 1]);
       } else if (!std::strcmp(argv[i], "--size")) {
@@ -54,8 +70,9 @@ int main(int argc, char** argv) {
       }
     }
     if (samples > 0) settings.num_samples = (size_t)samples;
-    const bool until = noise_target >= 0.f;
-    if (until && max_samples > 0) settings.num_samples = (size_t)max_samples;  // the bound, and the strata
+    const bool until = noise_target >= 0.f, adapt = adaptive >= 0.f;
+    if (until && adapt) return 2;
+    if ((until || adapt) && max_samples > 0) settings.num_samples = (size_t)max_samples;  // the bound, and the strata
 
     rt2::serialize::SceneLoader loader;
     auto scene_opt = loader.LoadScene(scene_path);
@@ -73,12 +90,17 @@ int main(int argc, char** argv) {
     scene.cam.SetSamplesPerPixel((int)settings.num_samples);
     tracer.camera = &scene.cam;
     tracer.OnResize(dims);
-    if (until) tracer.EnableMoments();
+    if (until || adapt) tracer.EnableMoments();
+    if (adapt) tracer.EnableAdaptive();
 
     const auto t0 = std::chrono::steady_clock::now();
     if (until) {
       const rt2_noise nz = tracer.RenderUntil(scene, noise_target, (int)settings.num_samples);
       std::fprintf(stderr, "frames %zu rms %.9g\n", (size_t)tracer.FrameIdx(), (double)nz.rms);
+    } else if (adapt) {
+      const rt2_adaptive a = tracer.RenderAdaptive(scene, adaptive, (int)settings.num_samples, window);
+      std::fprintf(stderr, "frames %zu active %llu samples %llu\n", (size_t)tracer.FrameIdx(),
+                   (unsigned long long)a.active, (unsigned long long)a.samples);
     } else {
       for (size_t i = 0; i < settings.num_samples; i++) tracer.Update(scene);
     }
@@ -92,7 +114,7 @@ int main(int argc, char** argv) {
                 "\"mray_s\": %.1f, \"launches\": %llu, \"gpus\": %d}\n",
                 (size_t)tracer.FrameIdx(), dims.x, dims.y, (unsigned long long)st.rays, s, st.rays / s / 1e6,
                 (unsigned long long)st.launches, tracer.NumGpus());
-    if (until) return tracer.FrameIdx() >= 1 && tracer.FrameIdx() <= settings.num_samples ? 0 : 3;
+    if (until || adapt) return tracer.FrameIdx() >= 1 && tracer.FrameIdx() <= settings.num_samples ? 0 : 3;
     return tracer.FrameIdx() == settings.num_samples ? 0 : 3;
   } catch (const rt2::Error& e) {
     std::fprintf(stderr, "rt2 error %d: %s\n", e.code, e.what());

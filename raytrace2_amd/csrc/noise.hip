@@ -7,6 +7,7 @@
 // for the sum and the maximum, whose every step adds the same two values in both lanes), then across
 // the four waves through LDS in wave order. Each workgroup writes one partial; the host adds the
 // partials in block order. No atomics: the same image gives the same bits every time.
+// counts (adaptive sampling, else null): each pixel's own sample count n_p in place of n_frames.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -21,6 +22,7 @@ constexpr int kNoiseWaves = kNoiseBlock / 64;
 
 __global__ __launch_bounds__(kNoiseBlock) void noise_kernel(const float* __restrict__ accum,
                                                             const float* __restrict__ moment2,
+                                                            const uint32_t* __restrict__ counts,
                                                             float* __restrict__ sem, NoisePartial* __restrict__ partials,
                                                             uint32_t npix, long long n_frames, double threshold) {
   __shared__ NoisePartial part[kNoiseWaves];
@@ -31,7 +33,7 @@ __global__ __launch_bounds__(kNoiseBlock) void noise_kernel(const float* __restr
   if (i < npix) {
     const float a[3] = {accum[3ull * i], accum[3ull * i + 1], accum[3ull * i + 2]};
     const float q[3] = {moment2[3ull * i], moment2[3ull * i + 1], moment2[3ull * i + 2]};
-    const PixelNoise pn = NoiseOfPixel(a, q, (int64_t)n_frames);
+    const PixelNoise pn = NoiseOfPixel(a, q, counts ? (int64_t)counts[i] : (int64_t)n_frames);
     if (sem) {
       sem[3ull * i] = pn.sem[0];
       sem[3ull * i + 1] = pn.sem[1];
@@ -79,11 +81,11 @@ __global__ __launch_bounds__(kNoiseBlock) void noise_kernel(const float* __restr
 uint32_t NoiseBlocks(uint32_t npix) { return (npix + (uint32_t)dev::kNoiseBlock - 1u) / (uint32_t)dev::kNoiseBlock; }
 
 // sem: float3 per pixel, or null; partials: NoiseBlocks(npix) entries.
-hipError_t LaunchNoise(const float* accum, const float* moment2, float* sem, NoisePartial* partials, uint32_t npix,
-                       int64_t n_frames, float threshold, hipStream_t stream) {
+hipError_t LaunchNoise(const float* accum, const float* moment2, const uint32_t* counts, float* sem,
+                       NoisePartial* partials, uint32_t npix, int64_t n_frames, float threshold, hipStream_t stream) {
   if (npix == 0) return hipSuccess;
-  hipLaunchKernelGGL(dev::noise_kernel, dim3(NoiseBlocks(npix)), dim3(dev::kNoiseBlock), 0, stream, accum, moment2, sem,
-                     partials, npix, (long long)n_frames, (double)threshold);
+  hipLaunchKernelGGL(dev::noise_kernel, dim3(NoiseBlocks(npix)), dim3(dev::kNoiseBlock), 0, stream, accum, moment2, counts,
+                     sem, partials, npix, (long long)n_frames, (double)threshold);
   return hipGetLastError();
 }
 

@@ -2312,8 +2312,15 @@ constexpr uint32_t StageGroup() {
   return MinWaves<F, kMode, kStats>() <= 7 && !LdsRng<F, kMode, kStats>() ? 8u : 4u;
 }
 
-template <uint32_t F, int kMode, bool kStats>
-__global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render_kernel(const RenderParams P) {
+// FL: the scene's feature set F, and for the list kernels (adaptive sampling) the bit kFeatList: their work
+// items run over the slots of RenderParams::active_list instead of the image's tiles. (A bit of the
+// feature word, not a template parameter of its own: the kernels without it keep their names, by which
+// tools and tests pick them out of the ISA, and their source is the source it was.)
+constexpr uint32_t kFeatList = 0x80000000u;
+template <uint32_t FL, int kMode, bool kStats>
+__global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~kFeatList), kMode, kStats>())) void render_kernel(const RenderParams P) {
+  constexpr uint32_t F = FL & ~kFeatList;
+  constexpr bool kList = (FL & kFeatList) != 0u;
   constexpr bool kLds = kMode == kModeStackLds || kMode == kModeStackHybrid;
   constexpr uint32_t kGroup = StageGroup<F, kMode, kStats>();
   constexpr uint32_t kPlanes = kGroup ? 3u * (kGroup - 1u) : 1u;  // [slot][component] planes of 64 lanes
@@ -2438,7 +2445,24 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
           static_assert(RT2_KOFF(frame_tile) == RT2_KOFF(frame_tiles) + 4 &&
                             RT2_KOFF(div_frame_tile) == RT2_KOFF(frame_tiles) + 8, "RenderParams layout");
           const u32x4 ft = karg4<RT2_KOFF(frame_tiles)>();  // frame_tiles, frame_tile, div_frame_tile
-          if (ft[0] != 0u) {  // frame tiles: one pixel x 64 consecutive one-frame chunks per 64 items
+          if constexpr (kList) {
+            // item -> (chunk, list slot) in either item shape, the slot's local pixel -> (x, local row).
+            // A padding slot holds width * local_rows: its row fails the partition check below.
+            uint32_t ls;
+            if (ft[0] != 0u) {  // frame tiles: frame_tile = 64 * slots
+              const uint32_t g = udiv(item, Magic{ft[2], ft[3]});
+              const uint32_t rem = item - g * ft[1];
+              ls = rem >> 6;
+              chunk = g * 64u + (rem & 63u);
+            } else {  // chunk-major over the slots padded to 64 (tile_items)
+              chunk = udiv(item, A.div_tile_items());
+              ls = item - chunk * A.tile_items();
+            }
+            const unsigned long long dw = karg2<RT2_KOFF(div_width)>();
+            const uint32_t pix = P.active_list[ls];
+            r = (int)udiv(pix, Magic{(uint32_t)dw, (uint32_t)(dw >> 32)});
+            x = (int)(pix - (uint32_t)r * (uint32_t)A.width());
+          } else if (ft[0] != 0u) {  // frame tiles: one pixel x 64 consecutive one-frame chunks per 64 items
             const unsigned long long dw = karg2<RT2_KOFF(div_width)>();
             const uint32_t g = udiv(item, Magic{ft[2], ft[3]});
             const uint32_t rem = item - g * ft[1];
@@ -2672,7 +2696,15 @@ __global__ __launch_bounds__(kBlock, (MinWaves<F, kMode, kStats>())) void render
       const uint32_t lidx = A.world() > 1 ? local_index(A, px, py) : path.pix;
       const uint32_t fr = path.frame - (uint32_t)A.frame_begin();  // launch-relative frame
       const uint32_t slot = fr & (kOctet - 1u);
-      float* blk = A.samples() + 3ull * kOctet * ((unsigned long long)(fr / kOctet) * A.local_pixels() + lidx);
+      // (a list launch: the sample buffer is [frames][slots], local_pixels the slot count; the pixel's slot
+      // is loaded only at the frames whose samples reach memory, not at those staged in LDS)
+      uint32_t sidx = lidx;
+      if constexpr (kList) {
+        const bool stores = kGroup == 0u || (slot & (kGroup - 1u)) == kGroup - 1u ||
+                            ((dl >> 16) & kChunkLeftMask) == 0u;
+        sidx = stores ? P.slot_of[lidx] : 0u;
+      }
+      float* blk = A.samples() + 3ull * kOctet * ((unsigned long long)(fr / kOctet) * A.local_pixels() + sidx);
       const bool more = ((dl >> 16) & kChunkLeftMask) != 0u;  // frames of the chunk after this one
 #if RT2_EXP_TWICE & 512
       for (int rep2 = 0; rep2 < 2; rep2++) {
@@ -2859,6 +2891,63 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const float* __restrict
   }
 }
 
+// The accumulate pass of adaptive sampling (rt2.h "Adaptive sampling"; moments are always on there): one
+// thread per slot of the launch streams the slot's octets (the sample buffer is [frames][slots]) and
+// updates the sums of local pixel list[slot] (list null: every pixel is active, slot = pixel), in the same
+// frame order and with the same operations as accumulate_kernel<true>, adds the launch's frames to the
+// pixel's sample count n_p and writes the display value from accum / n_p.
+__global__ __launch_bounds__(256) void accumulate_list_kernel(const float* __restrict__ samples,
+                                                              const uint32_t* __restrict__ list,
+                                                              float* __restrict__ accum, float* __restrict__ moment2,
+                                                              uint32_t* __restrict__ counts,
+                                                              uint32_t* __restrict__ pixels, uint32_t nslots,
+                                                              int n_frames) {
+  const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
+  if (slot >= nslots) return;
+  const uint32_t i = list ? list[slot] : slot;
+  float a0 = accum[3 * i], a1 = accum[3 * i + 1], a2 = accum[3 * i + 2];
+  float q0 = moment2[3 * i], q1 = moment2[3 * i + 1], q2 = moment2[3 * i + 2];
+  const float4* s = reinterpret_cast<const float4*>(samples) + 6ull * slot;
+  const unsigned long long stride = 6ull * nslots;  // float4s per octet plane
+  for (int f = 0; f < n_frames; f += (int)kOctet, s += stride) {
+    float x[3 * kOctet];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      const float4 q = s[j];
+      x[4 * j] = q.x, x[4 * j + 1] = q.y, x[4 * j + 2] = q.z, x[4 * j + 3] = q.w;
+    }
+    const int m = n_frames - f < (int)kOctet ? n_frames - f : (int)kOctet;  // frames of this octet
+#pragma unroll
+    for (int k = 0; k < (int)kOctet; k++) {
+      if (k < m) {
+        a0 += x[3 * k];
+        a1 += x[3 * k + 1];
+        a2 += x[3 * k + 2];
+        q0 = q0 + x[3 * k] * x[3 * k];
+        q1 = q1 + x[3 * k + 1] * x[3 * k + 1];
+        q2 = q2 + x[3 * k + 2] * x[3 * k + 2];
+      }
+    }
+  }
+  accum[3 * i] = a0;
+  accum[3 * i + 1] = a1;
+  accum[3 * i + 2] = a2;
+  moment2[3 * i] = q0, moment2[3 * i + 1] = q1, moment2[3 * i + 2] = q2;
+  const uint32_t np = counts[i] + (uint32_t)n_frames;
+  counts[i] = np;
+  if (pixels) {
+    const float fi = (float)np;
+    const float cc[3] = {a0 / fi, a1 / fi, a2 / fi};
+    uint32_t rgba = 0xFF000000u;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      float v = gmin(gmax(cc[k], 0.0f), 1.0f);
+      rgba |= ((uint32_t)(uint8_t)floor((double)v * 255.999)) << (8 * k);
+    }
+    pixels[i] = rgba;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Instantiated feature sets (a launch picks the smallest superset of the scene's features).
 constexpr uint32_t kVariants[] = {
@@ -2888,11 +2977,31 @@ KernelFn PickMode(int mode, bool stats) {
   }
 }
 
-KernelFn Kernel(int v, int mode, bool stats) {
+// The kernels over an active list (rt2.h "Adaptive sampling"): instantiated for the threaded traversal only,
+// the mode launches select by default.
+template <int V>
+KernelFn PickList(bool stats) {
+  return stats ? reinterpret_cast<KernelFn>(&render_kernel<kVariants[V] | kFeatList, kModeLinear, true>)
+               : reinterpret_cast<KernelFn>(&render_kernel<kVariants[V] | kFeatList, kModeLinear, false>);
+}
+
+// list: the kernel over an active list (threaded traversal only; null for the other modes).
+KernelFn Kernel(int v, int mode, bool stats, bool list = false) {
 #ifdef RT2_ONLY_VARIANT  // register-allocation experiments: one threaded product kernel only (not a usable build)
-  (void)v, (void)mode, (void)stats;
+  (void)v, (void)mode, (void)stats, (void)list;
   return reinterpret_cast<KernelFn>(&render_kernel<kVariants[RT2_ONLY_VARIANT], kModeLinear, false>);
 #else
+  if (list) {
+    if (mode != kModeLinear) return nullptr;
+    switch (v) {
+      case 0: return PickList<0>(stats);
+      case 1: return PickList<1>(stats);
+      case 2: return PickList<2>(stats);
+      case 3: return PickList<3>(stats);
+      case 4: return PickList<4>(stats);
+    }
+    return nullptr;
+  }
   switch (v) {
     case 0: return PickMode<0>(mode, stats);
     case 1: return PickMode<1>(mode, stats);
@@ -3146,9 +3255,19 @@ size_t RenderLdsBytes(const RenderParams& p) {
 
 // Launch entry used by capi.cpp. grid = resident workgroups (persistent lanes).
 hipError_t LaunchRender(const RenderParams& p, int variant, bool stats, int grid, hipStream_t stream) {
-  dev::KernelFn fn = dev::Kernel(variant, RenderMode(p), stats);
+  // a launch that carries an active list runs the list kernel (capi.cpp refuses one outside the threaded mode)
+  dev::KernelFn fn = dev::Kernel(variant, RenderMode(p), stats, p.active_list != nullptr);
   if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(dev::kBlock), RenderLdsBytes(p), stream, p);
+  return hipGetLastError();
+}
+
+// The accumulate pass of adaptive sampling over a launch's nslots slots (list null: slot = pixel).
+hipError_t LaunchAccumulateList(const float* samples, const uint32_t* list, float* accum, float* moment2,
+                                uint32_t* counts, uint8_t* pixels, uint32_t nslots, int n_frames, hipStream_t stream) {
+  if (nslots == 0) return hipSuccess;
+  hipLaunchKernelGGL(dev::accumulate_list_kernel, dim3((nslots + 255u) / 256u), dim3(256), 0, stream, samples, list,
+                     accum, moment2, counts, reinterpret_cast<uint32_t*>(pixels), nslots, n_frames);
   return hipGetLastError();
 }
 
@@ -3167,9 +3286,9 @@ hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsign
   return hipGetLastError();
 }
 
-int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes) {
+int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes, bool list) {
   int n = 0;
-  dev::KernelFn fn = dev::Kernel(variant, mode, stats);
+  dev::KernelFn fn = dev::Kernel(variant, mode, stats, list);
   if (!fn) return 1;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(fn), dev::kBlock,
                                                              lds_bytes);

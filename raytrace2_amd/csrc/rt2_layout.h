@@ -324,6 +324,14 @@ struct RenderParams {
   // kernel reads the records from lind, materials and textures.
   const void* hit_table;
   uint32_t hit_bytes;
+  // Adaptive sampling (adaptive.hip), a launch over the active pixels only; null: every local pixel.
+  // Work items then run over list slots instead of tile lanes: tile_items is the slot count padded to
+  // 64 (frame tiles: frame_tile = 64 * slots), slot s renders local pixel active_list[s] (padding slots
+  // hold width * local_rows, which decodes to a row past the partition, like a lane of an edge tile),
+  // and local_pixels is the slot count: the sample buffer is [frames][slots], indexed by
+  // slot_of[local pixel]. Only the list kernels (render.hip kFeatList) read these two.
+  const uint32_t* active_list;
+  const uint32_t* slot_of;
 };
 constexpr int kClockRing = 512;  // launch-clock pairs per tracer (drained at half)
 

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._native import AppSettings as _AppSettings
-from ._native import UNIQUE_ID_BYTES, CameraDesc, Noise, SceneInfo, Stats, check, lib
+from ._native import UNIQUE_ID_BYTES, Adaptive, CameraDesc, Noise, SceneInfo, Stats, check, lib
 
 DEFAULT_SEED = 0x5EED2024
 
@@ -427,6 +427,35 @@ class RayTracer:
         check(lib.rt2_tracer_render_until(self._h, float(target_rms), int(min_frames), int(max_frames),
                                           int(check_every), ctypes.byref(n)))
         return n.as_dict()
+
+    # -- adaptive sampling (rt2.h "Adaptive sampling") ----------------------------------------
+    def enable_adaptive(self, on: bool = True) -> None:
+        """Retire converged pixels and render only the rest (needs enable_moments; resets the frame)."""
+        check(lib.rt2_tracer_enable_adaptive(self._h, 1 if on else 0))
+
+    def sample_counts(self) -> np.ndarray:
+        """uint32 sample count n_p per local pixel."""
+        w, _ = self.Dims()
+        out = np.zeros((self.local_rows(), w), np.uint32)
+        check(lib.rt2_tracer_sample_counts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def adaptive_check(self, threshold: float, window: int = 1) -> dict:
+        """Retires the active pixels with no pixel over `threshold` within `window` columns of their row;
+        rt2_adaptive as a dict: frames, pixels, active, retired, samples, nonfinite."""
+        a = Adaptive()
+        check(lib.rt2_tracer_adaptive_check(self._h, float(threshold), int(window), ctypes.byref(a)))
+        return a.as_dict()
+
+    def render_adaptive(self, threshold: float, max_frames: int, window: int = 1, min_frames: int = 0,
+                        check_every: int = 0) -> dict:
+        """Renders in steps of check_every frames (0: one stratum sweep) with a check after each, until no
+        pixel is active or FrameIdx() reaches max_frames; returns the last check (adaptive_check())."""
+        self._push_camera()
+        a = Adaptive()
+        check(lib.rt2_tracer_render_adaptive(self._h, float(threshold), int(window), int(min_frames),
+                                             int(max_frames), int(check_every), ctypes.byref(a)))
+        return a.as_dict()
 
     def enable_stats(self, on: bool = True) -> None:
         check(lib.rt2_tracer_enable_stats(self._h, 1 if on else 0))
