@@ -67,6 +67,10 @@ typedef struct {
                              * quads, one flat record each, which the Cornell-box kernel stages in LDS); 0:
                              * none (RT2_HIT_TABLE=0 at load, nested transforms, no quad, or a table too
                              * large to stage without lowering the kernel's occupancy) */
+  int flat_steps;           /* length of the scene's flat program (its threaded program without the BVH steps,
+                             * walked with a per-lane certificate, DESIGN.md §4 "Flat walk of small BVHs"); 0:
+                             * none (RT2_FLAT_BVH=0 at load, or the scene does not qualify: more than 8 BVH
+                             * leaves, a sphere, a medium, a nested transform) */
 } rt2_scene_info;
 RT2_API int rt2_scene_get_info(const rt2_scene* scene, rt2_scene_info* out);
 /* Material table, 8 floats per material: type, albedo.xyz, fuzz, refraction_index, tex_idx, 0.
@@ -277,6 +281,12 @@ typedef struct {
    * from global memory (no table, a kernel that takes none, such as the counting kernels, or a table that
    * would have lowered the kernel's occupancy) */
   uint64_t hit_table_bytes;
+  /* the flat walk (launches over a scene's flat program; counted in every such launch, 0 otherwise): lanes
+   * whose hit the certificate left open, and wave-bounces that traced the BVH program again for them.
+   * flat_fallback_hits: the hits those wave-bounces ended with, over all their lanes. RT2_FLAT_BVH=2 at scene
+   * load certifies no hit: every wave-bounce with a hit falls back, and both flat_uncertified and
+   * flat_fallback_hits are the number of hits */
+  uint64_t flat_uncertified, flat_wave_fallbacks, flat_fallback_hits;
 } rt2_stats;
 RT2_API int rt2_tracer_get_stats(rt2_tracer* tr, rt2_stats* out);
 /* The stats of GPU `part` of a multi-GPU tracer (part 0 of a one-GPU tracer is itself). */

@@ -34,7 +34,7 @@ class SceneInfo(ctypes.Structure):
                 ("max_stack", ctypes.c_int), ("bvh_depth", ctypes.c_int), ("node_bytes", ctypes.c_uint64),
                 ("acc_lists", ctypes.c_int), ("acc_nodes", ctypes.c_int), ("linear_steps", ctypes.c_int),
                 ("origins_bounded", ctypes.c_int), ("box_steps", ctypes.c_int),
-                ("hit_table_bytes", ctypes.c_int)]
+                ("hit_table_bytes", ctypes.c_int), ("flat_steps", ctypes.c_int)]
 
 
 class CameraDesc(ctypes.Structure):
@@ -72,7 +72,10 @@ class Stats(ctypes.Structure):
                                                                            ("box_certified", ctypes.c_uint64),
                                                                            ("box_wave_visits", ctypes.c_uint64),
                                                                            ("box_wave_runs", ctypes.c_uint64),
-                                                                           ("hit_table_bytes", ctypes.c_uint64)]
+                                                                           ("hit_table_bytes", ctypes.c_uint64),
+                                                                           ("flat_uncertified", ctypes.c_uint64),
+                                                                           ("flat_wave_fallbacks", ctypes.c_uint64),
+                                                                           ("flat_fallback_hits", ctypes.c_uint64)]
 
     def as_dict(self):
         d = {n: (getattr(self, n) if n.endswith("_ms") else int(getattr(self, n))) for n, _ in self._fields_

@@ -15,6 +15,9 @@
 // passes through the box and that t lies in the interval, else no hit.
 // Where the certificate fails the lane falls back to the six-face run. DESIGN.md §4 "Box-level test"
 // has the proof; tests/cpp/box_cert.cpp checks it against the run on adversarial rays.
+//
+// Also here, so that the kernel's certificates have one home: FlatCertRule, the rule of the flat walk of small
+// BVHs (at the end of this file; DESIGN.md §4 "Flat walk of small BVHs", tests/cpp/flat_cert.cpp).
 #pragma once
 #include <cstdint>
 
@@ -121,6 +124,23 @@ RT2_BOXAA_FN BoxAAPairResult BoxAAPair(const float* w, float mB, float ox, float
   r.tin = tin;
   r.tout = tout;
   return r;
+}
+
+// The flat walk's certificate rule (rt2_layout.h "Flat program"; DESIGN.md §4 "Flat walk of small BVHs";
+// checked by tests/cpp/flat_cert.cpp): the reference's slab test AABB::Hit of a ray with finite reciprocal
+// on the certificate box (lo, hi) with the interval (tmin, T), max(tmin, T_in) < min(T, T_out), every
+// bound (bound - o) * inv with one rounding per operation, grouped as render.hip slab_t groups them (min
+// and max are associative and commutative on non-NaN operands). The caller has checked that inv is finite
+// in all three components; a lane where it is not is uncertified.
+template <class M>
+RT2_BOXAA_FN bool FlatCertRule(const float* lo, const float* hi, float ox, float oy, float oz, float ix, float iy,
+                               float iz, float tmin, float T) {
+  const float ax = (lo[0] - ox) * ix, bx = (hi[0] - ox) * ix;
+  const float ay = (lo[1] - oy) * iy, by = (hi[1] - oy) * iy;
+  const float az = (lo[2] - oz) * iz, bz = (hi[2] - oz) * iz;
+  const float t0 = M::max3(M::min(ax, bx), M::min(ay, by), M::max(M::min(az, bz), tmin));
+  const float t1 = M::min3(M::max(ax, bx), M::max(ay, by), M::min(M::max(az, bz), T));
+  return !(t1 <= t0);
 }
 
 }  // namespace rt2

@@ -24,7 +24,7 @@
 
 namespace rt2 {
 hipError_t LaunchRender(const RenderParams& p, int variant, bool stats, int grid, hipStream_t stream);
-int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes, bool list = false);
+int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes, bool list = false, bool flat = false);
 hipError_t LaunchAccumulateList(const float* samples, const uint32_t* list, float* accum, float* moment2,
                                 uint32_t* counts, uint8_t* pixels, uint32_t nslots, int n_frames, hipStream_t stream);
 uint32_t AdaptiveBlocks(uint32_t npix);
@@ -45,6 +45,7 @@ int RenderVariant(uint32_t features);
 uint32_t RenderVariantFeatures(int v);
 size_t RenderLdsBytes(const RenderParams& p);
 bool RenderTakesHitTable(int variant, int mode, bool stats);
+bool RenderTakesFlat(int variant, int mode, bool stats, bool list);
 bool WriteImage(const float* pixels, int w, int h, const std::string& path, bool png, std::string& err);
 hipError_t LaunchDeinterleave(const float* stacks, float* image, float* image_nc, uint8_t* pixels, int width, int height, int band_h,
                               int world, int max_rows, int frame_idx, hipStream_t stream);
@@ -81,6 +82,11 @@ struct rt2_tracer {
   int hit_key = -1;             // cached: the kernel variant asked whether the table keeps its occupancy
   bool hit_fits = false;
   uint32_t last_hit_bytes = 0;  // the table the last launch staged in LDS (0: none)
+  // flat program (rt2_layout.h "Flat program"): its wide steps, the certificate table, the FlatMode; null / 0:
+  // the scene has none
+  void* d_flat_wide = nullptr;
+  void* d_flat_cert = nullptr;
+  uint32_t flat_mode = 0;
   uint32_t lin_len = 0;
   bool use_linear = true;
   uint32_t root = kRefNone;
@@ -513,6 +519,7 @@ int rt2_scene_get_info(const rt2_scene* s, rt2_scene_info* o) {
   o->origins_bounded = c.origins_bounded ? 1 : 0;
   o->box_steps = c.box_steps;
   o->hit_table_bytes = (int)(c.hit.size() * sizeof(float));
+  o->flat_steps = c.flat_steps;
   return RT2_OK;
 }
 
@@ -687,6 +694,11 @@ int rt2_tracer_create(const rt2_scene* s, int device, rt2_tracer** out) {
       if ((rc = Upload(&t->d_hit, c.hit.data(), c.hit.size() * sizeof(float))) != RT2_OK) return rc;
       t->hit_bytes = (uint32_t)(c.hit.size() * sizeof(float));
     }
+    if (!c.flat_wide.empty() && c.flat_cert.size() == c.lind.size() && c.lin_xform_depth <= 1) {
+      if ((rc = Upload(&t->d_flat_wide, c.flat_wide.data(), c.flat_wide.size() * sizeof(uint32_t))) != RT2_OK) return rc;
+      if ((rc = Upload(&t->d_flat_cert, c.flat_cert.data(), c.flat_cert.size() * sizeof(float))) != RT2_OK) return rc;
+      t->flat_mode = c.flat_mode;
+    }
   }
   HIP_TRY(hipMalloc(&t->d_work, 128));
   HIP_TRY(hipMalloc(&t->d_clock, 2 * sizeof(unsigned long long) * kClockRing));
@@ -770,6 +782,8 @@ void rt2_tracer_destroy(rt2_tracer* t) {
   (void)hipFree(t->d_lin_wide);
   (void)hipFree(t->d_lind);
   (void)hipFree(t->d_hit);
+  (void)hipFree(t->d_flat_wide);
+  (void)hipFree(t->d_flat_cert);
   (void)hipFree(t->d_work);
   (void)hipFree(t->d_stats);
   for (auto& sl : t->slots) {
@@ -1213,26 +1227,39 @@ int LaunchFrames(rt2_tracer* t, int n_frames) {
   p.lds_nodes = lds ? t->node_records : hot;
   p.lds_partial = (!lds && hot) ? 1u : 0u;
   // The hit table in LDS, for the kernels that take it (render.hip HitTable()), when the kernel keeps
-  // the occupancy it has without the table: the runtime is asked with and without it
+  // the occupancy it has without the table: the runtime is asked with and without it.
+  // The flat program, for the launches whose kernel walks it (render.hip kFeatFlat: the Cornell kernel with
+  // its hit table staged): decided per launch, so a counting launch, a launch over an active list or one
+  // whose table is not staged walks the BVH program of the same scene.
   if (p.lin_len && t->d_hit && t->flat_xforms && RenderTakesHitTable(variant, kModeLinear, counting)) {
-    const int hkey = variant * 2 + (listed ? 1 : 0);  // (the list kernel is asked about itself)
-    if (t->hit_key != hkey) {
-      t->hit_fits = RenderBlocksPerCU(variant, kModeLinear, counting, t->hit_bytes, listed) >=
-                    RenderBlocksPerCU(variant, kModeLinear, counting, 0, listed);
-      t->hit_key = hkey;
+    const auto fits = [&](bool flat_kernel) {  // (the list / flat kernel is asked about itself)
+      const int hkey = variant * 4 + (listed ? 1 : 0) + (flat_kernel ? 2 : 0);
+      if (t->hit_key != hkey) {
+        t->hit_fits = RenderBlocksPerCU(variant, kModeLinear, counting, t->hit_bytes, listed, flat_kernel) >=
+                      RenderBlocksPerCU(variant, kModeLinear, counting, 0, listed, flat_kernel);
+        t->hit_key = hkey;
+      }
+      return t->hit_fits;
+    };
+    const bool flat_want = t->d_flat_wide && t->flat_mode != 0u && RenderTakesFlat(variant, kModeLinear, counting, listed);
+    if (flat_want && fits(true)) {
+      p.flat_wide = t->d_flat_wide;
+      p.flat_cert = t->d_flat_cert;
+      p.flat_mode = t->flat_mode;
     }
-    if (t->hit_fits) {
+    if (p.flat_wide != nullptr || fits(false)) {
       p.hit_table = t->d_hit;
       p.hit_bytes = t->hit_bytes;
     }
   }
+  const bool flat = p.flat_wide != nullptr;
   t->last_hit_bytes = p.hit_bytes;
   // resident lanes of this kernel instantiation (occupancy query cached: it costs far more than
   // a one-frame launch)
   const size_t lds_bytes = RenderLdsBytes(p);
-  const int okey = variant * 16 + RenderMode(p) * 2 + (counting ? 1 : 0) + (listed ? 8 : 0);
+  const int okey = variant * 32 + RenderMode(p) * 2 + (counting ? 1 : 0) + (listed ? 8 : 0) + (flat ? 16 : 0);
   if (t->occ_key != okey || t->occ_lds != lds_bytes) {
-    t->occ_blocks = RenderBlocksPerCU(variant, RenderMode(p), counting, lds_bytes, listed);
+    t->occ_blocks = RenderBlocksPerCU(variant, RenderMode(p), counting, lds_bytes, listed, flat);
     t->occ_key = okey;
     t->occ_lds = lds_bytes;
   }
@@ -1975,6 +2002,9 @@ int rt2_tracer_get_stats(rt2_tracer* t, rt2_stats* o) {
       sum.box_certified += s.box_certified;
       sum.box_wave_visits += s.box_wave_visits;
       sum.box_wave_runs += s.box_wave_runs;
+      sum.flat_uncertified += s.flat_uncertified;
+      sum.flat_wave_fallbacks += s.flat_wave_fallbacks;
+      sum.flat_fallback_hits += s.flat_fallback_hits;
       sum.hit_table_bytes = std::max(sum.hit_table_bytes, s.hit_table_bytes);
       sum.launches = std::max(sum.launches, s.launches);
       sum.kernel_ms = std::max(sum.kernel_ms, s.kernel_ms);
@@ -2013,6 +2043,9 @@ int rt2_tracer_get_stats(rt2_tracer* t, rt2_stats* o) {
   o->box_certified = s[StatsCounters::kBoxCertified];
   o->box_wave_visits = s[StatsCounters::kBoxWaveVisits];
   o->box_wave_runs = s[StatsCounters::kBoxWaveRuns];
+  o->flat_uncertified = s[StatsCounters::kFlatUncertified];
+  o->flat_wave_fallbacks = s[StatsCounters::kFlatWaveFallbacks];
+  o->flat_fallback_hits = s[StatsCounters::kFlatFallbackHits];
   o->hit_table_bytes = t->last_hit_bytes;
   for (int k = 0; k < 4; k++) o->stamps[k] = s[StatsCounters::kStamps + k];
   for (int k = 0; k < 8; k++) o->diag[k] = s[StatsCounters::kDiag + k];

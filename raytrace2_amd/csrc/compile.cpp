@@ -669,6 +669,51 @@ struct Flattener {
     }
     return BoxAAWordsOf(faces, bw, mB);
   }
+  // Flat program (rt2_layout.h): whether the scene qualifies. The root BVH's leaves, counted in pre-order
+  // (a span-1 node's left == right once), are at most kFlatBvhMaxLeaves, each a quad, a list of quads or a
+  // transform of one of those; and every BVH node's stored bounds are finite and contain its child nodes'
+  // bounds bit for bit (AABB(a, b) unions with fmin / fmax and PadToMinimums only enlarges, so this holds
+  // for the loader's trees; it is what the certificate's monotonicity argument stands on, so it is checked
+  // here and the scene keeps its BVH walk where it fails).
+  bool bvh_apart = false;        // BVH node records go after the leaves' records in `lind`
+  std::vector<float> lind_bvh;   // (collected here while bvh_apart)
+  static constexpr uint32_t kApartBase = 0x40000000u;
+  bool QuadsOnly(int i) const {
+    const Obj& o = s.objs[(size_t)i];
+    if (o.kind == kQuad) return true;
+    if (o.kind != kList || acc_depth.count(i)) return false;
+    for (int c : o.children)
+      if (s.objs[(size_t)c].kind != kQuad) return false;
+    return !o.children.empty();
+  }
+  static bool BoxFinite(const AABB& b) {
+    for (float v : {b.x.min, b.x.max, b.y.min, b.y.max, b.z.min, b.z.max})
+      if (!std::isfinite(v)) return false;
+    return true;
+  }
+  static bool BoxNested(const AABB& p, const AABB& c) {
+    return p.x.min <= c.x.min && c.x.max <= p.x.max && p.y.min <= c.y.min && c.y.max <= p.y.max &&
+           p.z.min <= c.z.min && c.z.max <= p.z.max;
+  }
+  bool FlatSubtree(int i, int& leaves) const {
+    const Obj& o = s.objs[(size_t)i];
+    if (o.kind != kBvh || !BoxFinite(o.aabb)) return false;
+    const int kids[2] = {o.left, o.right};
+    for (int k = 0; k < (o.left == o.right ? 1 : 2); k++) {
+      const Obj& c = s.objs[(size_t)kids[k]];
+      if (c.kind == kBvh) {
+        if (!BoxNested(o.aabb, c.aabb) || !FlatSubtree(kids[k], leaves)) return false;
+      } else {
+        if (!(QuadsOnly(kids[k]) || (c.kind == kXform && QuadsOnly(c.child)))) return false;
+        if (++leaves > kFlatBvhMaxLeaves) return false;
+      }
+    }
+    return true;
+  }
+  bool FlatQualifies() const {
+    int leaves = 0;
+    return FlatSubtree(s.root, leaves) && leaves >= 1;
+  }
   bool ContainsAccList(int i) const {
     const Obj& o = s.objs[(size_t)i];
     if (o.kind == kList && acc_depth.count(i)) return true;
@@ -687,7 +732,9 @@ struct Flattener {
     };
     switch (o.kind) {
       case kBvh: {
-        size_t me = emit(kBvh, CopyRecords(src, kBvhRecords, lind), 0);
+        // (bvh_apart: the node's record goes after the leaves' records; CompileSceneWith fixes the offset)
+        size_t me = emit(kBvh, bvh_apart ? kApartBase + CopyRecords(src, kBvhRecords, lind_bvh)
+                                         : CopyRecords(src, kBvhRecords, lind), 0);
         if (!Linearize(o.left, parent_xf, lin, lind, xf_depth)) return false;
         if (!(o.left == o.right && !HasMedium(o.left))) {
           if (!Linearize(o.right, parent_xf, lin, lind, xf_depth)) return false;
@@ -1000,9 +1047,19 @@ bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool
     return false;
   }
   fl.SetBoxAA();
+  // RT2_FLAT_BVH=0: no flat program (the A/B baseline); 2: built, and the kernel certifies no hit
+  const char* fe = getenv("RT2_FLAT_BVH");
+  const int flat_env = fe ? atoi(fe) : 1;
+  const bool flat = flat_env != 0 && fl.FlatQualifies();
+  fl.bvh_apart = flat;
   if (!fl.Linearize(s.root, kRefNone, out.lin, out.lind)) {
     out.lin.clear();
     out.lind.clear();
+  } else if (flat) {
+    const uint32_t base = (uint32_t)(out.lind.size() / 4);
+    for (size_t i = 0; i < out.lin.size() / 4; i++)
+      if (out.lin[4 * i] == kBvh) out.lin[4 * i + 2] = out.lin[4 * i + 2] - Flattener::kApartBase + base;
+    out.lind.insert(out.lind.end(), fl.lind_bvh.begin(), fl.lind_bvh.end());
   }
   out.origins_bounded = fl.origins_bounded && !out.lin.empty();
   // The stack traversal needs max_stack entries per lane; the threaded program needs none, so a
@@ -1091,6 +1148,92 @@ bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool
       memcpy(&w[13], &b[4], 4);
       memcpy(&w[14], &b[5], 4);
       memcpy(&w[15], &b[6], 4);
+    }
+  }
+  // Flat program (rt2_layout.h): the BVH program's leaf steps in their order, without its kBvh steps; quad
+  // runs formed again over the new adjacency (a MakeBox run still exactly its six faces, flagged); the
+  // certificate box of each leaf = its parent BVH node's record, bit for bit, in the kXform step's wide
+  // entry and in the certificate table at each world-space quad's record offset.
+  if (flat && !out.lin.empty()) {
+    const size_t n = out.lin.size() / 4;
+    std::vector<uint32_t> fmap(n + 1, 0), flin;
+    std::vector<size_t> parent;                 // per flat step: its parent BVH step in the BVH program
+    std::vector<char> under;                    // per flat step: inside a transform
+    std::vector<std::pair<size_t, size_t>> open;  // BVH steps whose range holds the current step: (step, end)
+    bool in_xf = false, ok = true;
+    for (size_t i = 0; i < n; i++) {
+      while (!open.empty() && i >= open.back().second) open.pop_back();
+      fmap[i] = (uint32_t)(flin.size() / 4);
+      const uint32_t kind = out.lin[4 * i];
+      if (kind == kBvh) {
+        open.emplace_back(i, out.lin[4 * i + 1]);
+        continue;
+      }
+      if (open.empty() || !(kind == kQuad || kind == kXform || kind == kXformExit)) ok = false;
+      if (!ok) break;
+      flin.insert(flin.end(), {kind, out.lin[4 * i + 1], out.lin[4 * i + 2], out.lin[4 * i + 3]});
+      parent.push_back(open.back().first);
+      under.push_back(in_xf && kind == kQuad);
+      if (kind == kXform) in_xf = true;
+      if (kind == kXformExit) in_xf = false;
+    }
+    fmap[n] = (uint32_t)(flin.size() / 4);
+    const size_t m = flin.size() / 4;
+    if (ok && m > 0) {
+      std::vector<char> entry(m + 1, 0);
+      for (uint32_t b : fl.box_runs) entry[fmap[b]] = entry[fmap[b] + 6] = 1;
+      for (size_t j = 0; j < m; j++)
+        if (flin[4 * j] == kXform) flin[4 * j + 1] = fmap[flin[4 * j + 1]];  // its exit step
+      for (size_t j = m; j-- > 0;) {
+        if (flin[4 * j] != kQuad) continue;
+        uint32_t run = 1;
+        if (j + 1 < m && flin[4 * (j + 1)] == kQuad && !entry[j + 1] &&
+            flin[4 * (j + 1) + 2] == flin[4 * j + 2] + (uint32_t)kQuadRecords)
+          run = std::min((flin[4 * (j + 1) + 3] & kRunLenMask) + 1, kLinearMaxRun);
+        flin[4 * j + 3] = run;
+      }
+      for (size_t j = 0; j < m; j++) {
+        if (flin[4 * j] != kQuad) continue;
+        uint32_t codes = 0;
+        const uint32_t run = flin[4 * j + 3];
+        for (uint32_t k = 0; k < run; k++) codes |= fl.lind_axis.at(flin[4 * (j + k) + 2]) << (3 * k);
+        flin[4 * j + 1] = codes | (1u << (3 * run));
+      }
+      for (uint32_t b : fl.box_runs) {
+        const size_t j = fmap[b];
+        if (flin[4 * j] != kQuad || flin[4 * j + 3] != 6u || flin[4 * j + 1] != kBoxAARunCodes) {
+          err = "internal: a box's quads did not form its run in the flat program";
+          return false;
+        }
+        flin[4 * j + 3] |= kRunBoxFlag;
+      }
+      out.flat_wide.assign(16 * (m + 1), 0u);
+      out.flat_wide[16 * m] = kProgramEnd;
+      out.flat_cert.assign(out.lind.size(), 0.0f);
+      for (size_t j = 0; j < m; j++) {
+        uint32_t* w = &out.flat_wide[16 * j];
+        for (int k = 0; k < 4; k++) w[k] = flin[4 * j + k];
+        const size_t rec = 4 * (size_t)flin[4 * j + 2];
+        const float* box = &out.lind[4 * (size_t)out.lin[4 * parent[j] + 2]];  // (lo.xyz, _) (hi.xyz, _)
+        if (flin[4 * j] == kXform) {
+          memcpy(&w[4], &box[0], 12);
+          memcpy(&w[7], &box[4], 12);
+        } else {
+          for (size_t k = 0; k < 12 && rec + k < out.lind.size(); k++) memcpy(&w[4 + k], &out.lind[rec + k], 4);
+        }
+        if (flin[4 * j] == kQuad) {
+          float* c = &out.flat_cert[rec];
+          if (under[j]) {
+            const uint32_t f = kFlatCertXform;
+            memcpy(&c[3], &f, 4);
+          } else {
+            memcpy(&c[0], &box[0], 12);
+            memcpy(&c[4], &box[4], 12);
+          }
+        }
+      }
+      out.flat_mode = flat_env == 2 ? kFlatCertifyNothing : kFlatOn;
+      out.flat_steps = (int)m;
     }
   }
   PackMaterials(s, out);

@@ -55,7 +55,8 @@ constexpr int kBlock = 256;
                          // 16 quad-run test, 32 threaded medium step, 64 its log, 128 its two boundary
                          // queries, 256 a Philox block (at every refill), 512 the sample store /
                          // staging, 2048 a threaded transform entry (ray into model space, its reciprocal),
-                         // 4096 an accelerated list's lane walk, 8192 the box-level test of a MakeBox run
+                         // 4096 an accelerated list's lane walk, 8192 the box-level test of a MakeBox run,
+                         // 16384 the flat walk's certificate rule (each entry rule and the end rule)
 #endif
 #ifndef RT2_EXP_WAVESTEPS
 #define RT2_EXP_WAVESTEPS 0  // diagnostic build: per-wave linear-traversal step counts into diag slots
@@ -1566,11 +1567,21 @@ template <uint32_t F>
 constexpr bool BoxOn() {
   return true;
 }
-template <uint32_t F, bool kStats, class W, class G>
+// kFlat (the kernels with kFeatFlat): the walk of the launch's flat program (rt2_layout.h "Flat program":
+// no kBvh steps, so no slab test, no next-index search between leaves) with the certificate of DESIGN.md §4
+// "Flat walk of small BVHs": `uncert` returns whether this lane's hit is not proven to be the hit of the
+// BVH program's walk (the caller then traces that program for the lane). Entry rule at every kXform step
+// (the step's certificate box, the world ray, the lane's tmax there); end rule for a winner in world space
+// (its certificate box from the table, T = its t).
+template <uint32_t F, bool kStats, bool kFlat = false, class W, class G>
 __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wray, float time, G& path, HitRef& h,
-                                             lds_u32* cand, lds_u32* xray, Counters& cnt, bool tab = false) {
+                                             lds_u32* cand, lds_u32* xray, Counters& cnt, bool tab = false,
+                                             bool* uncert = nullptr) {
   const Nodes<kModeLinear> N{reinterpret_cast<const float4*>(P.lind)};  // boundaries / nested xforms
   const void* recs = P.lind;
+  const void* prog = kFlat ? P.flat_wide : P.lin_wide;
+  bool xfail = false;  // kFlat: the entry rule failed at the transform the lane is in
+  bool xunc = false;   // kFlat: the closest hit so far under a transform was accepted after a failed entry rule
   // the world ray's reciprocal stays in registers for the transforms' exits to world space (three
   // VGPRs live across the trace), except with the parked ray (book 2), which recomputes it there
   constexpr bool kKeepW = !__is_same(W, ParkRay);
@@ -1593,8 +1604,8 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   uint32_t i = wave_min_next(next);  // wave-uniform step = min over live lanes of `next`
   // (i reaches P.lin_len when every lane is done: the wide program's entry there is kProgramEnd)
   while (true) {
-    u32x16 sw = sld16(P.lin_wide, i * 64u);  // entry + the first 48 bytes of its record
-    if (sw[0] == kBvh) {
+    u32x16 sw = sld16(prog, i * 64u);  // entry + the first 48 bytes of its record
+    if (!kFlat && sw[0] == kBvh) {
       // A run of BVH steps in a loop of their own: only `next` changes from step to step, so
       // nothing else is carried (no register copies between kinds) and the step costs the slab
       // test, the next-index update and the wave-minimum search. A paired step (compile.cpp: word
@@ -1635,7 +1646,7 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
           next = kSel && !act ? next : nx;
         }
         i = wave_min_next(next);
-        sw = sld16(P.lin_wide, i * 64u);
+        sw = sld16(prog, i * 64u);
       } while (sw[0] == kBvh);
     }
     const u32x4 st = {sw[0], sw[1], sw[2], sw[3]};
@@ -1778,6 +1789,20 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
     } else if (Has<F, kFeatXform>() && kind == kXform) {
       if (kStats) cnt.xform++;
       const u32x16 m = sld16(recs, off * 16u);  // inverse-model columns
+      if constexpr (kFlat) {
+        // the entry rule on the step's certificate box (words 4-9) with the world ray (flat programs nest
+        // no transform: o, inv are the world ray's) and T = this lane's tmax here
+        const float clo[3] = {uf(sw[4]), uf(sw[5]), uf(sw[6])}, chi[3] = {uf(sw[7]), uf(sw[8]), uf(sw[9])};
+        xfail = !FlatCertRule<BoxMath>(clo, chi, o.x, o.y, o.z, inv.x, inv.y, inv.z, tmin, tmax);
+#if RT2_EXP_TWICE & 16384
+        {
+          float ox2 = o.x;
+          asm volatile("" : "+v"(ox2));
+          const bool r2 = FlatCertRule<BoxMath>(clo, chi, ox2, o.y, o.z, inv.x, inv.y, inv.z, tmin, tmax);
+          asm volatile("" ::"v"((int)r2));
+        }
+#endif
+      }
       f3 no, nd;
       if (m[11] == kXformYAxis) {
         // a transform about y (compile.cpp YAxisPattern): the products of the +-0 entries col0.y,
@@ -1824,6 +1849,9 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
                                                        st.y - (off + (uint32_t)kXformRecords)) {
         pk_st3(xray, 0u, o);
         pk_st3(xray, 3u, d);
+        // (kFlat kernels keep the model-space ray, so this is every hit under the transform; a transform is
+        // entered once per trace, so the hit is this visit's)
+        if constexpr (kFlat) xunc = xfail;
       }
       cur_xf = st.w;
       if (cur_xf == kRefNone) {
@@ -1961,7 +1989,31 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   }
   h.t = tmax;
   h.prim = prim;
-  if constexpr (Has<F, kFeatXform>()) {
+  if constexpr (kFlat) {
+    // The certificate. No hit here is no hit there. A hit needs the world ray's reciprocal finite, and the
+    // winner's certificate (rt2_layout.h: the table has the shape of lind): under a transform, that its
+    // entry rule passed; in world space, the end rule on its box with T = its t.
+    bool u = false;
+    if (prim != kRefNone) {
+      const float4* ct = reinterpret_cast<const float4*>(P.flat_cert) + (prim & kOffsetMask);
+      const float4 c0 = ct[0], c1 = ct[1];
+      const float clo[3] = {c0.x, c0.y, c0.z}, chi[3] = {c1.x, c1.y, c1.z};
+      const bool end_ok = FlatCertRule<BoxMath>(clo, chi, wray.wo().x, wray.wo().y, wray.wo().z, winv.x, winv.y,
+                                                winv.z, tmin, tmax);
+#if RT2_EXP_TWICE & 16384
+      {
+        float ox2 = wray.wo().x;
+        asm volatile("" : "+v"(ox2));
+        const bool r2 = FlatCertRule<BoxMath>(clo, chi, ox2, wray.wo().y, wray.wo().z, winv.x, winv.y, winv.z, tmin, tmax);
+        asm volatile("" ::"v"((int)r2));
+      }
+#endif
+      u = !wfin || P.flat_mode == kFlatCertifyNothing || (bits(c0.w) == kFlatCertXform ? xunc : !end_ok);
+    }
+    *uncert = u;
+  }
+  // (kFlat kernels resolve every hit from the hit table)
+  if constexpr (Has<F, kFeatXform>() && !kFlat) {
     // (tab, wave-uniform: the hit is resolved from the hit table, whose record holds the transform)
     if (!tab) {
       if (prim != kRefNone && (prim >> 28) == kQuad) h.xf = N.word((prim & kOffsetMask) + 3u, 3);
@@ -2317,10 +2369,17 @@ constexpr uint32_t StageGroup() {
 // feature word, not a template parameter of its own: the kernels without it keep their names, by which
 // tools and tests pick them out of the ISA, and their source is the source it was.)
 constexpr uint32_t kFeatList = 0x80000000u;
+// kFeatFlat, likewise a bit of the feature word: the kernels that walk the launch's flat program
+// (rt2_layout.h "Flat program", RenderParams::flat_wide) and trace the BVH program `lin_wide` only for the
+// lanes the certificate leaves open. Instantiated for the Cornell box's product kernel (kFlatVariant), as
+// the kernel it is with its hit table staged: a launch without the table in LDS walks the BVH program.
+constexpr uint32_t kFeatFlat = 0x40000000u;
 template <uint32_t FL, int kMode, bool kStats>
-__global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~kFeatList), kMode, kStats>())) void render_kernel(const RenderParams P) {
-  constexpr uint32_t F = FL & ~kFeatList;
+__global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~(kFeatList | kFeatFlat)), kMode, kStats>())) void render_kernel(const RenderParams P) {
+  constexpr uint32_t F = FL & ~(kFeatList | kFeatFlat);
   constexpr bool kList = (FL & kFeatList) != 0u;
+  constexpr bool kFlat = (FL & kFeatFlat) != 0u;
+  static_assert(!kFlat || (kMode == kModeLinear && !kStats), "the flat walk: threaded product kernels only");
   constexpr bool kLds = kMode == kModeStackLds || kMode == kModeStackHybrid;
   constexpr uint32_t kGroup = StageGroup<F, kMode, kStats>();
   constexpr uint32_t kPlanes = kGroup ? 3u * (kGroup - 1u) : 1u;  // [slot][component] planes of 64 lanes
@@ -2530,7 +2589,8 @@ __global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~kFeatList), kMode, kStats>
         uint32_t mat;
         if constexpr (kMode == kModeLinear) {
           if constexpr (kHitTab) {
-            if (karg1<RT2_KOFF(hit_bytes)>() != 0u) {  // wave-uniform: the hit table is in LDS
+            // wave-uniform: the hit table is in LDS (kFlat: always, LaunchFrames gives such a kernel its table)
+            if (kFlat || karg1<RT2_KOFF(hit_bytes)>() != 0u) {
 #if RT2_EXP_TWICE & 1
               {
                 f3 ro2 = ro;
@@ -2641,6 +2701,31 @@ __global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~kFeatList), kMode, kStats>
         path.n = pk_ld(pk, kPkN);
         ro = pk_ld3(pk, kPkO);
         rd = pk_ld3(pk, kPkD);
+      } else if constexpr (kFlat) {
+        static_assert(!kFlat || (kXray && kHitTab), "the flat walk: a kernel that keeps the model-space ray and resolves from the hit table");
+        bool unc = false;
+        constexpr bool tab = true;
+        hit = trace_linear<F, kStats, true>(P, RegRay{ro, rd}, rtime, path, h, lp + 64u * kCandP, lp + 64u * kXrayP,
+                                            cnt, tab, &unc);
+        // the lanes the certificate leaves open trace the BVH program from scratch: it rewrites everything
+        // a trace leaves behind (the hit, the kept model-space ray); the other lanes are masked
+        const unsigned long long um = __ballot(unc);
+        if (um != 0ull) {  // wave-uniform, rare
+          // the flat walk's counters (rt2_layout.h StatsCounters), by atomics from here: this block runs in
+          // about 0.6 % of the Cornell box's wave-bounces, and wave totals carried to the kernel's end would
+          // be registers held through the path loop (this point is inside the lanes' depth branch, so they
+          // would be vector registers)
+          const bool lead = lane == __builtin_amdgcn_readfirstlane(lane);
+          if (lead) {
+            atomicAdd(P.stats + StatsCounters::kFlatUncertified, (unsigned long long)__popcll(um));
+            atomicAdd(P.stats + StatsCounters::kFlatWaveFallbacks, 1ull);
+          }
+          if (unc)
+            hit = trace_linear<F, kStats>(P, RegRay{ro, rd}, rtime, path, h, lp + 64u * kCandP, lp + 64u * kXrayP, cnt,
+                                          tab);
+          const unsigned long long hm = __ballot(hit);
+          if (lead) atomicAdd(P.stats + StatsCounters::kFlatFallbackHits, (unsigned long long)__popcll(hm));
+        }
       } else if constexpr (kMode == kModeLinear) {
         hit = trace_linear<F, kStats>(P, RegRay{ro, rd}, rtime, path, h, lp + 64u * kCandP,
                                       kXray ? lp + 64u * kXrayP : nullptr, cnt,
@@ -2986,11 +3071,19 @@ KernelFn PickList(bool stats) {
 }
 
 // list: the kernel over an active list (threaded traversal only; null for the other modes).
-KernelFn Kernel(int v, int mode, bool stats, bool list = false) {
+// flat: the kernel over a launch's flat program (kFlatVariant's threaded product kernel; null otherwise).
+constexpr int kFlatVariant = 0;  // the Cornell box
+KernelFn Kernel(int v, int mode, bool stats, bool list = false, bool flat = false) {
 #ifdef RT2_ONLY_VARIANT  // register-allocation experiments: one threaded product kernel only (not a usable build)
   (void)v, (void)mode, (void)stats, (void)list;
+  if (flat && RT2_ONLY_VARIANT == kFlatVariant)
+    return reinterpret_cast<KernelFn>(&render_kernel<kVariants[kFlatVariant] | kFeatFlat, kModeLinear, false>);
   return reinterpret_cast<KernelFn>(&render_kernel<kVariants[RT2_ONLY_VARIANT], kModeLinear, false>);
 #else
+  if (flat) {
+    if (v != kFlatVariant || mode != kModeLinear || stats || list) return nullptr;
+    return reinterpret_cast<KernelFn>(&render_kernel<kVariants[kFlatVariant] | kFeatFlat, kModeLinear, false>);
+  }
   if (list) {
     if (mode != kModeLinear) return nullptr;
     switch (v) {
@@ -3236,6 +3329,15 @@ int RenderMode(const RenderParams& p) {
   return p.lds_partial ? kModeStackHybrid : kModeStackLds;
 }
 
+// Whether a launch of this kernel can walk a flat program (render.hip kFeatFlat): the Cornell box's threaded
+// product kernel over the whole image. Counting launches, launches over an active list, the other feature
+// sets and the stack traversals keep the BVH program.
+bool RenderTakesHitTable(int variant, int mode, bool stats);
+bool RenderTakesFlat(int variant, int mode, bool stats, bool list) {
+  return variant == dev::kFlatVariant && mode == kModeLinear && !stats && !list &&
+         RenderTakesHitTable(variant, mode, stats);
+}
+
 bool RenderTakesHitTable(int variant, int mode, bool stats) {
   if (variant < 0 || variant >= dev::kNumVariants || mode != kModeLinear || stats) return false;
   switch (variant) {
@@ -3256,7 +3358,7 @@ size_t RenderLdsBytes(const RenderParams& p) {
 // Launch entry used by capi.cpp. grid = resident workgroups (persistent lanes).
 hipError_t LaunchRender(const RenderParams& p, int variant, bool stats, int grid, hipStream_t stream) {
   // a launch that carries an active list runs the list kernel (capi.cpp refuses one outside the threaded mode)
-  dev::KernelFn fn = dev::Kernel(variant, RenderMode(p), stats, p.active_list != nullptr);
+  dev::KernelFn fn = dev::Kernel(variant, RenderMode(p), stats, p.active_list != nullptr, p.flat_wide != nullptr);
   if (!fn) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(dev::kBlock), RenderLdsBytes(p), stream, p);
   return hipGetLastError();
@@ -3286,9 +3388,9 @@ hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsign
   return hipGetLastError();
 }
 
-int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes, bool list) {
+int RenderBlocksPerCU(int variant, int mode, bool stats, size_t lds_bytes, bool list, bool flat) {
   int n = 0;
-  dev::KernelFn fn = dev::Kernel(variant, mode, stats, list);
+  dev::KernelFn fn = dev::Kernel(variant, mode, stats, list, flat);
   if (!fn) return 1;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(fn), dev::kBlock,
                                                              lds_bytes);

@@ -221,6 +221,25 @@ constexpr uint32_t kRunLenMask = 0xFFu, kRunBoxFlag = 0x80000000u;
 static_assert(3 * kLinearMaxRun < 32, "a run's codes and their end bit fit one word");
 constexpr int kLinearMaxXformDepth = 8;  // deeper transform nesting uses the stack traversal
 
+// Flat program (CompiledScene::flat_wide, RenderParams::flat_wide; DESIGN.md §4 "Flat walk of small BVHs"):
+// the threaded program of a scene whose root BVH has at most kFlatBvhMaxLeaves leaves, all of them quads,
+// lists of quads or non-nested transforms of those, without its kBvh steps: the same leaf steps in the same
+// pre-order over the same record stream `lind` (whose BVH node records then lie after every leaf's, so
+// quads of neighbouring leaves are adjacent and share runs), in the wide layout only. A kernel that walks it
+// tests no node box; a per-lane certificate (boxaa.h FlatCertRule) proves that the reference's slab tests
+// would have culled nothing the lane's answer depends on, and the lanes it cannot certify trace the BVH
+// program again. Certificate boxes are bit copies of each leaf's parent BVH node's bounds:
+//   kXform step: words 4-9 of its wide entry (lo.xyz, hi.xyz) instead of the record's first words (the
+//     step loads its record itself)
+//   quads: the certificate table (CompiledScene::flat_cert, RenderParams::flat_cert), which has the shape
+//     of `lind`: at a quad record's offset (lo.xyz, flag bits) (hi.xyz, 0), flag = kFlatCertXform for a
+//     quad under a transform (no box: its transform's entry test decides)
+// 8 is the headline's leaf count, the only size with a wave-step measurement behind it.
+constexpr int kFlatBvhMaxLeaves = 8;
+constexpr uint32_t kFlatCertXform = 1u;
+// RenderParams::flat_mode: the flat kernel certifies as proven, or (RT2_FLAT_BVH=2) certifies no hit
+enum FlatMode : uint32_t { kFlatOff = 0, kFlatOn = 1, kFlatCertifyNothing = 2 };
+
 // kModeStackHybrid: the scene is too large for LDS, but its BVH node records (the prefix
 // [0, lds_nodes) of the record array) are staged in LDS; other records are read from global memory.
 enum TraversalMode : int { kModeStackGlobal = 0, kModeStackLds = 1, kModeLinear = 2, kModeStackHybrid = 3 };
@@ -239,6 +258,10 @@ struct StatsCounters {  // u64 slots written by the kernel
   // the box-level test of flagged MakeBox runs (boxaa.h): lanes tested, lanes certified; wave visits of
   // a flagged run, and those in which some lane fell back so the wave ran the six faces
   enum { kBoxTests = 24, kBoxCertified, kBoxWaveVisits, kBoxWaveRuns };
+  // the flat walk (kernels over RenderParams::flat_wide): lanes whose hit the certificate did not cover, and
+  // wave-bounces that traced the BVH program again for them, and the hits those wave-bounces ended with
+  // (wave totals, counted in every such launch; added from the fallback itself, which is rare)
+  enum { kFlatUncertified = 28, kFlatWaveFallbacks, kFlatFallbackHits };
 };
 constexpr int kStatsSlots = StatsCounters::kSlots;
 
@@ -332,6 +355,12 @@ struct RenderParams {
   // slot_of[local pixel]. Only the list kernels (render.hip kFeatList) read these two.
   const uint32_t* active_list;
   const uint32_t* slot_of;
+  // The flat program (above) of this launch, its certificate table and FlatMode; null / 0: the launch walks
+  // the BVH program `lin_wide`. Set only for the kernels that take it (render.hip kFeatFlat); those keep
+  // `lin_wide` for the lanes they cannot certify.
+  const void* flat_wide;
+  const void* flat_cert;
+  uint32_t flat_mode;
 };
 constexpr int kClockRing = 512;  // launch-clock pairs per tracer (drained at half)
 

@@ -158,6 +158,12 @@ struct CompiledScene {
   std::vector<uint32_t> lin_wide; // 16 words per step: the lin entry + the first 12 words of its record,
                                   // then one kProgramEnd entry
   std::vector<float> hit;         // hit table (rt2_layout.h HIT), as long as lind; empty: none
+  // Flat program (rt2_layout.h "Flat program"; empty / 0: the scene does not qualify, or RT2_FLAT_BVH=0):
+  // its wide steps and a kProgramEnd entry, the certificate table (as long as lind), the FlatMode
+  std::vector<uint32_t> flat_wide;
+  std::vector<float> flat_cert;
+  uint32_t flat_mode = 0;
+  int flat_steps = 0;
 };
 // accelerate_lists = false keeps every list a linear child loop (the reference's own order).
 bool CompileScene(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists = true);
