@@ -388,6 +388,56 @@ RT2_API int rt2_tracer_adaptive_check(rt2_tracer* tr, float threshold, int windo
 RT2_API int rt2_tracer_render_adaptive(rt2_tracer* tr, float threshold, int window, int min_frames, int max_frames,
                                        int check_every, rt2_adaptive* out);
 
+/* ---- Feature buffers and denoiser ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before.
+ * features: the scene's Hit (HitRecord) for the ray through each local pixel's centre, 16 floats per local
+ *   pixel in the row order of `accumulation`. With the words of rt2_camera_params, for the pixel at image
+ *   (x, y): pc = (pixel00 + (float)x * du) + (float)y * dv, origin = center (no defocus offset, whatever the
+ *   camera's defocus_angle), d = normalize(pc - center), time 0, interval (0.001, FLT_MAX), every operation
+ *   rounded on its own. Slots: 0 hit (0 / 1); 1 t; 2-4 point; 5-7 normal (facing against the ray); 8
+ *   front_face; 9 material index; 10-12 albedo; 13 dist = sqrt(dot(point - center, point - center)); 14-15 0.
+ *   Albedo: the material table's albedo (metal, lambertian), (1, 1, 1) (dielectric), Texture::Value at the
+ *   hit (texture, diffuse_light, isotropic). A miss: slot 0 = 0, albedo = the background, every other slot 0.
+ *   t is model-space under a transformed child (the reference's quirk); the filter uses dist and the point.
+ *   A ConstantMedium on the way draws from the path stream (tracer seed, pixel 0xFFFFFFF0, frame 0) from its
+ *   start, the same for every pixel: a medium's boundary in the feature image is the reference's
+ *   probabilistic hit, not a geometric surface. The buffer is cached on the device per (camera, size,
+ *   partition, seed); it works under set_partition on the local rows.
+ * denoise: an edge-avoiding a-trous wavelet filter (raytrace2_amd/csrc/denoise.h defines every operation)
+ *   over the tracer's mean image, guided by the features and weighted by the variance of the mean. Inputs,
+ *   exactly what the readbacks return: c = non_converted_pixels, v = ((sem_r^2 + sem_g^2) + sem_b^2) / 3 in
+ *   float32 from standard_error (adaptive sampling: both rest on each pixel's own n_p). Needs moments on,
+ *   FrameIdx() >= 2 and an unpartitioned one-GPU tracer (world 1, not joined). It launches queued frames and
+ *   synchronises; accumulation, moments, counts and FrameIdx() are unchanged. out_color: float3 per pixel;
+ *   out_variance: float per pixel, the filtered variance of the mean, or NULL.
+ * denoise_buffers: the same kernels over caller (host) buffers of any image: color float3, variance float,
+ *   features 16 floats per pixel, on `device`.
+ * A pixel whose colour or variance is not finite passes through unchanged and contributes to no other pixel.
+ * RT2_ERR_INVALID: features / denoise on a create_multi or joined tracer (gathering features is a
+ *   follow-up); denoise with moments off, fewer than 2 frames or a partition (world > 1); iterations outside
+ *   [1, 8], normal_power_log2 outside [0, 8], a sigma or eps_l that is not finite and > 0; a NULL out_color;
+ *   features on a scene only the threaded traversal can render (a stack deeper than the kernel's).
+ * The environment variable RT2_DENOISE_LDS=0 / 1 (read at every call) takes the small steps' LDS tiles off /
+ * on (same results; tools/denoise_cost.py measures both). */
+typedef struct {
+  int iterations;         /* 1..8, default 5: pass i has step 1 << i */
+  int normal_power_log2;  /* 0..8, default 7: max(0, dot(n_p, n_q)) squared this many times */
+  float sigma_l;          /* default 1: luminance tolerance in standard errors of the mean */
+  float sigma_p;          /* default 0.01: plane-distance tolerance as a fraction of the hit's distance */
+  float sigma_a;          /* default 0.1: albedo tolerance */
+  float eps_l;            /* default 1e-3: luminance tolerance floor */
+} rt2_denoise_params;     /* NULL = defaults */
+RT2_API void rt2_denoise_defaults(rt2_denoise_params* out);
+RT2_API int rt2_tracer_features(rt2_tracer* tr, float* out); /* 16 floats per local pixel */
+RT2_API int rt2_tracer_denoise(rt2_tracer* tr, const rt2_denoise_params* p, float* out_color,
+                               float* out_variance /* may be NULL */);
+RT2_API int rt2_denoise_buffers(int device, int width, int height, const float* color, const float* variance,
+                                const float* features, const rt2_denoise_params* p, float* out_color,
+                                float* out_variance /* may be NULL */);
+/* GPU time (HIP events on the tracer's stream) of the tracer's last feature pass and of the kernels of its
+ * last denoise call, in ms; -1: none yet. */
+RT2_API int rt2_tracer_denoise_times(rt2_tracer* tr, double* features_ms, double* denoise_ms);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -260,6 +260,29 @@ class RayTracer {
     return a;
   }
 
+  // Feature buffers and denoiser (rt2.h "Feature buffers and denoiser"). Features: the first-hit record of
+  // the ray through each local pixel's centre, 16 floats per pixel. Denoise: the variance-guided a-trous
+  // filter over the mean image (needs EnableMoments, FrameIdx() >= 2, one unpartitioned GPU); params null:
+  // the defaults (DenoiseDefaults); variance: receives the filtered variance of the mean when not null.
+  static rt2_denoise_params DenoiseDefaults() {
+    rt2_denoise_params p{};
+    rt2_denoise_defaults(&p);
+    return p;
+  }
+  [[nodiscard]] std::vector<float> Features() {
+    Sync();
+    std::vector<float> out((size_t)dims_.x * LocalRows() * 16);
+    Check(rt2_tracer_features(t_.get(), out.data()));
+    return out;
+  }
+  [[nodiscard]] std::vector<vec3> Denoise(const rt2_denoise_params* params = nullptr, std::vector<float>* variance = nullptr) {
+    Sync();
+    std::vector<vec3> out((size_t)dims_.x * LocalRows());
+    if (variance) variance->assign(out.size(), 0.0f);
+    Check(rt2_tracer_denoise(t_.get(), params, reinterpret_cast<float*>(out.data()), variance ? variance->data() : nullptr));
+    return out;
+  }
+
   rt2_tracer* handle() const { return t_.get(); }
   [[nodiscard]] int NumGpus() const { return rt2_tracer_n_gpus(t_.get()); }
 

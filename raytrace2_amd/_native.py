@@ -106,6 +106,15 @@ class Adaptive(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class DenoiseParams(ctypes.Structure):
+    """rt2_denoise_params."""
+    _fields_ = [("iterations", ctypes.c_int), ("normal_power_log2", ctypes.c_int), ("sigma_l", ctypes.c_float),
+                ("sigma_p", ctypes.c_float), ("sigma_a", ctypes.c_float), ("eps_l", ctypes.c_float)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Every RT2_API function name declared in include/rt2.h."""
     txt = open(header).read()
@@ -206,6 +215,11 @@ def _load():
         "rt2_tracer_sample_counts": (i32, [vp, ctypes.POINTER(ctypes.c_uint32)]),
         "rt2_tracer_adaptive_check": (i32, [vp, f32, i32, ctypes.POINTER(Adaptive)]),
         "rt2_tracer_render_adaptive": (i32, [vp, f32, i32, i32, i32, i32, ctypes.POINTER(Adaptive)]),
+        "rt2_denoise_defaults": (None, [ctypes.POINTER(DenoiseParams)]),
+        "rt2_tracer_features": (i32, [vp, fp]),
+        "rt2_tracer_denoise": (i32, [vp, ctypes.POINTER(DenoiseParams), fp, fp]),
+        "rt2_denoise_buffers": (i32, [i32, i32, i32, fp, fp, fp, ctypes.POINTER(DenoiseParams), fp, fp]),
+        "rt2_tracer_denoise_times": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

@@ -19,6 +19,7 @@
 
 #include "../../include/rt2.h"
 #include "adaptive.h"
+#include "denoise.h"
 #include "noise.h"
 #include "scene.h"
 
@@ -39,6 +40,12 @@ uint32_t NoiseBlocks(uint32_t npix);
 hipError_t LaunchNoise(const float* accum, const float* moment2, const uint32_t* counts, float* sem,
                        NoisePartial* partials, uint32_t npix, int64_t n_frames, float threshold, hipStream_t stream);
 hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsigned long long* d_out, hipStream_t stream);
+hipError_t LaunchFeatures(const RenderParams& p, float* out, hipStream_t stream);
+size_t DenoiseScratchBytes(size_t npix);
+hipError_t LaunchDenoiseInputs(const float* accum, const float* moment2, const uint32_t* counts, void* scratch,
+                               uint32_t npix, int64_t n_frames, hipStream_t stream);
+hipError_t LaunchDenoise(void* scratch, const float* features, int width, int height, const DenoiseParams& k, bool lds,
+                         hipStream_t stream);
 int RenderMode(const RenderParams& p);
 int RenderBlockSize();
 int RenderVariant(uint32_t features);
@@ -133,6 +140,16 @@ struct rt2_tracer {
   void* d_ad_scratch = nullptr;  // wg counts (uint2), wg offsets, classify partials, totals
   size_t ad_scratch_bytes = 0;
   uint32_t n_active = 0;
+  // feature buffers and denoiser (rt2.h "Feature buffers and denoiser"), allocated at the first call: the
+  // cached feature records (16 floats per local pixel) with the launch values they were traced under, the
+  // filter's scratch planes, and the GPU times of the last feature pass and the last denoise (-1: none)
+  float* d_features = nullptr;
+  bool features_valid = false;
+  CameraParams features_cam;
+  uint64_t features_seed = 0;
+  void* d_dn_scratch = nullptr;
+  size_t dn_scratch_bytes = 0;
+  double features_ms = -1.0, denoise_ms = -1.0;
   uint32_t* d_work = nullptr;  // one work counter per launch slot (words 0 and 16)
   unsigned long long* d_stats = nullptr;
   bool stats_on = false;
@@ -305,6 +322,12 @@ void FreeFrame(rt2_tracer* t) {
   (void)hipFree(t->d_list);
   (void)hipFree(t->d_slot_of);
   (void)hipFree(t->d_ad_scratch);
+  (void)hipFree(t->d_features);
+  (void)hipFree(t->d_dn_scratch);
+  t->d_features = nullptr;
+  t->features_valid = false;
+  t->d_dn_scratch = nullptr;
+  t->dn_scratch_bytes = 0;
   t->d_counts = nullptr;
   t->d_active = nullptr;
   t->d_over = nullptr;
@@ -327,7 +350,8 @@ size_t DeviceBytes(const rt2_tracer* t) {
   const size_t n = (size_t)t->width * (size_t)AllocRows(t);
   size_t b = t->scene_bytes + (t->d_accum ? n * 12 : 0) + (t->d_pixels ? n * 4 : 0) + (t->d_ray_counts ? n * 4 : 0) +
              (t->d_moment2 ? n * 12 : 0) + t->noise_blocks * sizeof(NoisePartial) +
-             (t->d_counts ? n * (4 + 1 + 1 + 4 + 4) + 64 * 4 : 0) + t->ad_scratch_bytes;
+             (t->d_counts ? n * (4 + 1 + 1 + 4 + 4) + 64 * 4 : 0) + t->ad_scratch_bytes +
+             (t->d_features ? n * kDenoiseFeatureFloats * sizeof(float) : 0) + t->dn_scratch_bytes;
   for (const auto& sl : t->slots) b += sl.samples_bytes + sl.chunks_bytes;
   if (t->d_image) b += t->stacks_bytes + t->image_pixels * (12 + 12 + 4);
   return b;
@@ -1968,6 +1992,220 @@ int rt2_tracer_render_adaptive(rt2_tracer* t, float threshold, int window, int m
     if ((rc = rt2_tracer_adaptive_check(t, threshold, window, out)) != RT2_OK) return rc;
     if (out->active == 0) return RT2_OK;
   }
+  return RT2_OK;
+}
+
+// ---- feature buffers and denoiser (rt2.h "Feature buffers and denoiser") ----
+void rt2_denoise_defaults(rt2_denoise_params* out) {
+  if (!out) return;
+  const DenoiseParams d = DenoiseDefaults();
+  out->iterations = d.iterations;
+  out->normal_power_log2 = d.normal_power_log2;
+  out->sigma_l = d.sigma_l;
+  out->sigma_p = d.sigma_p;
+  out->sigma_a = d.sigma_a;
+  out->eps_l = d.eps_l;
+}
+
+static int DenoiseParamsOf(const rt2_denoise_params* p, DenoiseParams* k) {
+  *k = DenoiseDefaults();
+  if (p) *k = DenoiseParams{p->iterations, p->normal_power_log2, p->sigma_l, p->sigma_p, p->sigma_a, p->eps_l};
+  if (!DenoiseParamsValid(*k))
+    return Fail(RT2_ERR_INVALID, "denoise: need 1 <= iterations <= 8, 0 <= normal_power_log2 <= 8, and sigma_l, sigma_p, "
+                                 "sigma_a, eps_l finite and > 0");
+  return RT2_OK;
+}
+
+// The small steps' LDS tiles (denoise.hip): on unless RT2_DENOISE_LDS=0 (measured: DESIGN.md §6e).
+static bool DenoiseLds() {
+  const char* e = getenv("RT2_DENOISE_LDS");
+  return !(e && e[0] == '0');
+}
+
+// GPU time between two events recorded on the tracer's stream, which the caller has synchronised.
+static double EventMs(rt2_tracer* t, hipEvent_t a, hipEvent_t b) {
+  float ms = -1.0f;
+  if (hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = -1.0f;
+  t->event_pool.push_back(a);
+  t->event_pool.push_back(b);
+  return (double)ms;
+}
+
+// The tracer's feature records on its device, traced again when the camera, the seed, the size or the
+// partition have changed since (Realloc drops the buffer). e0 / e1: events around the pass, or null.
+static int EnsureFeatures(rt2_tracer* t, bool* launched, hipEvent_t e0, hipEvent_t e1) {
+  *launched = false;
+  if (!t->stack_ok)
+    return Fail(RT2_ERR_INVALID, "features: the scene needs a traversal stack of " + std::to_string(t->max_stack) +
+                                     " entries (kernel has " + std::to_string(kTraversalStack) + ")");
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  const CameraParams cam = t->camera.Params();
+  if (n == 0) return RT2_OK;
+  if (t->d_features && t->features_valid && t->features_seed == t->seed &&
+      memcmp(&t->features_cam, &cam, sizeof(cam)) == 0)
+    return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  if (!t->d_features) {
+    const size_t rows = (size_t)t->width * (size_t)AllocRows(t);
+    HIP_TRY(hipMalloc(&t->d_features, rows * kDenoiseFeatureFloats * sizeof(float)));
+    NoteDeviceBytes(t);
+  }
+  RenderParams p;
+  memset(&p, 0, sizeof(p));
+  p.nodes = t->d_nodes;
+  p.materials = t->d_materials;
+  p.textures = t->d_textures;
+  p.perlin_vec = t->d_perlin_vec;
+  p.perlin_perm = t->d_perlin_perm;
+  p.root = t->root;
+  memcpy(p.background, t->background, sizeof(p.background));
+  p.cam = cam;
+  p.width = t->width;
+  p.height = t->height;
+  p.local_rows = t->local_rows;
+  p.band_h = t->band_h > 0 ? t->band_h : t->height;
+  p.rank = t->rank;
+  p.world = t->world;
+  p.seed_lo = (uint32_t)t->seed;
+  p.seed_hi = (uint32_t)(t->seed >> 32);
+  for (uint32_t r = 0; r < 10; r++) {
+    p.philox_keys[2 * r] = p.seed_lo + r * 0x9E3779B9u;
+    p.philox_keys[2 * r + 1] = p.seed_hi + r * 0xBB67AE85u;
+  }
+  p.stack_depth = t->max_stack;
+  p.local_pixels = (uint32_t)n;
+  if (e0) HIP_TRY(hipEventRecord(e0, t->stream));
+  HIP_TRY(LaunchFeatures(p, t->d_features, t->stream));
+  if (e1) HIP_TRY(hipEventRecord(e1, t->stream));
+  t->features_valid = true;
+  t->features_cam = cam;
+  t->features_seed = t->seed;
+  *launched = true;
+  return RT2_OK;
+}
+
+static int FeaturesTimed(rt2_tracer* t) {
+  hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
+  if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
+  bool launched = false;
+  int rc = EnsureFeatures(t, &launched, e0, e1);
+  if (rc == RT2_OK && launched) {
+    hipError_t e = hipStreamSynchronize(t->stream);
+    t->host_waits++;
+    if (e != hipSuccess) rc = HipFail(e, "feature pass");
+    if (rc == RT2_OK) {
+      t->features_ms = EventMs(t, e0, e1);
+      return RT2_OK;
+    }
+  }
+  t->event_pool.push_back(e0);
+  t->event_pool.push_back(e1);
+  return rc;
+}
+
+int rt2_tracer_features(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || t->comm)
+    return Fail(RT2_ERR_INVALID, "features: not on a multi-GPU or joined tracer (a set_partition tracer works)");
+  int rc = FeaturesTimed(t);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n) {
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipMemcpyAsync(out, t->d_features, n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    t->host_waits++;
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  return RT2_OK;
+}
+
+int rt2_tracer_denoise(rt2_tracer* t, const rt2_denoise_params* params, float* out_color, float* out_variance) {
+  if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || t->comm || t->world != 1)
+    return Fail(RT2_ERR_INVALID, "denoise: needs an unpartitioned one-GPU tracer (world 1, not joined)");
+  DenoiseParams k;
+  int rc = DenoiseParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "denoise: moments not enabled (rt2_tracer_enable_moments)");
+  if ((rc = Sync(t)) != RT2_OK) return rc;
+  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "denoise needs at least 2 frames");
+  if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  const size_t need = DenoiseScratchBytes(n);
+  if (need > t->dn_scratch_bytes) {
+    (void)hipFree(t->d_dn_scratch);
+    t->d_dn_scratch = nullptr;
+    t->dn_scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&t->d_dn_scratch, need));
+    t->dn_scratch_bytes = need;
+    NoteDeviceBytes(t);
+  }
+  hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
+  if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
+  float* d_color = static_cast<float*>(t->d_dn_scratch);
+  hipError_t e = hipEventRecord(e0, t->stream);
+  if (e == hipSuccess)
+    e = LaunchDenoiseInputs(t->d_accum, t->d_moment2, t->adaptive_on ? t->d_counts : nullptr, t->d_dn_scratch, (uint32_t)n,
+                            t->frame_idx, t->stream);
+  if (e == hipSuccess) e = LaunchDenoise(t->d_dn_scratch, t->d_features, t->width, t->local_rows, k, DenoiseLds(), t->stream);
+  if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) {
+    t->event_pool.push_back(e0);
+    t->event_pool.push_back(e1);
+    return HipFail(e, "denoise");
+  }
+  t->denoise_ms = EventMs(t, e0, e1);
+  return RT2_OK;
+}
+
+int rt2_tracer_denoise_times(rt2_tracer* t, double* features_ms, double* denoise_ms) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "denoise_times: not on a multi-GPU tracer");
+  if (features_ms) *features_ms = t->features_ms;
+  if (denoise_ms) *denoise_ms = t->denoise_ms;
+  return RT2_OK;
+}
+
+int rt2_denoise_buffers(int device, int width, int height, const float* color, const float* variance,
+                        const float* features, const rt2_denoise_params* params, float* out_color, float* out_variance) {
+  if (!color || !variance || !features || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
+    return Fail(RT2_ERR_INVALID, "denoise_buffers: need width, height > 0 and width * height below 2^26");
+  DenoiseParams k;
+  int rc = DenoiseParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  const size_t n = (size_t)width * (size_t)height;
+  void* scratch = nullptr;
+  float* d_feat = nullptr;
+  hipStream_t stream = nullptr;
+  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipMalloc(&scratch, DenoiseScratchBytes(n));
+  if (e == hipSuccess) e = hipMalloc(&d_feat, n * kDenoiseFeatureFloats * sizeof(float));
+  float* d_color = static_cast<float*>(scratch);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_color, color, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_color + 3 * n, variance, n * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_feat, features, n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = LaunchDenoise(scratch, d_feat, width, height, k, DenoiseLds(), stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  (void)hipFree(d_feat);
+  (void)hipFree(scratch);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (e != hipSuccess) return HipFail(e, "denoise_buffers");
   return RT2_OK;
 }
 

@@ -5,6 +5,7 @@
 //
 //   rt2_headless <scene.json> <out.png> [--settings settings.json] [--samples N] [--size WxH] [--gpus N]
 //                [--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]]
+//                [--denoise [--denoise-iterations N]]
 //
 // Without --settings the reference's Settings.hpp defaults apply (num_samples 1, max_depth 50);
 // --samples / --size override num_samples and the output dims (App.cpp:115-124: scene dims, else
@@ -15,6 +16,9 @@
 // --adaptive THRESHOLD renders with adaptive sampling (RenderAdaptive with moments on, one check per
 // stratum sweep, --window N columns, default 1): pixels whose noise estimate is at most THRESHOLD retire,
 // at most N = --max-samples frames (default: num_samples); it prints "frames <f> active <a> samples <s>".
+// --denoise turns moments on and writes the denoised image (RayTracer::Denoise: the variance-guided a-trous
+// filter at its defaults, --denoise-iterations N passes) where it wrote the plain one; it composes with
+// --noise-target and --adaptive and needs at least 2 frames and one GPU.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -26,7 +30,8 @@
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene.json> <out.png> [--settings f] [--samples N] [--size WxH] [--gpus N] "
-                         "[--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]]\n", argv[0]);
+                         "[--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]] "
+                         "[--denoise [--denoise-iterations N]]\n", argv[0]);
     return 2;
   }
   const std::string scene_path = argv[1], out_path = argv[2];
@@ -38,9 +43,23 @@ int main(int argc, char** argv) {
   long max_samples = -1;
   float adaptive = -1.f;  // >= 0: adaptive sampling with this threshold
   int window = 1;
+  bool denoise = false;
+  int denoise_iterations = 0;  // 0: the default
   try {
-    for (int i = 3; i + 1 < argc; i += 2) {
-      if (!std::strcmp(argv[i], "--settings")) {
+    for (int i = 3; i < argc; i += 2) {
+      if (!std::strcmp(argv[i], "--denoise")) {  // a flag: no value follows
+        denoise = true;
+        i -= 1;
+        continue;
+      }
+      if (i + 1 >= argc) break;
+      if (!std::strcmp(argv[i], "--denoise-iterations")) {
+        denoise_iterations = std::atoi(argv[i + 1]);
+        if (denoise_iterations < 1 || denoise_iterations > 8) {
+          std::fprintf(stderr, "--denoise-iterations needs an integer in [1, 8]\n");
+          return 2;
+        }
+      } else if (!std::strcmp(argv[i], "--settings")) {
         settings = rt2::serialize::LoadAppSettings(argv[i + 1]);
       } else if (!std::strcmp(argv[i], "--samples")) {
         samples = std::atol(argv[i + 1]);
@@ -90,7 +109,7 @@ int main(int argc, char** argv) {
     scene.cam.SetSamplesPerPixel((int)settings.num_samples);
     tracer.camera = &scene.cam;
     tracer.OnResize(dims);
-    if (until || adapt) tracer.EnableMoments();
+    if (until || adapt || denoise) tracer.EnableMoments();
     if (adapt) tracer.EnableAdaptive();
 
     const auto t0 = std::chrono::steady_clock::now();
@@ -104,7 +123,9 @@ int main(int argc, char** argv) {
     } else {
       for (size_t i = 0; i < settings.num_samples; i++) tracer.Update(scene);
     }
-    const auto pixels = tracer.NonConvertedPixels();  // runs the queued frames
+    rt2_denoise_params dp = rt2::RayTracer::DenoiseDefaults();
+    if (denoise_iterations > 0) dp.iterations = denoise_iterations;
+    const auto pixels = denoise ? tracer.Denoise(&dp) : tracer.NonConvertedPixels();  // runs the queued frames
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     rt2::util::WriteImage(pixels, tracer.Dims().x, tracer.Dims().y, out_path);
 

@@ -2027,8 +2027,10 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
 }
 
 // The closest hit's record in world space (what the reference's rec holds after the chain of
-// TransformedHittable::Hit returns): point, normal, front_face, material.
-template <uint32_t F, int kMode>
+// TransformedHittable::Hit returns): point, normal, front_face, material. kMediumNormal (the feature pass): a
+// medium's (1, 0, 0) goes through the enclosing transforms too, as the reference's record has it; the render
+// kernels never read it.
+template <uint32_t F, int kMode, bool kMediumNormal = false>
 __device__ __forceinline__ void resolve_hit(const Nodes<kMode>& N, const HitRef& h, f3 wo, f3 wd, float time, f3& p,
                                             f3& n, bool& front, uint32_t& mat, const lds_u32* xray = nullptr,
                                             bool flat = false) {
@@ -2089,7 +2091,7 @@ __device__ __forceinline__ void resolve_hit(const Nodes<kMode>& N, const HitRef&
                (m0.z * p.x + m1.z * p.y) + (m2.z * p.z + m3.z));
       }
       // (a medium's hit normal is never read: Isotropic::Scatter ignores it, Material.cpp:76-83)
-      if (!(Has<F, kFeatMedium>() && kind == kMedium) && !wnormal) {
+      if ((kMediumNormal || !(Has<F, kFeatMedium>() && kind == kMedium)) && !wnormal) {
         const float4 c0 = N[xo], c2 = N[xo + 2];
         n = normalize(mk(c0.x * n.x + c0.y * n.y + c0.z * n.z, c1.x * n.x + c1.y * n.y + c1.z * n.z,
                          c2.x * n.x + c2.y * n.y + c2.z * n.z));
@@ -3107,6 +3109,76 @@ KernelFn Kernel(int v, int mode, bool stats, bool list = false, bool flat = fals
 }
 
 // ------------------------------------------------------------------------------------------
+// Feature buffers (rt2.h "Feature buffers and denoiser"): the scene's Hit for the ray through each local
+// pixel's centre, one thread per local pixel, one launch per camera, size or partition change (not a hot
+// path: one instantiation, every feature compiled in, the stack traversal over the node array in global
+// memory, which covers every scene the stack traversal covers).
+//   pc = (pixel00 + ((float)x * du)) + ((float)y * dv)   camera_ray's expression with a zero sub-pixel offset
+//   o = center (no defocus offset), d = normalize(pc - center), time 0, interval (0.001, FLT_MAX)
+// A ConstantMedium on the way draws from the path stream (seed, pixel 0xFFFFFFF0, frame 0) from its start,
+// the same for every pixel (the stream oracle_scene_hit opens): a medium's boundary in the feature image
+// is the reference's probabilistic hit, not a geometric surface.
+// Record, 16 floats: hit, t, point, normal (facing against the ray), front_face, material, albedo, dist =
+// |point - center|, 0, 0. Albedo: the material's albedo (metal, lambertian), (1, 1, 1) (dielectric),
+// tex_value at the hit (texture, diffuse_light, isotropic). A miss: hit 0, albedo = the background, every
+// other slot 0. RenderParams first: the path stream reads its seed from the argument segment (seed_args).
+__global__ __launch_bounds__(kBlock) void features_kernel(const RenderParams P, float4* __restrict__ out) {
+  constexpr uint32_t F = kFeatAll;
+  const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;  // local pixel
+  const uint32_t width = (uint32_t)P.width;
+  if (i >= width * (uint32_t)P.local_rows) return;
+  uint32_t* stk = reinterpret_cast<uint32_t*>(s_dyn) + threadIdx.x;
+  // local row -> global row (rt2_layout.h BandRank: the rank's band of period r / band_h)
+  const uint32_t lr = i / width, x = i - lr * width;
+  const uint32_t bh = (uint32_t)P.band_h, world = (uint32_t)P.world;
+  const uint32_t period = lr / bh;
+  const uint32_t phase = ((uint32_t)P.rank + world - period % world) % world;
+  const uint32_t y = (period * world + phase) * bh + lr % bh;
+  const CameraParams& C = P.cam;
+  const f3 p00 = mk(C.pixel00[0], C.pixel00[1], C.pixel00[2]);
+  const f3 du = mk(C.du[0], C.du[1], C.du[2]), dv = mk(C.dv[0], C.dv[1], C.dv[2]);
+  const f3 c = mk(C.center[0], C.center[1], C.center[2]);
+  const f3 pc = (p00 + ((float)x * du)) + ((float)y * dv);
+  const f3 d = normalize(pc - c);
+  PathT<false> path;
+  path.rb = nullptr;
+  path.pix = 0xFFFFFFF0u;
+  path.sij = 0;
+  path.r0 = path.r1 = path.r2 = path.r3 = 0;
+  path.start(0);
+  const Nodes<kModeStackGlobal> N{reinterpret_cast<const float4*>(P.nodes), 0u};
+  HitRef h{0.0f, kRefNone, kRefNone};
+  Counters cnt = {};
+  bool overflow = false;
+  const bool hit = trace_stack<F, kModeStackGlobal, false>(P, N, c, d, 0.0f, path, h, stk, cnt, overflow);
+  float4* o = out + 4ull * i;
+  if (!hit) {
+    o[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    o[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    o[2] = make_float4(0.0f, 0.0f, P.background[0], P.background[1]);
+    o[3] = make_float4(P.background[2], 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  f3 hp, hn;
+  bool front;
+  uint32_t mat;
+  resolve_hit<F, kModeStackGlobal, true>(N, h, c, d, 0.0f, hp, hn, front, mat);
+  const ShadeArgs S{reinterpret_cast<const float4*>(P.materials), reinterpret_cast<const float4*>(P.textures),
+                    reinterpret_cast<const float4*>(P.perlin_vec), P.perlin_perm};
+  const float4 m0 = S.materials[2 * mat], m1 = S.materials[2 * mat + 1];
+  const uint32_t type = bits(m0.x);
+  f3 alb = mk(m0.y, m0.z, m0.w);
+  if (type == kMatDielectric) alb = mk(1.0f, 1.0f, 1.0f);
+  if (type == kMatTexture || type == kMatDiffuseLight || type == kMatIsotropic) alb = tex_value<F>(S, bits(m1.z), hp);
+  const f3 dp = hp - c;
+  const float dist = sqrtf(dot(dp, dp));
+  o[0] = make_float4(1.0f, h.t, hp.x, hp.y);
+  o[1] = make_float4(hp.z, hn.x, hn.y, hn.z);
+  o[2] = make_float4(front ? 1.0f : 0.0f, (float)mat, alb.x, alb.y);
+  o[3] = make_float4(alb.z, dist, 0.0f, 0.0f);
+}
+
+// ------------------------------------------------------------------------------------------
 // Self-tests of the kernel's exact shortcuts on random inputs (rt2_selftest):
 //   which 0: div_by_inv(a, b, fl(1/b)) == a / b for |b| > 1e-8, |a / b| >= 1e-3 (accepted quad t)
 //   which 3: the same for any quotient with 2^-100 <= |a| < 2^21 (medium box boundaries, any t)
@@ -3380,6 +3452,16 @@ hipError_t LaunchAccumulate(const float* samples, float* accum, float* moment2, 
   auto* fn = moment2 ? dev::accumulate_kernel<true> : dev::accumulate_kernel<false>;
   hipLaunchKernelGGL(fn, dim3((npix + 255u) / 256u), dim3(256), 0, stream, samples, accum, moment2,
                      reinterpret_cast<uint32_t*>(pixels), npix, n_frames, frame_idx);
+  return hipGetLastError();
+}
+
+// The feature pass over p's local pixels into out (16 floats per local pixel). p: the scene tables, root,
+// background, camera, image and partition, seed and stack_depth of a render launch.
+hipError_t LaunchFeatures(const RenderParams& p, float* out, hipStream_t stream) {
+  const uint32_t npix = (uint32_t)p.width * (uint32_t)p.local_rows;
+  if (npix == 0) return hipSuccess;
+  hipLaunchKernelGGL(dev::features_kernel, dim3((npix + (uint32_t)dev::kBlock - 1u) / (uint32_t)dev::kBlock), dim3(dev::kBlock),
+                     (size_t)p.stack_depth * dev::kBlock * 4, stream, p, reinterpret_cast<float4*>(out));
   return hipGetLastError();
 }
 

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._native import AppSettings as _AppSettings
-from ._native import UNIQUE_ID_BYTES, Adaptive, CameraDesc, Noise, SceneInfo, Stats, check, lib
+from ._native import UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Noise, SceneInfo, Stats, check, lib
 
 DEFAULT_SEED = 0x5EED2024
 
@@ -194,6 +194,41 @@ def comm_unique_id() -> bytes:
     buf = (ctypes.c_uint8 * UNIQUE_ID_BYTES)()
     check(lib.rt2_comm_unique_id(buf, UNIQUE_ID_BYTES))
     return bytes(buf)
+
+
+def denoise_defaults() -> dict:
+    """rt2_denoise_defaults as a dict."""
+    p = DenoiseParams()
+    lib.rt2_denoise_defaults(ctypes.byref(p))
+    return p.as_dict()
+
+
+def _denoise_params(params: dict):
+    """A rt2_denoise_params pointer for the keyword arguments (None = NULL: the defaults)."""
+    if not params:
+        return None
+    p = DenoiseParams()
+    lib.rt2_denoise_defaults(ctypes.byref(p))
+    for k, v in params.items():
+        if k not in dict(DenoiseParams._fields_):
+            raise TypeError(f"denoise: unknown parameter {k!r}")
+        setattr(p, k, int(v) if k in ("iterations", "normal_power_log2") else float(v))
+    return ctypes.byref(p)
+
+
+def denoise_buffers(color, variance, features, device: int = 0, **params):
+    """rt2_denoise_buffers: the tracer's filter over caller buffers, color (H, W, 3), variance (H, W),
+    features (H, W, 16) float32. Returns (color', variance')."""
+    color = np.ascontiguousarray(color, np.float32)
+    variance = np.ascontiguousarray(variance, np.float32)
+    features = np.ascontiguousarray(features, np.float32)
+    h, w = variance.shape
+    if color.shape != (h, w, 3) or features.shape != (h, w, 16):
+        raise ValueError("denoise_buffers: need color (H, W, 3), variance (H, W), features (H, W, 16)")
+    out, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+    check(lib.rt2_denoise_buffers(int(device), w, h, _fp(color), _fp(variance), _fp(features), _denoise_params(params),
+                                  _fp(out), _fp(var)))
+    return out, var
 
 
 class RayTracer:
@@ -456,6 +491,34 @@ class RayTracer:
         check(lib.rt2_tracer_render_adaptive(self._h, float(threshold), int(window), int(min_frames),
                                              int(max_frames), int(check_every), ctypes.byref(a)))
         return a.as_dict()
+
+    # -- feature buffers and denoiser (rt2.h "Feature buffers and denoiser") -------------------
+    def features(self) -> np.ndarray:
+        """The first-hit record of the ray through each local pixel's centre, (rows, W, 16) float32: hit, t,
+        point, normal, front_face, material, albedo, dist, 0, 0 (cached on the device per camera)."""
+        self._push_camera()
+        w, _ = self.Dims()
+        out = np.zeros((self.local_rows(), w, 16), np.float32)
+        check(lib.rt2_tracer_features(self._h, _fp(out)))
+        return out
+
+    def denoise(self, variance: bool = False, **params):
+        """The variance-guided a-trous filter over the mean image (needs enable_moments, FrameIdx() >= 2, one
+        unpartitioned GPU): (H, W, 3) float32, with variance=True also the filtered variance of the mean
+        (H, W). params: the fields of rt2_denoise_params that differ from denoise_defaults()."""
+        self._push_camera()
+        w, _ = self.Dims()
+        rows = max(self.local_rows(), 0)
+        out = np.zeros((rows, w, 3), np.float32)
+        var = np.zeros((rows, w), np.float32) if variance else None
+        check(lib.rt2_tracer_denoise(self._h, _denoise_params(params), _fp(out), _fp(var) if variance else None))
+        return (out, var) if variance else out
+
+    def denoise_times(self) -> dict:
+        """GPU ms of the last feature pass and of the last denoise call's kernels (-1: none yet)."""
+        f, d = ctypes.c_double(-1.0), ctypes.c_double(-1.0)
+        check(lib.rt2_tracer_denoise_times(self._h, ctypes.byref(f), ctypes.byref(d)))
+        return {"features_ms": f.value, "denoise_ms": d.value}
 
     def enable_stats(self, on: bool = True) -> None:
         check(lib.rt2_tracer_enable_stats(self._h, 1 if on else 0))
