@@ -2,7 +2,7 @@
 
 Only tests/, ``__graft_entry__.smoke()`` and bench.py's ``cpu_baseline`` leg may import this
 module, and only as the checker or the timed CPU baseline — never as the product path.
-Parity status: see the header of rt_oracle.cpp (partially pinned).
+Parity status: see the header of rt_oracle.cpp (pinned to the compiled reference, oracle/ref.py).
 """
 from __future__ import annotations
 
@@ -53,6 +53,7 @@ def lib():
         L.oracle_scene_materials.argtypes = [vp, fp, i32]
         L.oracle_scene_textures.argtypes = [vp, fp, i32]
         L.oracle_scene_perlin.argtypes = [vp, i32, fp, ctypes.POINTER(ctypes.c_int)]
+        L.oracle_texture_value.argtypes = [vp, i32, fp, i32, fp]
         L.oracle_camera_params.argtypes = [vp, i32, i32, i32, fp]
         L.oracle_scene_set_camera.argtypes = [vp, fp]
         L.oracle_scene_set_camera.restype = None
@@ -120,6 +121,14 @@ class OracleScene:
         if pc < 0:
             raise ValueError("not a noise texture")
         return vec[:pc].copy(), perm[:3 * pc].reshape(3, pc).copy()
+
+    def texture_value(self, tex: int, points) -> np.ndarray:
+        """Texture `tex`'s colour (Texture.cpp:7-22) at the given points, (n, 3) float32."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        out = np.zeros_like(p)
+        if lib().oracle_texture_value(self._h, tex, _f(p), len(p), _f(out)) != 0:
+            raise ValueError("no such texture")
+        return out
 
     def set_camera(self, center, look_at, view_up, vfov, defocus_angle, focus_distance) -> None:
         """Camera setters (Camera.hpp:69-101) for the renders that follow."""

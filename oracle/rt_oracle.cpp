@@ -4,13 +4,19 @@
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library,
 // and only as the checker / the timed CPU baseline — never as the product path.
 //
-// Parity status: PARTIALLY PINNED. The reference ships no tests or golden vectors and cannot be
-// built here (glm, nlohmann>=3.6, SDL2, GLEW, imgui and TBB headers are absent). This restatement
-// is pinned by (a) the Philox4x32-10 known-answer vectors, (b) hand-derived known answers for the
-// deterministic functions (tests/test_oracle_kat.py) and (c) a statistical comparison of its
-// converged Cornell render against the reference's own committed render
-// screenshots/cornell_box.png (tests/golden/cornell_box_screenshot_blocks.json). Everything at the
-// glm / libstdc++ boundary beyond that is "parity unpinned" (see DESIGN.md §Oracle).
+// Parity status: PINNED TO THE COMPILED REFERENCE for everything in src/cpu_raytrace. oracle/Makefile's
+// ref target compiles the reference's own src/cpu_raytrace/*.cpp (RayTracer.cpp included) against the
+// stand-ins of oracle/refshim into oracle/_ref/librt2_ref.so, and tests/test_reference_build.py compares
+// this restatement with it bit for bit under CTL_REF_MATH, the reference fed this file's uniforms: the
+// streams, the camera, closest hits on thousands of rays per scene, whole paths through
+// RayTracer::Update and the Perlin textures, with zero differing words on the nine parity scenes.
+// Besides: (a) the Philox4x32-10 known-answer vectors, (b) hand-derived known answers for the
+// deterministic functions (tests/test_oracle_kat.py) and (c) a statistical comparison of converged
+// renders against the reference's screenshots (tests/test_reference_pin.py).
+// Still restated, not pinned: glm's arithmetic (lines "glm-like value types" below and the stand-in
+// oracle/refshim/glm/rt2_glm.hpp are two writings of glm's published operation order; glm itself is not
+// available) and Serialize.cpp (LoadScene below and ref_driver.cpp's loader are two independent
+// restatements that agree). See DESIGN.md §2.
 //
 // Deliberate, documented deviations from the reference (all RNG-related, Finding 2 of SURVEY.md):
 //  * RandReal(): Philox4x32-10 counter stream keyed by (seed, pixel, frame) instead of the
@@ -346,9 +352,12 @@ inline vec3 RandUnitVec3(Rng& g) {
   return {r * c, r * s, z};
 }
 inline vec3 RandInUnitDisk(Rng& g) {
-  if (g_controls & kCtlRefMath) {  // Math.hpp:34-41 (arguments drawn left to right)
+  if (g_controls & kCtlRefMath) {
+    // Math.hpp:34-41 draws both inside one constructor call, vec3(RandReal(-1, 1), RandReal(-1, 1), 0): the
+    // language leaves the order open, and the g++ build of the reference (oracle/_ref) evaluates the
+    // arguments right to left, so the first uniform is y (tests/test_reference_build.py pins this)
     while (true) {
-      const float x = g.RandReal(-1, 1), y = g.RandReal(-1, 1);
+      const float y = g.RandReal(-1, 1), x = g.RandReal(-1, 1);
       const vec3 p{x, y, 0.0f};
       if ((double)dot(p, p) < 1.0) return p;
     }
@@ -1449,6 +1458,19 @@ int oracle_scene_perlin(void* sp, int tex, float* vec, int* perm) {
     perm[2 * pc + i] = t.perlin->perm_z[(size_t)i];
   }
   return pc;
+}
+
+// Value of texture `tex` (Texture.cpp:7-22) at n points (3 floats in, 3 floats out each).
+int oracle_texture_value(void* sp, int tex, const float* points, int n, float* out) {
+  Scene* s = (Scene*)sp;
+  if (tex < 0 || (size_t)tex >= s->textures.size()) return -1;
+  for (int i = 0; i < n; i++) {
+    vec3 v = TexValue(*s, (uint32_t)tex, vec3{points[3 * i], points[3 * i + 1], points[3 * i + 2]});
+    out[3 * i] = v.x;
+    out[3 * i + 1] = v.y;
+    out[3 * i + 2] = v.z;
+  }
+  return 0;
 }
 
 // Camera setters (Camera.hpp:69-101) on the scene camera the next renders use:
