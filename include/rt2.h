@@ -438,6 +438,57 @@ RT2_API int rt2_denoise_buffers(int device, int width, int height, const float* 
  * last denoise call, in ms; -1: none yet. */
 RT2_API int rt2_tracer_denoise_times(rt2_tracer* tr, double* features_ms, double* denoise_ms);
 
+/* ---- Temporal reuse ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before.
+ * The image history reprojected across a camera move: each pixel's first-hit point (feature slots 2-4) is
+ * projected into the camera the history was taken under, the history is read there with bilinear weights from
+ * the taps whose old first hit is the same surface (material index, normal, plane distance, albedo), and
+ * blended with the current estimate in proportion to the two lengths (frames). raytrace2_amd/csrc/temporal.h
+ * defines every operation; float32, bit for bit the same on the GPU, the host and in numpy.
+ * temporal_buffers: the kernels over caller (host) buffers of any image on `device`: the current color float3,
+ *   variance float (of the mean), length float (frames, >= 0) and features (16 floats) per pixel; the same four
+ *   of the history (length 0: none) with the 21 words of rt2_camera_params it was taken under; the material
+ *   table of rt2_scene_materials (8 floats each) or NULL (every material diffuse). out_variance and out_length
+ *   may be NULL.
+ * temporal_resolve: a readback of the tracer's estimate blended with its history. Inputs as rt2_tracer_denoise
+ *   takes them (c = non_converted_pixels, v from standard_error), n = (float)FrameIdx() or each pixel's own n_p
+ *   under adaptive sampling, the tracer's features. With no history held the current estimate comes back
+ *   with length n (0 at a pixel that is not finite). denoise != 0: rt2_tracer_denoise's filter (dp, NULL =
+ *   defaults) then runs over the blended colour and variance with the current features, and the filtered
+ *   colour and variance are returned; out_length is the blend's. Needs what rt2_tracer_denoise needs: moments
+ *   on, FrameIdx() >= 2, an unpartitioned one-GPU tracer. It launches queued frames and synchronises; the
+ *   history, accumulation, moments, counts and FrameIdx() are unchanged: a second call returns the same bytes.
+ * temporal_push: the same blend, never filtered, becomes the history, with the current features and camera
+ *   words; it replaces the previous history. Call it right before set_camera + reset.
+ * The history survives reset and set_camera; on_resize, enable_moments, enable_adaptive, set_partition
+ *   (which reallocate) and temporal_clear drop it.
+ * temporal_time: GPU time (HIP events) of the last resolve's temporal kernels (inputs and blend; not the
+ *   feature pass, not the filter), in ms; -1: none yet.
+ * RT2_ERR_INVALID: resolve / push / clear on a create_multi, joined or partitioned tracer; resolve / push with
+ *   moments off or fewer than 2 frames; max_history, sigma_p or sigma_a not finite and > 0,
+ *   max_history_specular not finite and >= 0, min_normal_dot not finite; a NULL out_color; temporal_buffers
+ *   with width or height <= 0, width * height >= 2^26, n_materials < 0 or a NULL input. */
+typedef struct {
+  float max_history;          /* default 1024: the longest history a pixel carries, in frames */
+  float max_history_specular; /* default 0: the same where the current first hit is a metal or a dielectric */
+  float min_normal_dot;       /* default 0.9: least dot of the current and the old normal */
+  float sigma_p;              /* default 0.01: plane-distance tolerance as a fraction of the hit's distance */
+  float sigma_a;              /* default 0.1: albedo tolerance */
+} rt2_temporal_params;        /* NULL = defaults */
+RT2_API void rt2_temporal_defaults(rt2_temporal_params* out);
+RT2_API int rt2_temporal_buffers(int device, int width, int height, const float* color, const float* variance,
+                                 const float* length, const float* features, const float* hist_color,
+                                 const float* hist_variance, const float* hist_length, const float* hist_features,
+                                 const float* hist_camera /* 21 words */, const float* materials /* may be NULL */,
+                                 int n_materials, const rt2_temporal_params* p, float* out_color, float* out_variance,
+                                 float* out_length);
+RT2_API int rt2_tracer_temporal_resolve(rt2_tracer* tr, const rt2_temporal_params* p, int denoise,
+                                        const rt2_denoise_params* dp, float* out_color,
+                                        float* out_variance /* may be NULL */, float* out_length /* may be NULL */);
+RT2_API int rt2_tracer_temporal_push(rt2_tracer* tr, const rt2_temporal_params* p);
+RT2_API int rt2_tracer_temporal_clear(rt2_tracer* tr);
+RT2_API int rt2_tracer_temporal_time(rt2_tracer* tr, double* resolve_ms);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -283,6 +283,34 @@ class RayTracer {
     return out;
   }
 
+  // Temporal reuse (rt2.h "Temporal reuse"). TemporalPush right before the camera moves and Reset();
+  // TemporalResolve then returns the current estimate blended with the reprojected history (needs what
+  // Denoise needs), filtered by Denoise's filter when denoise is set; it changes nothing. params null: the
+  // defaults (TemporalDefaults); variance / length: receive the variance of the mean and the length in
+  // frames when not null.
+  static rt2_temporal_params TemporalDefaults() {
+    rt2_temporal_params p{};
+    rt2_temporal_defaults(&p);
+    return p;
+  }
+  [[nodiscard]] std::vector<vec3> TemporalResolve(const rt2_temporal_params* params = nullptr, bool denoise = false,
+                                                  const rt2_denoise_params* denoise_params = nullptr,
+                                                  std::vector<float>* variance = nullptr,
+                                                  std::vector<float>* length = nullptr) {
+    Sync();
+    std::vector<vec3> out((size_t)dims_.x * LocalRows());
+    if (variance) variance->assign(out.size(), 0.0f);
+    if (length) length->assign(out.size(), 0.0f);
+    Check(rt2_tracer_temporal_resolve(t_.get(), params, denoise ? 1 : 0, denoise_params, reinterpret_cast<float*>(out.data()),
+                                      variance ? variance->data() : nullptr, length ? length->data() : nullptr));
+    return out;
+  }
+  void TemporalPush(const rt2_temporal_params* params = nullptr) {
+    Sync();
+    Check(rt2_tracer_temporal_push(t_.get(), params));
+  }
+  void TemporalClear() { Check(rt2_tracer_temporal_clear(t_.get())); }
+
   rt2_tracer* handle() const { return t_.get(); }
   [[nodiscard]] int NumGpus() const { return rt2_tracer_n_gpus(t_.get()); }
 

@@ -115,6 +115,15 @@ class DenoiseParams(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class TemporalParams(ctypes.Structure):
+    """rt2_temporal_params."""
+    _fields_ = [("max_history", ctypes.c_float), ("max_history_specular", ctypes.c_float),
+                ("min_normal_dot", ctypes.c_float), ("sigma_p", ctypes.c_float), ("sigma_a", ctypes.c_float)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Every RT2_API function name declared in include/rt2.h."""
     txt = open(header).read()
@@ -220,6 +229,14 @@ def _load():
         "rt2_tracer_denoise": (i32, [vp, ctypes.POINTER(DenoiseParams), fp, fp]),
         "rt2_denoise_buffers": (i32, [i32, i32, i32, fp, fp, fp, ctypes.POINTER(DenoiseParams), fp, fp]),
         "rt2_tracer_denoise_times": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+        "rt2_temporal_defaults": (None, [ctypes.POINTER(TemporalParams)]),
+        "rt2_temporal_buffers": (i32, [i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, i32,
+                                       ctypes.POINTER(TemporalParams), fp, fp, fp]),
+        "rt2_tracer_temporal_resolve": (i32, [vp, ctypes.POINTER(TemporalParams), i32, ctypes.POINTER(DenoiseParams), fp, fp,
+                                              fp]),
+        "rt2_tracer_temporal_push": (i32, [vp, ctypes.POINTER(TemporalParams)]),
+        "rt2_tracer_temporal_clear": (i32, [vp]),
+        "rt2_tracer_temporal_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

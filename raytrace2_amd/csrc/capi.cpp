@@ -22,6 +22,7 @@
 #include "denoise.h"
 #include "noise.h"
 #include "scene.h"
+#include "temporal.h"
 
 namespace rt2 {
 hipError_t LaunchRender(const RenderParams& p, int variant, bool stats, int grid, hipStream_t stream);
@@ -46,6 +47,13 @@ hipError_t LaunchDenoiseInputs(const float* accum, const float* moment2, const u
                                uint32_t npix, int64_t n_frames, hipStream_t stream);
 hipError_t LaunchDenoise(void* scratch, const float* features, int width, int height, const DenoiseParams& k, bool lds,
                          hipStream_t stream);
+size_t TemporalHistoryBytes(size_t npix);
+hipError_t LaunchTemporalPack(const float* color, const float* variance, const float* length, const float* features,
+                              void* hist, uint32_t npix, hipStream_t stream);
+hipError_t LaunchTemporalBlend(float* color, float* variance, const float* length, const uint32_t* counts, float n_scalar,
+                               const float* features, const void* hist, const float* camera, const float* materials,
+                               int n_materials, bool type_bits, const TemporalParams& k, float* out_length, int width,
+                               int height, hipStream_t stream);
 int RenderMode(const RenderParams& p);
 int RenderBlockSize();
 int RenderVariant(uint32_t features);
@@ -150,6 +158,16 @@ struct rt2_tracer {
   void* d_dn_scratch = nullptr;
   size_t dn_scratch_bytes = 0;
   double features_ms = -1.0, denoise_ms = -1.0;
+  // temporal reuse (rt2.h "Temporal reuse"), allocated at the first call: the packed history (temporal.hip's
+  // four planes) and the blend's length plane; whether a history is held and the camera words it was pushed
+  // under; the GPU time of the last resolve's temporal kernels (-1: none)
+  void* d_tp_hist = nullptr;
+  float* d_tp_len = nullptr;
+  size_t tp_bytes = 0;
+  bool tp_valid = false;
+  float tp_cam[kTemporalCameraWords] = {};
+  int n_materials = 0;  // materials in d_materials
+  double temporal_ms = -1.0;
   uint32_t* d_work = nullptr;  // one work counter per launch slot (words 0 and 16)
   unsigned long long* d_stats = nullptr;
   bool stats_on = false;
@@ -324,6 +342,12 @@ void FreeFrame(rt2_tracer* t) {
   (void)hipFree(t->d_ad_scratch);
   (void)hipFree(t->d_features);
   (void)hipFree(t->d_dn_scratch);
+  (void)hipFree(t->d_tp_hist);
+  (void)hipFree(t->d_tp_len);
+  t->d_tp_hist = nullptr;
+  t->d_tp_len = nullptr;
+  t->tp_bytes = 0;
+  t->tp_valid = false;
   t->d_features = nullptr;
   t->features_valid = false;
   t->d_dn_scratch = nullptr;
@@ -351,7 +375,7 @@ size_t DeviceBytes(const rt2_tracer* t) {
   size_t b = t->scene_bytes + (t->d_accum ? n * 12 : 0) + (t->d_pixels ? n * 4 : 0) + (t->d_ray_counts ? n * 4 : 0) +
              (t->d_moment2 ? n * 12 : 0) + t->noise_blocks * sizeof(NoisePartial) +
              (t->d_counts ? n * (4 + 1 + 1 + 4 + 4) + 64 * 4 : 0) + t->ad_scratch_bytes +
-             (t->d_features ? n * kDenoiseFeatureFloats * sizeof(float) : 0) + t->dn_scratch_bytes;
+             (t->d_features ? n * kDenoiseFeatureFloats * sizeof(float) : 0) + t->dn_scratch_bytes + t->tp_bytes;
   for (const auto& sl : t->slots) b += sl.samples_bytes + sl.chunks_bytes;
   if (t->d_image) b += t->stacks_bytes + t->image_pixels * (12 + 12 + 4);
   return b;
@@ -744,6 +768,7 @@ int rt2_tracer_create(const rt2_scene* s, int device, rt2_tracer** out) {
   t->node_records = (uint32_t)(c.nodes.size() / 4);
   t->hot_records = c.hot_records;
   t->features = c.features;
+  t->n_materials = (int)(c.materials.size() / 8);
   t->max_stack = c.max_stack;
   t->stack_ok = c.stack_ok;
   t->flat_xforms = c.lin_xform_depth <= 1;
@@ -2206,6 +2231,227 @@ int rt2_denoise_buffers(int device, int width, int height, const float* color, c
   (void)hipFree(scratch);
   if (stream) (void)hipStreamDestroy(stream);
   if (e != hipSuccess) return HipFail(e, "denoise_buffers");
+  return RT2_OK;
+}
+
+// ---- temporal reuse (rt2.h "Temporal reuse") ----
+void rt2_temporal_defaults(rt2_temporal_params* out) {
+  if (!out) return;
+  const TemporalParams d = TemporalDefaults();
+  out->max_history = d.max_history;
+  out->max_history_specular = d.max_history_specular;
+  out->min_normal_dot = d.min_normal_dot;
+  out->sigma_p = d.sigma_p;
+  out->sigma_a = d.sigma_a;
+}
+
+static int TemporalParamsOf(const rt2_temporal_params* p, TemporalParams* k) {
+  *k = TemporalDefaults();
+  if (p) *k = TemporalParams{p->max_history, p->max_history_specular, p->min_normal_dot, p->sigma_p, p->sigma_a};
+  if (!TemporalParamsValid(*k))
+    return Fail(RT2_ERR_INVALID, "temporal: need max_history, sigma_p, sigma_a finite and > 0, max_history_specular finite "
+                                 "and >= 0, min_normal_dot finite");
+  return RT2_OK;
+}
+
+// The blend of the tracer's current estimate with its history, left on the device: colour and variance at
+// the head of the denoise scratch (where LaunchDenoise takes them), the length in d_tp_len. The checks of
+// rt2_tracer_denoise; push: the result then replaces the history. ev (or null): two events taken from the pool
+// and recorded around the kernels, left null on failure.
+static int TemporalBlend(rt2_tracer* t, const rt2_temporal_params* params, bool with_denoise, bool push, hipEvent_t* ev) {
+  if (IsMulti(t) || t->comm || t->world != 1)
+    return Fail(RT2_ERR_INVALID, "temporal: needs an unpartitioned one-GPU tracer (world 1, not joined)");
+  TemporalParams k;
+  int rc = TemporalParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "temporal: moments not enabled (rt2_tracer_enable_moments)");
+  if ((rc = Sync(t)) != RT2_OK) return rc;
+  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "temporal needs at least 2 frames");
+  if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  const size_t need = with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float);
+  if (need > t->dn_scratch_bytes) {
+    (void)hipFree(t->d_dn_scratch);
+    t->d_dn_scratch = nullptr;
+    t->dn_scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&t->d_dn_scratch, need));
+    t->dn_scratch_bytes = need;
+    NoteDeviceBytes(t);
+  }
+  if (!t->d_tp_hist) {
+    t->tp_valid = false;
+    HIP_TRY(hipMalloc(&t->d_tp_hist, TemporalHistoryBytes(n)));
+    if (hipMalloc(&t->d_tp_len, n * sizeof(float)) != hipSuccess) {
+      (void)hipFree(t->d_tp_hist);
+      t->d_tp_hist = nullptr;
+      return Fail(RT2_ERR_HIP, "temporal: out of device memory");
+    }
+    t->tp_bytes = TemporalHistoryBytes(n) + n * sizeof(float);
+    NoteDeviceBytes(t);
+  }
+  float* d_color = static_cast<float*>(t->d_dn_scratch);
+  hipEvent_t e0 = ev ? TakeEvent(t) : nullptr, e1 = ev ? TakeEvent(t) : nullptr;
+  if (ev && (!e0 || !e1)) {
+    if (e0) t->event_pool.push_back(e0);
+    return Fail(RT2_ERR_HIP, "event create failed");
+  }
+  hipError_t e = e0 ? hipEventRecord(e0, t->stream) : hipSuccess;
+  if (e == hipSuccess)
+    e = LaunchDenoiseInputs(t->d_accum, t->d_moment2, t->adaptive_on ? t->d_counts : nullptr, t->d_dn_scratch, (uint32_t)n,
+                            t->frame_idx, t->stream);
+  if (e == hipSuccess)
+    e = LaunchTemporalBlend(d_color, d_color + 3 * n, nullptr, t->adaptive_on ? t->d_counts : nullptr, (float)t->frame_idx,
+                            t->d_features, t->tp_valid ? t->d_tp_hist : nullptr, t->tp_cam,
+                            static_cast<const float*>(t->d_materials), t->n_materials, true, k, t->d_tp_len, t->width,
+                            t->local_rows, t->stream);
+  if (e == hipSuccess && e1) e = hipEventRecord(e1, t->stream);
+  if (e == hipSuccess && push) {
+    t->tp_valid = false;  // until the pack has run
+    e = LaunchTemporalPack(d_color, d_color + 3 * n, t->d_tp_len, t->d_features, t->d_tp_hist, (uint32_t)n, t->stream);
+  }
+  if (e != hipSuccess) {
+    if (ev) t->event_pool.push_back(e0), t->event_pool.push_back(e1);
+    return HipFail(e, "temporal");
+  }
+  if (ev) ev[0] = e0, ev[1] = e1;
+  return RT2_OK;
+}
+
+static void CameraWords(const CameraParams& p, float* out) {  // rt2_camera_params' 21 words
+  memcpy(out, p.pixel00, 3 * sizeof(float));
+  memcpy(out + 3, p.du, 3 * sizeof(float));
+  memcpy(out + 6, p.dv, 3 * sizeof(float));
+  memcpy(out + 9, p.center, 3 * sizeof(float));
+  memcpy(out + 12, p.defocus_u, 3 * sizeof(float));
+  memcpy(out + 15, p.defocus_v, 3 * sizeof(float));
+  out[18] = p.defocus_angle;
+  out[19] = p.recip_sqrt_spp;
+  out[20] = (float)p.sqrt_spp;
+}
+
+int rt2_tracer_temporal_resolve(rt2_tracer* t, const rt2_temporal_params* params, int denoise, const rt2_denoise_params* dparams,
+                                float* out_color, float* out_variance, float* out_length) {
+  if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  DenoiseParams dk = DenoiseDefaults();
+  int rc = denoise ? DenoiseParamsOf(dparams, &dk) : RT2_OK;
+  if (rc != RT2_OK) return rc;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if ((rc = TemporalBlend(t, params, denoise != 0, false, ev)) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  float* d_color = static_cast<float*>(t->d_dn_scratch);
+  hipError_t e = hipSuccess;
+  if (denoise) e = LaunchDenoise(t->d_dn_scratch, t->d_features, t->width, t->local_rows, dk, DenoiseLds(), t->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess && out_length)
+    e = hipMemcpyAsync(out_length, t->d_tp_len, n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) {
+    t->event_pool.push_back(ev[0]);
+    t->event_pool.push_back(ev[1]);
+    return HipFail(e, "temporal_resolve");
+  }
+  t->temporal_ms = EventMs(t, ev[0], ev[1]);
+  return RT2_OK;
+}
+
+int rt2_tracer_temporal_push(rt2_tracer* t, const rt2_temporal_params* params) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  int rc = TemporalBlend(t, params, false, true, nullptr);
+  if (rc != RT2_OK) return rc;
+  if ((size_t)t->width * (size_t)t->local_rows == 0) return RT2_OK;
+  hipError_t e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, "temporal_push");
+  CameraWords(t->camera.Params(), t->tp_cam);
+  t->tp_valid = true;
+  return RT2_OK;
+}
+
+int rt2_tracer_temporal_clear(rt2_tracer* t) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t) || t->comm || t->world != 1)
+    return Fail(RT2_ERR_INVALID, "temporal: needs an unpartitioned one-GPU tracer (world 1, not joined)");
+  t->tp_valid = false;
+  return RT2_OK;
+}
+
+int rt2_tracer_temporal_time(rt2_tracer* t, double* resolve_ms) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "temporal_time: not on a multi-GPU tracer");
+  if (resolve_ms) *resolve_ms = t->temporal_ms;
+  return RT2_OK;
+}
+
+int rt2_temporal_buffers(int device, int width, int height, const float* color, const float* variance, const float* length,
+                         const float* features, const float* hist_color, const float* hist_variance,
+                         const float* hist_length, const float* hist_features, const float* hist_camera,
+                         const float* materials, int n_materials, const rt2_temporal_params* params, float* out_color,
+                         float* out_variance, float* out_length) {
+  if (!color || !variance || !length || !features || !hist_color || !hist_variance || !hist_length || !hist_features ||
+      !hist_camera || !out_color)
+    return Fail(RT2_ERR_INVALID, "null argument");
+  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
+    return Fail(RT2_ERR_INVALID, "temporal_buffers: need width, height > 0 and width * height below 2^26");
+  if (n_materials < 0 || n_materials >= 1 << 24)
+    return Fail(RT2_ERR_INVALID, "temporal_buffers: need 0 <= n_materials < 2^24");
+  TemporalParams k;
+  int rc = TemporalParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  const size_t n = (size_t)width * (size_t)height;
+  const size_t nf = n * kDenoiseFeatureFloats * sizeof(float);
+  const bool mats = materials && n_materials > 0;
+  // cur / old: colour float3, variance, length; then the two feature images, the history planes, the table
+  float *d_cur = nullptr, *d_old = nullptr, *d_feat = nullptr, *d_hfeat = nullptr, *d_out_len = nullptr, *d_mat = nullptr;
+  void* d_hist = nullptr;
+  hipStream_t stream = nullptr;
+  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipMalloc(&d_cur, n * 5 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_old, n * 5 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_feat, nf);
+  if (e == hipSuccess) e = hipMalloc(&d_hfeat, nf);
+  if (e == hipSuccess) e = hipMalloc(&d_out_len, n * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_hist, TemporalHistoryBytes(n));
+  if (e == hipSuccess && mats) e = hipMalloc(&d_mat, (size_t)n_materials * kTemporalMaterialFloats * sizeof(float));
+  const auto up = [&](float* dst, const float* src, size_t bytes) {
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
+  };
+  up(d_cur, color, n * 3 * sizeof(float));
+  up(d_cur + 3 * n, variance, n * sizeof(float));
+  up(d_cur + 4 * n, length, n * sizeof(float));
+  up(d_old, hist_color, n * 3 * sizeof(float));
+  up(d_old + 3 * n, hist_variance, n * sizeof(float));
+  up(d_old + 4 * n, hist_length, n * sizeof(float));
+  up(d_feat, features, nf);
+  up(d_hfeat, hist_features, nf);
+  if (mats) up(d_mat, materials, (size_t)n_materials * kTemporalMaterialFloats * sizeof(float));
+  if (e == hipSuccess) e = LaunchTemporalPack(d_old, d_old + 3 * n, d_old + 4 * n, d_hfeat, d_hist, (uint32_t)n, stream);
+  if (e == hipSuccess)
+    e = LaunchTemporalBlend(d_cur, d_cur + 3 * n, d_cur + 4 * n, nullptr, 0.0f, d_feat, d_hist, hist_camera, d_mat,
+                            mats ? n_materials : 0, false, k, d_out_len, width, height, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_cur, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_cur + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_length) e = hipMemcpyAsync(out_length, d_out_len, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  (void)hipFree(d_mat);
+  (void)hipFree(d_hist);
+  (void)hipFree(d_out_len);
+  (void)hipFree(d_hfeat);
+  (void)hipFree(d_feat);
+  (void)hipFree(d_old);
+  (void)hipFree(d_cur);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (e != hipSuccess) return HipFail(e, "temporal_buffers");
   return RT2_OK;
 }
 

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._native import AppSettings as _AppSettings
-from ._native import UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Noise, SceneInfo, Stats, check, lib
+from ._native import UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Noise, SceneInfo, Stats, TemporalParams, check, lib
 
 DEFAULT_SEED = 0x5EED2024
 
@@ -229,6 +229,54 @@ def denoise_buffers(color, variance, features, device: int = 0, **params):
     check(lib.rt2_denoise_buffers(int(device), w, h, _fp(color), _fp(variance), _fp(features), _denoise_params(params),
                                   _fp(out), _fp(var)))
     return out, var
+
+
+def temporal_defaults() -> dict:
+    """rt2_temporal_defaults as a dict."""
+    p = TemporalParams()
+    lib.rt2_temporal_defaults(ctypes.byref(p))
+    return p.as_dict()
+
+
+def _temporal_params(params: dict):
+    """A rt2_temporal_params pointer for the keyword arguments (None = NULL: the defaults)."""
+    if not params:
+        return None
+    p = TemporalParams()
+    lib.rt2_temporal_defaults(ctypes.byref(p))
+    for k, v in params.items():
+        if k not in dict(TemporalParams._fields_):
+            raise TypeError(f"temporal: unknown parameter {k!r}")
+        setattr(p, k, float(v))
+    return ctypes.byref(p)
+
+
+def temporal_buffers(color, variance, length, features, hist_color, hist_variance, hist_length, hist_features, hist_camera,
+                     materials=None, device: int = 0, **params):
+    """rt2_temporal_buffers: the tracer's temporal blend over caller buffers: the current and the history's color
+    (H, W, 3), variance (H, W), length (H, W), features (H, W, 16) float32, the 21 camera words the history was
+    taken under, and the material table (n, 8) of Scene.materials() or None. Returns (color', variance', length')."""
+    cur = [np.ascontiguousarray(a, np.float32) for a in (color, variance, length, features)]
+    old = [np.ascontiguousarray(a, np.float32) for a in (hist_color, hist_variance, hist_length, hist_features)]
+    cam = np.ascontiguousarray(hist_camera, np.float32)
+    if cur[1].ndim != 2:
+        raise ValueError("temporal_buffers: need variance (H, W)")
+    h, w = cur[1].shape
+    shapes = [(h, w, 3), (h, w), (h, w), (h, w, 16)]
+    if [a.shape for a in cur] != shapes or [a.shape for a in old] != shapes or cam.shape != (21,):
+        raise ValueError("temporal_buffers: need color (H, W, 3), variance (H, W), length (H, W), features (H, W, 16) of the "
+                         "current image and of the history, and 21 camera words")
+    mats, n_mats = None, 0
+    if materials is not None:
+        mats = np.ascontiguousarray(materials, np.float32)
+        if mats.ndim != 2 or mats.shape[1] != 8:
+            raise ValueError("temporal_buffers: need materials (n, 8)")
+        n_mats = mats.shape[0]
+    out, var, ln = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+    check(lib.rt2_temporal_buffers(int(device), w, h, *[_fp(a) for a in cur], *[_fp(a) for a in old], _fp(cam),
+                                   _fp(mats) if n_mats else None, n_mats, _temporal_params(params), _fp(out), _fp(var),
+                                   _fp(ln)))
+    return out, var, ln
 
 
 class RayTracer:
@@ -519,6 +567,39 @@ class RayTracer:
         f, d = ctypes.c_double(-1.0), ctypes.c_double(-1.0)
         check(lib.rt2_tracer_denoise_times(self._h, ctypes.byref(f), ctypes.byref(d)))
         return {"features_ms": f.value, "denoise_ms": d.value}
+
+    # -- temporal reuse (rt2.h "Temporal reuse") ------------------------------------------------
+    def temporal_resolve(self, denoise=False, variance: bool = False, length: bool = False, **params):
+        """The current estimate blended with the history pushed before the last camera move (needs what denoise()
+        needs): (H, W, 3) float32; with variance / length also the variance of the mean and the length in frames,
+        (H, W) each. denoise: True, or a dict of rt2_denoise_params fields, runs denoise()'s filter over the blend.
+        params: the fields of rt2_temporal_params that differ from temporal_defaults(). Changes nothing."""
+        self._push_camera()
+        w, _ = self.Dims()
+        rows = max(self.local_rows(), 0)
+        out = np.zeros((rows, w, 3), np.float32)
+        var = np.zeros((rows, w), np.float32) if variance else None
+        ln = np.zeros((rows, w), np.float32) if length else None
+        dn = _denoise_params(denoise) if isinstance(denoise, dict) else None
+        check(lib.rt2_tracer_temporal_resolve(self._h, _temporal_params(params), 1 if denoise else 0, dn, _fp(out),
+                                              _fp(var) if variance else None, _fp(ln) if length else None))
+        res = (out,) + ((var,) if variance else ()) + ((ln,) if length else ())
+        return res if len(res) > 1 else out
+
+    def temporal_push(self, **params) -> None:
+        """Make the blended estimate (never filtered) the history, with the current features and camera: call it
+        before changing the camera, then Reset()."""
+        self._push_camera()
+        check(lib.rt2_tracer_temporal_push(self._h, _temporal_params(params)))
+
+    def temporal_clear(self) -> None:
+        check(lib.rt2_tracer_temporal_clear(self._h))
+
+    def temporal_time(self) -> float:
+        """GPU ms of the last temporal_resolve's temporal kernels (-1: none yet)."""
+        ms = ctypes.c_double(-1.0)
+        check(lib.rt2_tracer_temporal_time(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def enable_stats(self, on: bool = True) -> None:
         check(lib.rt2_tracer_enable_stats(self._h, 1 if on else 0))
