@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "adaptive.h"
+#include "kernels.h"
 
 namespace rt2 {
 namespace dev {

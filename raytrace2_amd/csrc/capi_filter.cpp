@@ -1,0 +1,391 @@
+// capi_filter.cpp — the feature buffers, the denoiser and temporal reuse of include/rt2.h (over render.hip's feature
+// pass, denoise.hip and temporal.hip).
+#include <hip/hip_runtime_api.h>
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "tracer.h"
+
+using namespace rt2;
+using namespace rt2::detail;
+
+extern "C" {
+
+// ---- feature buffers and denoiser (rt2.h "Feature buffers and denoiser") ----
+void rt2_denoise_defaults(rt2_denoise_params* out) {
+  if (!out) return;
+  const DenoiseParams d = DenoiseDefaults();
+  out->iterations = d.iterations;
+  out->normal_power_log2 = d.normal_power_log2;
+  out->sigma_l = d.sigma_l;
+  out->sigma_p = d.sigma_p;
+  out->sigma_a = d.sigma_a;
+  out->eps_l = d.eps_l;
+}
+
+static int DenoiseParamsOf(const rt2_denoise_params* p, DenoiseParams* k) {
+  *k = DenoiseDefaults();
+  if (p) *k = DenoiseParams{p->iterations, p->normal_power_log2, p->sigma_l, p->sigma_p, p->sigma_a, p->eps_l};
+  if (!DenoiseParamsValid(*k))
+    return Fail(RT2_ERR_INVALID, "denoise: need 1 <= iterations <= 8, 0 <= normal_power_log2 <= 8, and sigma_l, sigma_p, "
+                                 "sigma_a, eps_l finite and > 0");
+  return RT2_OK;
+}
+
+// The small steps' LDS tiles (denoise.hip): on unless RT2_DENOISE_LDS=0 (measured: DESIGN.md §6e).
+static bool DenoiseLds() {
+  const char* e = getenv("RT2_DENOISE_LDS");
+  return !(e && e[0] == '0');
+}
+
+// GPU time between the pair's events, recorded on the tracer's stream, which the caller has synchronised.
+static double EventMs(const EventPair& ev) {
+  float ms = -1.0f;
+  if (hipEventElapsedTime(&ms, ev.e0, ev.e1) != hipSuccess) ms = -1.0f;
+  return (double)ms;
+}
+
+// The tracer's feature records on its device, traced again when the camera, the seed, the size or the
+// partition have changed since (Realloc drops the buffer). ev: events recorded around the pass.
+static int EnsureFeatures(rt2_tracer* t, bool* launched, const EventPair& ev) {
+  *launched = false;
+  if (!t->stack_ok)
+    return Fail(RT2_ERR_INVALID, "features: the scene needs a traversal stack of " + std::to_string(t->max_stack) +
+                                     " entries (kernel has " + std::to_string(kTraversalStack) + ")");
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  const CameraParams cam = t->camera.Params();
+  if (n == 0) return RT2_OK;
+  if (t->d_features && t->features_valid && t->features_seed == t->seed &&
+      memcmp(&t->features_cam, &cam, sizeof(cam)) == 0)
+    return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  if (!t->d_features) {
+    const size_t rows = (size_t)t->width * (size_t)AllocRows(t);
+    HIP_TRY(t->d_features.Alloc(rows * kDenoiseFeatureFloats * sizeof(float)));
+    NoteDeviceBytes(t);
+  }
+  RenderParams p;
+  BaseParams(t, cam, &p);
+  p.local_pixels = (uint32_t)n;
+  HIP_TRY(hipEventRecord(ev.e0, t->stream));
+  HIP_TRY(LaunchFeatures(p, t->d_features.get<float>(), t->stream));
+  HIP_TRY(hipEventRecord(ev.e1, t->stream));
+  t->features_valid = true;
+  t->features_cam = cam;
+  t->features_seed = t->seed;
+  *launched = true;
+  return RT2_OK;
+}
+
+static int FeaturesTimed(rt2_tracer* t) {
+  EventPair ev(t);
+  if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
+  bool launched = false;
+  int rc = EnsureFeatures(t, &launched, ev);
+  if (rc != RT2_OK || !launched) return rc;
+  hipError_t e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, "feature pass");
+  t->features_ms = EventMs(ev);
+  return RT2_OK;
+}
+
+// The denoise scratch, grown to `need` bytes.
+static int EnsureScratch(rt2_tracer* t, size_t need) {
+  if (need > t->d_dn_scratch.bytes()) {
+    HIP_TRY(t->d_dn_scratch.Grow(need));
+    NoteDeviceBytes(t);
+  }
+  return RT2_OK;
+}
+
+int rt2_tracer_features(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || t->comm)
+    return Fail(RT2_ERR_INVALID, "features: not on a multi-GPU or joined tracer (a set_partition tracer works)");
+  int rc = FeaturesTimed(t);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n) {
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipMemcpyAsync(out, t->d_features.get<float>(), n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyDeviceToHost,
+                           t->stream));
+    t->host_waits++;
+    HIP_TRY(hipStreamSynchronize(t->stream));
+  }
+  return RT2_OK;
+}
+
+int rt2_tracer_denoise(rt2_tracer* t, const rt2_denoise_params* params, float* out_color, float* out_variance) {
+  if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || t->comm || t->world != 1)
+    return Fail(RT2_ERR_INVALID, "denoise: needs an unpartitioned one-GPU tracer (world 1, not joined)");
+  DenoiseParams k;
+  int rc = DenoiseParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "denoise: moments not enabled (rt2_tracer_enable_moments)");
+  if ((rc = Sync(t)) != RT2_OK) return rc;
+  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "denoise needs at least 2 frames");
+  if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  if ((rc = EnsureScratch(t, DenoiseScratchBytes(n))) != RT2_OK) return rc;
+  EventPair ev(t);
+  if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
+  float* d_color = t->d_dn_scratch.get<float>();
+  hipError_t e = hipEventRecord(ev.e0, t->stream);
+  if (e == hipSuccess)
+    e = LaunchDenoiseInputs(t->d_accum.get<float>(), t->d_moment2.get<float>(),
+                            t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr, d_color, (uint32_t)n, t->frame_idx, t->stream);
+  if (e == hipSuccess) e = LaunchDenoise(d_color, t->d_features.get<float>(), t->width, t->local_rows, k, DenoiseLds(), t->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev.e1, t->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, "denoise");
+  t->denoise_ms = EventMs(ev);
+  return RT2_OK;
+}
+
+int rt2_tracer_denoise_times(rt2_tracer* t, double* features_ms, double* denoise_ms) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "denoise_times: not on a multi-GPU tracer");
+  if (features_ms) *features_ms = t->features_ms;
+  if (denoise_ms) *denoise_ms = t->denoise_ms;
+  return RT2_OK;
+}
+
+int rt2_denoise_buffers(int device, int width, int height, const float* color, const float* variance,
+                        const float* features, const rt2_denoise_params* params, float* out_color, float* out_variance) {
+  if (!color || !variance || !features || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
+    return Fail(RT2_ERR_INVALID, "denoise_buffers: need width, height > 0 and width * height below 2^26");
+  DenoiseParams k;
+  int rc = DenoiseParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  const size_t n = (size_t)width * (size_t)height;
+  DeviceBuffer scratch, feat;  // (freed in the reverse order)
+  hipStream_t stream = nullptr;
+  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = scratch.Alloc(DenoiseScratchBytes(n));
+  if (e == hipSuccess) e = feat.Alloc(n * kDenoiseFeatureFloats * sizeof(float));
+  float* d_color = scratch.get<float>();
+  float* d_feat = feat.get<float>();
+  if (e == hipSuccess) e = hipMemcpyAsync(d_color, color, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_color + 3 * n, variance, n * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_feat, features, n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = LaunchDenoise(d_color, d_feat, width, height, k, DenoiseLds(), stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (e != hipSuccess) return HipFail(e, "denoise_buffers");
+  return RT2_OK;
+}
+
+// ---- temporal reuse (rt2.h "Temporal reuse") ----
+void rt2_temporal_defaults(rt2_temporal_params* out) {
+  if (!out) return;
+  const TemporalParams d = TemporalDefaults();
+  out->max_history = d.max_history;
+  out->max_history_specular = d.max_history_specular;
+  out->min_normal_dot = d.min_normal_dot;
+  out->sigma_p = d.sigma_p;
+  out->sigma_a = d.sigma_a;
+}
+
+static int TemporalParamsOf(const rt2_temporal_params* p, TemporalParams* k) {
+  *k = TemporalDefaults();
+  if (p) *k = TemporalParams{p->max_history, p->max_history_specular, p->min_normal_dot, p->sigma_p, p->sigma_a};
+  if (!TemporalParamsValid(*k))
+    return Fail(RT2_ERR_INVALID, "temporal: need max_history, sigma_p, sigma_a finite and > 0, max_history_specular finite "
+                                 "and >= 0, min_normal_dot finite");
+  return RT2_OK;
+}
+
+// The blend of the tracer's current estimate with its history, left on the device: colour and variance at
+// the head of the denoise scratch (where LaunchDenoise takes them), the length in d_tp_len. The checks of
+// rt2_tracer_denoise; push: the result then replaces the history. ev (or null): takes its two events from the
+// pool and records them around the kernels.
+static int TemporalBlend(rt2_tracer* t, const rt2_temporal_params* params, bool with_denoise, bool push, EventPair* ev) {
+  if (IsMulti(t) || t->comm || t->world != 1)
+    return Fail(RT2_ERR_INVALID, "temporal: needs an unpartitioned one-GPU tracer (world 1, not joined)");
+  TemporalParams k;
+  int rc = TemporalParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "temporal: moments not enabled (rt2_tracer_enable_moments)");
+  if ((rc = Sync(t)) != RT2_OK) return rc;
+  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "temporal needs at least 2 frames");
+  if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  if ((rc = EnsureScratch(t, with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float))) != RT2_OK) return rc;
+  if (!t->d_tp_hist) {
+    t->tp_valid = false;
+    HIP_TRY(t->d_tp_hist.Alloc(TemporalHistoryBytes(n)));
+    if (t->d_tp_len.Alloc(n * sizeof(float)) != hipSuccess) {
+      t->d_tp_hist.reset();
+      return Fail(RT2_ERR_HIP, "temporal: out of device memory");
+    }
+    NoteDeviceBytes(t);
+  }
+  float* d_color = t->d_dn_scratch.get<float>();
+  const uint32_t* counts = t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr;
+  if (ev && !ev->Take()) return Fail(RT2_ERR_HIP, "event create failed");
+  hipError_t e = ev ? hipEventRecord(ev->e0, t->stream) : hipSuccess;
+  if (e == hipSuccess)
+    e = LaunchDenoiseInputs(t->d_accum.get<float>(), t->d_moment2.get<float>(), counts, d_color, (uint32_t)n, t->frame_idx,
+                            t->stream);
+  if (e == hipSuccess)
+    e = LaunchTemporalBlend(d_color, d_color + 3 * n, nullptr, counts, (float)t->frame_idx, t->d_features.get<float>(),
+                            t->tp_valid ? t->d_tp_hist.get<void>() : nullptr, t->tp_cam, t->d_materials.get<float>(),
+                            t->n_materials, true, k, t->d_tp_len.get<float>(), t->width, t->local_rows, t->stream);
+  if (e == hipSuccess && ev) e = hipEventRecord(ev->e1, t->stream);
+  if (e == hipSuccess && push) {
+    t->tp_valid = false;  // until the pack has run
+    e = LaunchTemporalPack(d_color, d_color + 3 * n, t->d_tp_len.get<float>(), t->d_features.get<float>(),
+                           t->d_tp_hist.get<void>(), (uint32_t)n, t->stream);
+  }
+  if (e != hipSuccess) return HipFail(e, "temporal");
+  return RT2_OK;
+}
+
+static void CameraWords(const CameraParams& p, float* out) {  // rt2_camera_params' 21 words
+  memcpy(out, p.pixel00, 3 * sizeof(float));
+  memcpy(out + 3, p.du, 3 * sizeof(float));
+  memcpy(out + 6, p.dv, 3 * sizeof(float));
+  memcpy(out + 9, p.center, 3 * sizeof(float));
+  memcpy(out + 12, p.defocus_u, 3 * sizeof(float));
+  memcpy(out + 15, p.defocus_v, 3 * sizeof(float));
+  out[18] = p.defocus_angle;
+  out[19] = p.recip_sqrt_spp;
+  out[20] = (float)p.sqrt_spp;
+}
+
+int rt2_tracer_temporal_resolve(rt2_tracer* t, const rt2_temporal_params* params, int denoise, const rt2_denoise_params* dparams,
+                                float* out_color, float* out_variance, float* out_length) {
+  if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  DenoiseParams dk = DenoiseDefaults();
+  int rc = denoise ? DenoiseParamsOf(dparams, &dk) : RT2_OK;
+  if (rc != RT2_OK) return rc;
+  EventPair ev(t);
+  if ((rc = TemporalBlend(t, params, denoise != 0, false, &ev)) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  float* d_color = t->d_dn_scratch.get<float>();
+  hipError_t e = hipSuccess;
+  if (denoise) e = LaunchDenoise(d_color, t->d_features.get<float>(), t->width, t->local_rows, dk, DenoiseLds(), t->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess && out_length)
+    e = hipMemcpyAsync(out_length, t->d_tp_len.get<float>(), n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, "temporal_resolve");
+  t->temporal_ms = EventMs(ev);
+  return RT2_OK;
+}
+
+int rt2_tracer_temporal_push(rt2_tracer* t, const rt2_temporal_params* params) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  int rc = TemporalBlend(t, params, false, true, nullptr);
+  if (rc != RT2_OK) return rc;
+  if ((size_t)t->width * (size_t)t->local_rows == 0) return RT2_OK;
+  hipError_t e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, "temporal_push");
+  CameraWords(t->camera.Params(), t->tp_cam);
+  t->tp_valid = true;
+  return RT2_OK;
+}
+
+int rt2_tracer_temporal_clear(rt2_tracer* t) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t) || t->comm || t->world != 1)
+    return Fail(RT2_ERR_INVALID, "temporal: needs an unpartitioned one-GPU tracer (world 1, not joined)");
+  t->tp_valid = false;
+  return RT2_OK;
+}
+
+int rt2_tracer_temporal_time(rt2_tracer* t, double* resolve_ms) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "temporal_time: not on a multi-GPU tracer");
+  if (resolve_ms) *resolve_ms = t->temporal_ms;
+  return RT2_OK;
+}
+
+int rt2_temporal_buffers(int device, int width, int height, const float* color, const float* variance, const float* length,
+                         const float* features, const float* hist_color, const float* hist_variance,
+                         const float* hist_length, const float* hist_features, const float* hist_camera,
+                         const float* materials, int n_materials, const rt2_temporal_params* params, float* out_color,
+                         float* out_variance, float* out_length) {
+  if (!color || !variance || !length || !features || !hist_color || !hist_variance || !hist_length || !hist_features ||
+      !hist_camera || !out_color)
+    return Fail(RT2_ERR_INVALID, "null argument");
+  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
+    return Fail(RT2_ERR_INVALID, "temporal_buffers: need width, height > 0 and width * height below 2^26");
+  if (n_materials < 0 || n_materials >= 1 << 24)
+    return Fail(RT2_ERR_INVALID, "temporal_buffers: need 0 <= n_materials < 2^24");
+  TemporalParams k;
+  int rc = TemporalParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  const size_t n = (size_t)width * (size_t)height;
+  const size_t nf = n * kDenoiseFeatureFloats * sizeof(float);
+  const bool mats = materials && n_materials > 0;
+  // cur / old: colour float3, variance, length; then the two feature images, the history planes, the table
+  DeviceBuffer cur, old, feat, hfeat, out_len, hist, mat;  // (freed in the reverse order)
+  hipStream_t stream = nullptr;
+  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = cur.Alloc(n * 5 * sizeof(float));
+  if (e == hipSuccess) e = old.Alloc(n * 5 * sizeof(float));
+  if (e == hipSuccess) e = feat.Alloc(nf);
+  if (e == hipSuccess) e = hfeat.Alloc(nf);
+  if (e == hipSuccess) e = out_len.Alloc(n * sizeof(float));
+  if (e == hipSuccess) e = hist.Alloc(TemporalHistoryBytes(n));
+  if (e == hipSuccess && mats) e = mat.Alloc((size_t)n_materials * kTemporalMaterialFloats * sizeof(float));
+  float *d_cur = cur.get<float>(), *d_old = old.get<float>(), *d_feat = feat.get<float>(), *d_hfeat = hfeat.get<float>();
+  float *d_out_len = out_len.get<float>(), *d_mat = mat.get<float>();
+  void* d_hist = hist.get<void>();
+  const auto up = [&](float* dst, const float* src, size_t bytes) {
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
+  };
+  up(d_cur, color, n * 3 * sizeof(float));
+  up(d_cur + 3 * n, variance, n * sizeof(float));
+  up(d_cur + 4 * n, length, n * sizeof(float));
+  up(d_old, hist_color, n * 3 * sizeof(float));
+  up(d_old + 3 * n, hist_variance, n * sizeof(float));
+  up(d_old + 4 * n, hist_length, n * sizeof(float));
+  up(d_feat, features, nf);
+  up(d_hfeat, hist_features, nf);
+  if (mats) up(d_mat, materials, (size_t)n_materials * kTemporalMaterialFloats * sizeof(float));
+  if (e == hipSuccess) e = LaunchTemporalPack(d_old, d_old + 3 * n, d_old + 4 * n, d_hfeat, d_hist, (uint32_t)n, stream);
+  if (e == hipSuccess)
+    e = LaunchTemporalBlend(d_cur, d_cur + 3 * n, d_cur + 4 * n, nullptr, 0.0f, d_feat, d_hist, hist_camera, d_mat,
+                            mats ? n_materials : 0, false, k, d_out_len, width, height, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_cur, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_cur + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_length) e = hipMemcpyAsync(out_length, d_out_len, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (e != hipSuccess) return HipFail(e, "temporal_buffers");
+  return RT2_OK;
+}
+}  // extern "C"

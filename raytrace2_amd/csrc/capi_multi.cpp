@@ -1,0 +1,290 @@
+// capi_multi.cpp — the gather of the ranks' row bands to rank 0 and the multi-GPU entry points of include/rt2.h: a
+// multi-GPU tracer is a facade over one one-GPU tracer per device.
+#include <hip/hip_runtime_api.h>
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "tracer.h"
+
+using namespace rt2;
+using namespace rt2::detail;
+
+namespace {
+
+// Row-band height of the multi-GPU partitions (band_h 0). Measured, 8-way split emulated rank by rank
+// on one MI355X (job rate = all ranks' rays / the slowest rank's time), band heights 8 / 4 / 2 / 1:
+// Cornell 190 / 193 / 197 / 198 k Mray/s, book 1 55.9 / 57.5 / 54.9 / 54.6 k, Cornell volume
+// 119.6 / - / 121.5 / 122.4 k, book 2 9.89 / - / 10.15 / 9.81 k. Narrow bands balance the ranks
+// (image cost varies smoothly with the row); 2 rows (32x2 work tiles) is within 1-5 % of the best.
+constexpr int kDefaultBandH = 2;
+
+// ---- multi-GPU gather ----
+// Sizes the root's gathered band stacks and full-image buffers for its current dims and world.
+int EnsureImage(rt2_tracer* root) {
+  const size_t npix = (size_t)root->width * (size_t)root->height;
+  const size_t stacks = (size_t)root->world * (size_t)BandRowsMax(root) * (size_t)root->width * 3 * sizeof(float);
+  if (root->d_image.bytes() == npix * 3 * sizeof(float) && root->d_stacks.bytes() == stacks) return RT2_OK;
+  FreeImage(root);
+  HIP_TRY(hipSetDevice(root->device));
+  HIP_TRY(root->d_stacks.Alloc(stacks));
+  HIP_TRY(root->d_image.Alloc(npix * 3 * sizeof(float)));
+  HIP_TRY(root->d_image_nc.Alloc(npix * 3 * sizeof(float)));
+  HIP_TRY(root->d_image_px.Alloc(npix * 4));
+  NoteDeviceBytes(root);
+  return RT2_OK;
+}
+
+// Gathers the band stacks of `ranks` (every rank this thread drives: a multi tracer's parts, or
+// one joined tracer) to rank 0 and de-interleaves them there. RCCL unless `loopback` (the ranks
+// share one GPU and their stacks are copied on it). Enqueued on the streams; does not wait.
+int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback) {
+  rt2_tracer* root = nullptr;
+  for (rt2_tracer* p : ranks) {
+    int rc = Flush(p);
+    if (rc != RT2_OK) return rc;
+    if (p->rank == 0) root = p;
+  }
+  const rt2_tracer* r0 = ranks[0];
+  for (rt2_tracer* p : ranks)
+    if (p->width != r0->width || p->height != r0->height || p->frame_idx != r0->frame_idx)
+      return Fail(RT2_ERR_INVALID, "gather: the ranks disagree on dims or frame index");
+  const size_t count = (size_t)BandRowsMax(r0) * (size_t)r0->width * 3;  // floats per rank
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (root) {
+    int rc = EnsureImage(root);
+    if (rc != RT2_OK) return rc;
+    HIP_TRY(hipSetDevice(root->device));
+    e0 = TakeEvent(root);
+    e1 = TakeEvent(root);
+    if (e0) HIP_TRY(hipEventRecord(e0, root->stream));
+  }
+  if (count > 0) {
+    if (loopback) {
+      for (rt2_tracer* p : ranks) {
+        HIP_TRY(hipSetDevice(p->device));
+        if (p != root) {
+          hipEvent_t e = TakeEvent(p);
+          if (!e) return Fail(RT2_ERR_HIP, "event create failed");
+          HIP_TRY(hipEventRecord(e, p->stream));
+          HIP_TRY(hipStreamWaitEvent(root->stream, e, 0));
+          p->event_pool.push_back(e);
+        }
+        HIP_TRY(hipMemcpyAsync(root->d_stacks.get<float>() + (size_t)p->rank * count, p->d_accum.get<float>(),
+                               count * sizeof(float), hipMemcpyDeviceToDevice, root->stream));
+      }
+      // later work on a part's stream (Render, Reset) must not overwrite its accumulation while the
+      // root's copy may still read it: every part stream waits for the copies
+      if (ranks.size() > 1) {
+        HIP_TRY(hipSetDevice(root->device));
+        hipEvent_t e = TakeEvent(root);
+        if (!e) return Fail(RT2_ERR_HIP, "event create failed");
+        HIP_TRY(hipEventRecord(e, root->stream));
+        for (rt2_tracer* p : ranks)
+          if (p != root) HIP_TRY(hipStreamWaitEvent(p->stream, e, 0));
+        root->event_pool.push_back(e);
+      }
+    } else {
+      for (rt2_tracer* p : ranks)
+        if (!p->comm) return Fail(RT2_ERR_INVALID, "gather: tracer is not part of a communicator");
+      NCCL_TRY(ncclGroupStart());
+      for (rt2_tracer* p : ranks) {
+        ncclResult_t r = ncclGather(p->d_accum.get<float>(), p == root ? root->d_stacks.get<float>() : nullptr, count,
+                                    ncclFloat32, 0, p->comm, p->stream);
+        if (r != ncclSuccess) {
+          (void)ncclGroupEnd();
+          return Fail(RT2_ERR_HIP, std::string("ncclGather: ") + ncclGetErrorString(r));
+        }
+      }
+      NCCL_TRY(ncclGroupEnd());
+    }
+  }
+  if (root) {
+    HIP_TRY(hipSetDevice(root->device));
+    HIP_TRY(LaunchDeinterleave(root->d_stacks.get<float>(), root->d_image.get<float>(), root->d_image_nc.get<float>(),
+                               root->d_image_px.get<uint8_t>(), root->width, root->height, BandH(root), root->world,
+                               BandRowsMax(root), (int)root->frame_idx, root->stream));
+    if (e1) HIP_TRY(hipEventRecord(e1, root->stream));
+    if (e0 && e1) root->gpending.emplace_back(e0, e1);
+    root->image_frame = root->frame_idx;
+    root->gathers++;
+  }
+  return RT2_OK;
+}
+}  // namespace
+
+int rt2::detail::GatherMulti(rt2_tracer* t) {
+  if (IsMulti(t)) return GatherRanks(t->parts, t->loopback);
+  if (t->comm) return GatherRanks({t}, false);
+  if (t->world > 1) return Fail(RT2_ERR_INVALID, "gather: a partitioned tracer must be joined to a communicator");
+  return GatherRanks({t}, true);  // one GPU, whole image: the "gather" is a device-local copy
+}
+
+namespace {
+// The root tracer holding the gathered image (rank 0), after a gather.
+int ImageRoot(rt2_tracer* t, rt2_tracer** root) {
+  rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
+  if (r->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  if (r->image_frame < 0) return Fail(RT2_ERR_INVALID, "no gathered image (call rt2_tracer_gather first)");
+  int rc = Sync(r);
+  if (rc != RT2_OK) return rc;
+  *root = r;
+  return RT2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// ---- multi-GPU entry points ----
+int rt2_multi_plan(int n, const int* devices, int band_h, int width, int height, rt2_part_plan* out, int* loopback) {
+  if (n < 1 || band_h < 0) return Fail(RT2_ERR_INVALID, "rt2_tracer_create_multi: need n_gpus >= 1, band_h >= 0");
+  if (width < 0 || height < 0) return Fail(RT2_ERR_INVALID, "rt2_multi_plan: negative dims");
+  std::vector<int> devs((size_t)n);
+  for (int i = 0; i < n; i++) devs[(size_t)i] = devices ? devices[i] : i;
+  for (int d : devs)
+    if (d < 0) return Fail(RT2_ERR_INVALID, "rt2_tracer_create_multi: negative device id");
+  const bool all_same = std::all_of(devs.begin(), devs.end(), [&](int d) { return d == devs[0]; });
+  std::vector<int> sorted = devs;
+  std::sort(sorted.begin(), sorted.end());
+  const bool distinct = std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+  if (!distinct && !all_same)
+    return Fail(RT2_ERR_INVALID, "rt2_tracer_create_multi: devices must be distinct (or all one GPU, for tests)");
+  const int bh = band_h > 0 ? band_h : kDefaultBandH;
+  if (loopback) *loopback = n > 1 && all_same ? 1 : 0;
+  if (out) {
+    for (int i = 0; i < n; i++) {
+      rt2_part_plan& q = out[i];
+      q.device = devs[(size_t)i];
+      q.rank = i;
+      q.world = n;
+      q.band_h = bh;
+      q.local_rows = height > 0 ? LocalRows(height, bh, i, n) : 0;
+      q.rows_max = rt2::BandRowsMax(height, bh, n);
+    }
+  }
+  return RT2_OK;
+}
+
+int rt2_tracer_create_multi(const rt2_scene* s, int n, const int* devices, int band_h, rt2_tracer** out) {
+  if (!s || !out) return Fail(RT2_ERR_INVALID, "rt2_tracer_create_multi: null argument");
+  *out = nullptr;
+  int lb = 0;
+  int prc = rt2_multi_plan(n, devices, band_h, 0, 0, nullptr, &lb);
+  if (prc != RT2_OK) return prc;
+  std::vector<int> devs((size_t)n);
+  for (int i = 0; i < n; i++) devs[(size_t)i] = devices ? devices[i] : i;
+  auto m = std::make_unique<rt2_tracer>();
+  m->loopback = lb != 0;
+  const int bh = band_h > 0 ? band_h : kDefaultBandH;
+  auto cleanup = [&](int rc) {
+    for (rt2_tracer* p : m->parts) rt2_tracer_destroy(p);
+    m->parts.clear();
+    return rc;
+  };
+  for (int i = 0; i < n; i++) {
+    rt2_tracer* p = nullptr;
+    int rc = rt2_tracer_create(s, devs[(size_t)i], &p);
+    if (rc != RT2_OK) return cleanup(rc);
+    m->parts.push_back(p);
+    if ((rc = rt2_tracer_set_partition(p, bh, i, n)) != RT2_OK) return cleanup(rc);
+  }
+  if (!m->loopback) {  // one communicator per device (rank i on devs[i]), RCCL over xGMI
+    std::vector<ncclComm_t> comms((size_t)n, nullptr);
+    ncclResult_t r = ncclCommInitAll(comms.data(), n, devs.data());
+    if (r != ncclSuccess) return cleanup(Fail(RT2_ERR_HIP, std::string("ncclCommInitAll: ") + ncclGetErrorString(r)));
+    for (int i = 0; i < n; i++) m->parts[(size_t)i]->comm = comms[(size_t)i];
+  }
+  m->device = devs[0];
+  m->width = m->parts[0]->width;
+  m->height = m->parts[0]->height;
+  m->band_h = bh;
+  m->world = n;
+  *out = m.release();
+  return RT2_OK;
+}
+
+int rt2_comm_unique_id(uint8_t* out, size_t cap) {
+  if (!out || cap < sizeof(ncclUniqueId)) return Fail(RT2_ERR_INVALID, "rt2_comm_unique_id: need RT2_UNIQUE_ID_BYTES");
+  ncclUniqueId id;
+  NCCL_TRY(ncclGetUniqueId(&id));
+  memcpy(out, &id, sizeof(id));
+  return RT2_OK;
+}
+
+int rt2_tracer_join(rt2_tracer* t, const uint8_t* unique_id, int world, int rank, int band_h) {
+  if (!t || !unique_id) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: null argument");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: a multi-GPU tracer has its own communicators");
+  if (t->comm) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: already joined");
+  if (t->adaptive_on) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: adaptive sampling is on (one-GPU tracers only)");
+  int rc = rt2_tracer_set_partition(t, band_h > 0 ? band_h : kDefaultBandH, rank, world);
+  if (rc != RT2_OK) return rc;
+  ncclUniqueId id;
+  memcpy(&id, unique_id, sizeof(id));
+  HIP_TRY(hipSetDevice(t->device));
+  NCCL_TRY(ncclCommInitRank(&t->comm, world, id, rank));
+  return RT2_OK;
+}
+
+int rt2_tracer_gather(rt2_tracer* t) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  return GatherMulti(t);
+}
+
+int rt2_tracer_image_accumulation(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  rt2_tracer* r = nullptr;
+  int rc = ImageRoot(t, &r);
+  if (rc != RT2_OK) return rc;
+  size_t n = (size_t)r->width * (size_t)r->height;
+  if (n) HIP_TRY(hipMemcpy(out, r->d_image.get<float>(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+
+// NonConvertedPixels() of the gathered image: accumulation / frame_idx_ (RayTracer.cpp:108-109),
+// divided on the GPU by the de-interleave kernel (the same IEEE quotient as the host's)
+int rt2_tracer_image_non_converted_pixels(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  rt2_tracer* r = nullptr;
+  int rc = ImageRoot(t, &r);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)r->width * (size_t)r->height;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (n) HIP_TRY(hipMemcpy(out, r->d_image_nc.get<float>(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  r->readback_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  r->readbacks++;
+  return RT2_OK;
+}
+
+// The same, enqueued on the root's stream (out: pinned host memory, rt2_host_alloc); complete once
+// rt2_tracer_query returns 1 or after rt2_tracer_synchronize. Needs a gather enqueued before it.
+int rt2_tracer_image_non_converted_pixels_async(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
+  if (r->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  if (r->image_frame < 0) return Fail(RT2_ERR_INVALID, "no gathered image (call rt2_tracer_gather first)");
+  HIP_TRY(hipSetDevice(r->device));
+  const size_t n = (size_t)r->width * (size_t)r->height;
+  hipEvent_t e0 = TakeEvent(r), e1 = TakeEvent(r);
+  if (e0) HIP_TRY(hipEventRecord(e0, r->stream));
+  if (n) HIP_TRY(hipMemcpyAsync(out, r->d_image_nc.get<float>(), n * 3 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+  if (e1) HIP_TRY(hipEventRecord(e1, r->stream));
+  if (e0 && e1) r->rpending.emplace_back(e0, e1);
+  r->readbacks++;
+  return RT2_OK;
+}
+
+int rt2_tracer_image_pixels(rt2_tracer* t, uint8_t* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  rt2_tracer* r = nullptr;
+  int rc = ImageRoot(t, &r);
+  if (rc != RT2_OK) return rc;
+  size_t n = (size_t)r->width * (size_t)r->height;
+  if (n) HIP_TRY(hipMemcpy(out, r->d_image_px.get<uint8_t>(), n * 4, hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+}  // extern "C"

@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "denoise.h"
+#include "kernels.h"
 #include "noise.h"
 
 namespace rt2 {

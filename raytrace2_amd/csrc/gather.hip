@@ -10,6 +10,7 @@
 
 #include <cstdint>
 
+#include "kernels.h"
 #include "rt2_layout.h"
 
 namespace rt2 {

@@ -1,0 +1,134 @@
+// launch_plan.h — the render launch planner: the integer arithmetic between "render n frames" and a
+// kernel launch (magic divisors, tile geometry, frames per launch, the chunk schedule, item counts).
+// Host only, no HIP call and no tracer: tests/cpp/launch_plan_host.cpp runs it without a GPU.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "rt2_layout.h"
+
+namespace rt2 {
+
+inline Magic MakeMagic(uint32_t d) {  // rt2_layout.h Magic: floor(n / d) for n < 2^31
+  uint32_t l = 0;
+  while ((1ull << l) < (uint64_t)d) l++;
+  const uint64_t m = ((1ull << (31 + l)) + d - 1) / d;
+  return Magic{(uint32_t)m, 31 + l};
+}
+
+// Work tiles of 64 pixels: 8x8, or as tall as a row band narrower than 8 rows (16x4, 32x2, 64x1)
+// so that a wave's pixels stay in one band (neighbouring pixels, coherent primary rays).
+// band_h: the band height of the launch (RenderParams::band_h, the image height when unpartitioned).
+struct TileGeometry {
+  uint32_t tile_shift;
+  int tiles_x;
+  uint32_t tile_items;
+};
+inline TileGeometry PlanTiles(int width, int local_rows, int band_h, int world) {
+  const int tile_rows = world > 1 && band_h < 8 ? (band_h >= 4 ? 4 : band_h >= 2 ? 2 : 1) : 8;
+  TileGeometry g;
+  g.tile_shift = tile_rows == 8 ? 3u : tile_rows == 4 ? 4u : tile_rows == 2 ? 5u : 6u;
+  g.tiles_x = (width + (1 << g.tile_shift) - 1) >> g.tile_shift;
+  g.tile_items = (uint32_t)g.tiles_x * (uint32_t)((local_rows + tile_rows - 1) / tile_rows) * 64u;
+  return g;
+}
+
+// The sample buffer holds whole octets of frames (rt2_layout.h kOctet).
+inline size_t SampleOctets(size_t frames) { return (frames + kOctet - 1) / kOctet * kOctet; }
+
+// Frames per launch: the caller's launch_frames (0: all n_frames), bounded by the sample-buffer budget
+// (each of the two slots gets half the budget, so both together stay within it; frame_bytes = one frame
+// of samples) and, with frame tiles, by the items (64-frame groups x 64 x local pixels) staying below 2^31.
+inline int FramesPerLaunch(int launch_frames, int n_frames, size_t sample_budget, size_t frame_bytes, bool frame_tiles,
+                           uint32_t local_pixels) {
+  int per_launch = launch_frames > 0 ? std::min(launch_frames, n_frames) : n_frames;
+  const size_t budget_frames = std::max<size_t>(1, sample_budget / 2 / frame_bytes);
+  per_launch = (int)std::min<size_t>((size_t)per_launch, budget_frames < kOctet ? budget_frames : budget_frames - budget_frames % kOctet);
+  if (frame_tiles) {
+    const size_t groups = std::max<size_t>(1, (size_t)0x7FFFFFFF / (64u * (size_t)local_pixels));
+    per_launch = (int)std::min<size_t>((size_t)per_launch, groups * 64u);
+  }
+  return per_launch;
+}
+
+struct ChunkSettings {
+  bool frame_tiles;    // items = one pixel x 64 short chunks per wave
+  int frame_tile_len;  // most frames per chunk in frame-tile mode
+  int work_split;      // work left split into >= k items per lane (0: one chunk)
+  int chunk_max;       // longest chunk (frames)
+  bool chunk_align;    // chunks of >= kOctet frames: multiples of 4 frames
+};
+
+// Frame chunks of one launch: frames [fb, fb + n) cut into chunks, every pixel's chunk c one work
+// item (chunk-major). A chunk starting with R frames left holds about R * T / (k * L) frames (T =
+// items per chunk, L = resident lanes, k = work_split), at least 1 and at most chunk_max: early
+// items are long (few item setups per sample) and the last ones short, so the launch's tail — the
+// time in which lanes run out of work while others finish their item — stays short. k = 0: one
+// chunk (each pixel's frames in one item). Appends the table (first frame, stratum) per chunk and
+// the sentinel to `tab`; returns the number of chunks and the first chunk's length.
+inline void ChunkSchedule(const ChunkSettings& t, int fb, int n, uint32_t tile_items, int64_t lanes, int sq,
+                          std::vector<uint32_t>& tab, uint32_t* n_chunks, int* first_len) {
+  const size_t start = tab.size();
+  // items must stay below 2^31 (kernel index arithmetic): shortest chunk that allows it
+  const int64_t max_chunks = std::max<int64_t>(1, (int64_t)0x7FFFFFFF / tile_items);
+  const int lo = (int)std::max<int64_t>(1, ((int64_t)n + max_chunks - 1) / max_chunks);
+  int first = 0;
+  // frame tiles: chunks of up to frame_tile_len frames, as even as the 64-chunk groups allow (the
+  // last group is padded with empty chunks, whose lanes fetch again)
+  int ft_len = 1;
+  if (t.frame_tiles) {
+    const int groups = (n + 64 * t.frame_tile_len - 1) / (64 * t.frame_tile_len);
+    ft_len = (n + 64 * groups - 1) / (64 * groups);
+  }
+  for (int s = 0; s < n;) {
+    int len = n - s;
+    if (t.frame_tiles) {
+      len = ft_len;  // frame tiles: short chunks of one pixel (RenderParams::frame_tiles)
+    } else if (t.work_split > 0) {
+      const double want = (double)(n - s) * (double)tile_items / ((double)t.work_split * (double)lanes);
+      len = (int)std::min<double>(want, (double)t.chunk_max);
+    }
+    // long chunks start on a 4-frame group of the sample octets (the 8-wave kernels stage samples
+    // by 4 frames; whole octets would cut a 15-frame chunk to 8)
+    if (t.chunk_align && len >= (int)kOctet) len -= len % 4;
+    if (!t.frame_tiles) len = std::max(len, lo);
+    len = std::min({len, n - s, kChunkMaxFrames});
+    const uint32_t f = (uint32_t)(fb + s), usq = (uint32_t)sq;
+    tab.push_back(f);
+    tab.push_back((f % usq) | (((f / usq) % usq) << 16));  // RayTracer.cpp:59-60
+    if (s == 0) first = len;
+    s += len;
+  }
+  if (t.frame_tiles) {  // padding chunks up to a multiple of 64 (empty: first frame = the launch end)
+    while (((tab.size() - start) / 2) % 64 != 0) {
+      tab.push_back((uint32_t)(fb + n));
+      tab.push_back(0u);
+    }
+  }
+  tab.push_back((uint32_t)(fb + n));
+  tab.push_back(0u);
+  *n_chunks = (uint32_t)((tab.size() - start) / 2 - 1);
+  *first_len = first;
+}
+
+// Per-launch item fields: the work items of n_chunks chunks (frame tiles: 64-chunk groups of one pixel each),
+// the reservation divisor (half of the left work / waves) and the grid of `block`-lane workgroups that
+// `resident` lanes, or the items if fewer, fill.
+struct LaunchItems {
+  uint32_t n_items, frame_tile, batch_div;
+  int grid;
+};
+inline LaunchItems PlanItems(uint32_t n_chunks, uint32_t tile_items, bool frame_tiles, uint32_t local_pixels,
+                             int64_t resident, int block) {
+  LaunchItems it;
+  it.frame_tile = frame_tiles ? 64u * local_pixels : 0u;
+  it.n_items = frame_tiles ? (n_chunks / 64u) * it.frame_tile : n_chunks * tile_items;
+  it.batch_div = (uint32_t)std::max<int64_t>(1, (resident / 64) * 2);
+  it.grid = std::max((int)std::min<int64_t>(resident, (int64_t)it.n_items) / block, 1);
+  return it;
+}
+
+}  // namespace rt2

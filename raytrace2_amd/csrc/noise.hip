@@ -12,6 +12,7 @@
 
 #include <cstdint>
 
+#include "kernels.h"
 #include "noise.h"
 
 namespace rt2 {

@@ -39,6 +39,7 @@
 #include "rt2_layout.h"
 #define RT2_BOXAA_FN __device__ __forceinline__
 #include "boxaa.h"
+#include "kernels.h"
 
 namespace rt2 {
 namespace dev {
@@ -3404,7 +3405,6 @@ int RenderMode(const RenderParams& p) {
 // Whether a launch of this kernel can walk a flat program (render.hip kFeatFlat): the Cornell box's threaded
 // product kernel over the whole image. Counting launches, launches over an active list, the other feature
 // sets and the stack traversals keep the BVH program.
-bool RenderTakesHitTable(int variant, int mode, bool stats);
 bool RenderTakesFlat(int variant, int mode, bool stats, bool list) {
   return variant == dev::kFlatVariant && mode == kModeLinear && !stats && !list &&
          RenderTakesHitTable(variant, mode, stats);

@@ -17,6 +17,7 @@
 
 #include <cstdint>
 
+#include "kernels.h"
 #include "temporal.h"
 
 namespace rt2 {

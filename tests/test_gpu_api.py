@@ -190,3 +190,73 @@ def test_medium_box_far_away_matches_the_oracle(have_gpu):
     o_acc, _, _ = o.render(w, h, spp, frames, forward=True)
     assert st["box_certified"] > 0
     assert np.array_equal(acc.view(np.uint32), o_acc.view(np.uint32))
+
+
+# ---- device-byte accounting ---------------------------------------------------------------------------------
+# Scene program, tables and small per-tracer buffers (work counters, clock ring, counters) of the two scenes, in
+# bytes: what a fresh tracer reported beyond its frame buffers before the flat program's tables were counted.
+CORNELL_SCENE_BYTES = 17140
+BOOK1_SCENE_BYTES = 167476
+# The Cornell box's flat program: its wide steps, 64 * (flat_steps + 1) = 1472 bytes, and the certificate table,
+# 1984 bytes (one float per float of the threaded program's records).
+CORNELL_FLAT_BYTES = 1472 + 1984
+
+
+@pytest.mark.parametrize("w,h", [(64, 48), (672, 672)])
+def test_device_bytes_peak_is_the_sum_of_the_buffers(have_gpu, w, h):
+    """rt2_stats.device_bytes_peak is the high-water mark of everything the tracer holds: it equals, state by
+    state, the running maximum of the documented buffer list (a tracer is created at the scene's own dims, which
+    is the mark until a larger state; 672 x 672 is above the Cornell box's 600 x 600, so there every Cornell state
+    shows, while book 1's 1600 x 900 mark checks its scene bytes alone)."""
+    from raytrace2_amd.dist import band_rows_max
+    n = w * h
+    sc = R.Scene(scene_path("cornell_box_original"), R.DEFAULT_SEED)
+    assert 64 * (sc.info().flat_steps + 1) == 1472
+    scene = CORNELL_SCENE_BYTES + CORNELL_FLAT_BYTES
+    tr = R.RayTracer(sc, 0)
+    peak = scene + 600 * 600 * 16  # accumulation float3 + RGBA8 at the scene's 600 x 600
+
+    def check(t, now, what):
+        nonlocal peak
+        peak = max(peak, now)
+        got = t.stats()["device_bytes_peak"]
+        print(f"{w}x{h} {what}: held {now}, peak {got}")
+        assert got == peak, (what, got, peak)
+
+    tr.SetSamplesPerPixel(16)
+    tr.OnResize((w, h))
+    check(tr, scene + n * 16, "fresh")
+    tr.enable_moments()  # + the float3 sums of squares
+    check(tr, scene + n * 28, "moments")
+    tr.enable_adaptive()  # + counts, active, over, list (padded by 64), slot_of, and the check's scratch
+    tiles, blocks = -(-w // 32) * -(-h // 8), -(-n // 256)
+    frame = n * 28 + n * 14 + 256 + tiles * 12 + 4 + blocks * 16 + 32 + 16
+    check(tr, scene + frame, "adaptive")
+    tr.Render(2)
+    tr.denoise()
+    assert tr.last_launch()["chunk_frames"] == 1
+    # one launch slot: an octet of frames of float3 samples, and the table of two one-frame chunks and the
+    # sentinel; the feature records (16 floats); the filter's scratch (DenoiseScratchBytes: 100 bytes per pixel)
+    held = scene + frame + 8 * n * 12 + 24 + n * 64 + n * 100
+    check(tr, held, "denoise")
+    tr.temporal_resolve()  # + the packed history (64 bytes per pixel) and the length plane
+    check(tr, held + n * 68, "temporal")
+    tr.close()
+
+    # two parts on one GPU: each holds its band stack (the largest rank's rows); the root, after a gather, also
+    # the gathered stacks and the image (float3 sum, float3 mean, RGBA8)
+    tr = R.RayTracer(sc, devices=[0, 0])
+    peak = scene + 600 * 600 * 16
+    tr.OnResize((w, h))
+    rows = band_rows_max(h, 2, 2)
+    tr.gather()
+    check(tr, scene + w * rows * 16 + 2 * rows * w * 12 + n * 28, "gathered")
+    tr.close()
+
+    sc = R.Scene(scene_path("final_render_book_1"), R.DEFAULT_SEED)
+    assert sc.info().flat_steps == 0
+    tr = R.RayTracer(sc, 0)
+    peak = BOOK1_SCENE_BYTES + 1600 * 900 * 16  # no dims in the scene file: the window default
+    tr.OnResize((w, h))
+    check(tr, BOOK1_SCENE_BYTES + n * 16, "book 1, fresh")
+    tr.close()
