@@ -489,6 +489,51 @@ RT2_API int rt2_tracer_temporal_push(rt2_tracer* tr, const rt2_temporal_params* 
 RT2_API int rt2_tracer_temporal_clear(rt2_tracer* tr);
 RT2_API int rt2_tracer_temporal_time(rt2_tracer* tr, double* resolve_ms);
 
+/* ---- Presenting reconstructed frames ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before.
+ * The display path of the reconstruction: what rt2_tracer_pixels_async is to the raw accumulation. Every call
+ * but `present` and `present_buffers` only enqueues on the tracer's stream and returns at once; none of them
+ * adds to rt2_stats.host_waits.
+ * present_async: enqueues, in this order, the queued frames (as rt2_tracer_flush), the feature pass if its cache
+ *   is stale, the inputs of rt2_tracer_denoise (c = non_converted_pixels, v from standard_error; each pixel's
+ *   own n_p under adaptive sampling), if `temporal` rt2_tracer_temporal_resolve's blend with the held history
+ *   (none held: the current estimate), if `denoise` rt2_tracer_denoise's filter, the tone map
+ *   (raytrace2_amd/csrc/present.h: per channel v = c > 0 ? c : 0, v = v < 1 ? v : 1, byte = floor((double)v *
+ *   255.999), alpha 255: Pixels()'s arithmetic, defined for every input: NaN -> 0, +inf -> 255, -inf -> 0) and
+ *   a copy of 4 * width * height bytes into out_rgba. The buffer is complete when rt2_tracer_query returns 1 or
+ *   after rt2_tracer_synchronize; pinned memory from rt2_host_alloc makes the copy a DMA. With both stages off
+ *   the bytes are those of rt2_tracer_pixels. Needs what temporal_resolve needs, decided on the host without a
+ *   wait (FrameIdx() counts queued frames): moments on, FrameIdx() >= 2, an unpartitioned one-GPU tracer. The
+ *   accumulation, moments, counts, history and FrameIdx() are unchanged. Later calls reuse the tracer's scratch;
+ *   stream order makes several presents in flight into different buffers safe.
+ * present: present_async, then rt2_tracer_synchronize.
+ * move_camera: temporal_push, set_camera and reset in one call, without a wait. With moments on and
+ *   FrameIdx() >= 2 on an unpartitioned tracer the blend (tp, NULL = defaults) becomes the history, taken under
+ *   the camera the frames were rendered with; otherwise (also on a set_partition tracer) it is set_camera +
+ *   reset, and a history already held is kept. The reset's zeroing runs on the tracer's stream behind the push.
+ * present_time: GPU time (HIP events) of the last present's kernels (inputs, blend, filter, tone map; not the
+ *   render, the feature pass or the copy), in ms; -1 while that present has not finished, or when there was
+ *   none. It polls the event and never waits.
+ * present_buffers: the tone map alone over a caller (host) float3 image on `device`; it blocks, like
+ *   rt2_denoise_buffers.
+ * RT2_ERR_INVALID: any of the four tracer calls on a create_multi or joined tracer, and all but move_camera on a
+ *   partitioned one; present / present_async with moments off or fewer than 2 frames, or with invalid temporal
+ *   or denoise parameters (checked only for the stages switched on); move_camera with invalid temporal
+ *   parameters; a NULL tracer, output or camera; present_buffers with width or height <= 0, width * height >=
+ *   2^26 or a NULL argument. A refused call changes nothing. */
+typedef struct {
+  int temporal;            /* default 1: blend with the history (rt2_tracer_temporal_resolve's blend) */
+  int denoise;             /* default 1: then rt2_tracer_denoise's filter */
+  rt2_temporal_params tp;  /* defaults of rt2_temporal_defaults */
+  rt2_denoise_params dp;   /* defaults of rt2_denoise_defaults */
+} rt2_present_params;      /* NULL = defaults */
+RT2_API void rt2_present_defaults(rt2_present_params* out);
+RT2_API int rt2_tracer_present_async(rt2_tracer* tr, const rt2_present_params* p, uint8_t* out_rgba);
+RT2_API int rt2_tracer_present(rt2_tracer* tr, const rt2_present_params* p, uint8_t* out_rgba);
+RT2_API int rt2_tracer_move_camera(rt2_tracer* tr, const rt2_camera_desc* cam, const rt2_temporal_params* tp);
+RT2_API int rt2_tracer_present_time(rt2_tracer* tr, double* ms);
+RT2_API int rt2_present_buffers(int device, int width, int height, const float* color, uint8_t* out_rgba);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -311,6 +311,49 @@ class RayTracer {
   }
   void TemporalClear() { Check(rt2_tracer_temporal_clear(t_.get())); }
 
+  // Presenting reconstructed frames (rt2.h "Presenting reconstructed frames"): the display path of the
+  // reconstruction. PresentAsync enqueues blend, filter, tone map and the copy of Dims().x * LocalRows RGBA8
+  // pixels into `out` (pinned memory from rt2_host_alloc makes it a DMA) and returns at once; the bytes are
+  // complete once Query() returns true or after Synchronize(). Present is the blocking form. MoveCamera is
+  // TemporalPush, the camera change and Reset() in one call that does not wait; the history is taken under the
+  // camera of the last Update(), and `*camera`, when set, takes `to`'s fields (`to` may be `*camera` itself,
+  // moved in place since that Update). params null: the defaults (PresentDefaults).
+  static rt2_present_params PresentDefaults() {
+    rt2_present_params p{};
+    rt2_present_defaults(&p);
+    return p;
+  }
+  void PresentAsync(u8vec4* out, const rt2_present_params* params = nullptr) {
+    Sync();
+    Check(rt2_tracer_present_async(t_.get(), params, reinterpret_cast<uint8_t*>(out)));
+  }
+  [[nodiscard]] const PixelArray& Present(const rt2_present_params* params = nullptr) {
+    Sync();
+    pixels_.resize((size_t)dims_.x * LocalRows());
+    Check(rt2_tracer_present(t_.get(), params, reinterpret_cast<uint8_t*>(pixels_.data())));
+    return pixels_;
+  }
+  void MoveCamera(const Camera& to, const rt2_temporal_params* params = nullptr) {
+    const rt2_camera_desc d = to.Desc();
+    Check(rt2_tracer_move_camera(t_.get(), &d, params));
+    if (camera && camera != &to) {
+      const int spp = camera->samples_per_pixel_;
+      *camera = to;
+      camera->samples_per_pixel_ = spp;
+    }
+  }
+  [[nodiscard]] double PresentTime() {  // GPU ms of the last present's kernels; -1: not finished, or none
+    double ms = -1.0;
+    Check(rt2_tracer_present_time(t_.get(), &ms));
+    return ms;
+  }
+  [[nodiscard]] bool Query() {
+    const int q = rt2_tracer_query(t_.get());
+    Check(q);
+    return q == 1;
+  }
+  void Synchronize() { Check(rt2_tracer_synchronize(t_.get())); }
+
   rt2_tracer* handle() const { return t_.get(); }
   [[nodiscard]] int NumGpus() const { return rt2_tracer_n_gpus(t_.get()); }
 

@@ -124,6 +124,15 @@ class TemporalParams(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class PresentParams(ctypes.Structure):
+    """rt2_present_params."""
+    _fields_ = [("temporal", ctypes.c_int), ("denoise", ctypes.c_int), ("tp", TemporalParams), ("dp", DenoiseParams)]
+
+    def as_dict(self):
+        return {"temporal": int(self.temporal), "denoise": int(self.denoise), "tp": self.tp.as_dict(),
+                "dp": self.dp.as_dict()}
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Every RT2_API function name declared in include/rt2.h."""
     txt = open(header).read()
@@ -237,6 +246,12 @@ def _load():
         "rt2_tracer_temporal_push": (i32, [vp, ctypes.POINTER(TemporalParams)]),
         "rt2_tracer_temporal_clear": (i32, [vp]),
         "rt2_tracer_temporal_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
+        "rt2_present_defaults": (None, [ctypes.POINTER(PresentParams)]),
+        "rt2_tracer_present_async": (i32, [vp, ctypes.POINTER(PresentParams), ctypes.POINTER(ctypes.c_uint8)]),
+        "rt2_tracer_present": (i32, [vp, ctypes.POINTER(PresentParams), ctypes.POINTER(ctypes.c_uint8)]),
+        "rt2_tracer_move_camera": (i32, [vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(TemporalParams)]),
+        "rt2_tracer_present_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
+        "rt2_present_buffers": (i32, [i32, i32, i32, fp, ctypes.POINTER(ctypes.c_uint8)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

@@ -535,6 +535,8 @@ rt2_tracer::~rt2_tracer() {
   }
   if (stream) (void)hipStreamSynchronize(stream);
   for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+  if (present_e0) (void)hipEventDestroy(present_e0);
+  if (present_e1) (void)hipEventDestroy(present_e1);
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
   FreeFrame(this);

@@ -1,5 +1,5 @@
-// capi_filter.cpp — the feature buffers, the denoiser and temporal reuse of include/rt2.h (over render.hip's feature
-// pass, denoise.hip and temporal.hip).
+// capi_filter.cpp — the feature buffers, the denoiser, temporal reuse and the presenting calls of include/rt2.h
+// (over render.hip's feature pass, denoise.hip, temporal.hip and present.hip).
 #include <hip/hip_runtime_api.h>
 
 #include <cstdlib>
@@ -48,8 +48,9 @@ static double EventMs(const EventPair& ev) {
 }
 
 // The tracer's feature records on its device, traced again when the camera, the seed, the size or the
-// partition have changed since (Realloc drops the buffer). ev: events recorded around the pass.
-static int EnsureFeatures(rt2_tracer* t, bool* launched, const EventPair& ev) {
+// partition have changed since (Realloc drops the buffer). ev: events recorded around the pass, or null. Enqueued
+// on the tracer's stream; the host does not wait.
+static int EnsureFeatures(rt2_tracer* t, bool* launched, const EventPair* ev) {
   *launched = false;
   if (!t->stack_ok)
     return Fail(RT2_ERR_INVALID, "features: the scene needs a traversal stack of " + std::to_string(t->max_stack) +
@@ -69,9 +70,9 @@ static int EnsureFeatures(rt2_tracer* t, bool* launched, const EventPair& ev) {
   RenderParams p;
   BaseParams(t, cam, &p);
   p.local_pixels = (uint32_t)n;
-  HIP_TRY(hipEventRecord(ev.e0, t->stream));
+  if (ev) HIP_TRY(hipEventRecord(ev->e0, t->stream));
   HIP_TRY(LaunchFeatures(p, t->d_features.get<float>(), t->stream));
-  HIP_TRY(hipEventRecord(ev.e1, t->stream));
+  if (ev) HIP_TRY(hipEventRecord(ev->e1, t->stream));
   t->features_valid = true;
   t->features_cam = cam;
   t->features_seed = t->seed;
@@ -83,7 +84,7 @@ static int FeaturesTimed(rt2_tracer* t) {
   EventPair ev(t);
   if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
   bool launched = false;
-  int rc = EnsureFeatures(t, &launched, ev);
+  int rc = EnsureFeatures(t, &launched, &ev);
   if (rc != RT2_OK || !launched) return rc;
   hipError_t e = hipStreamSynchronize(t->stream);
   t->host_waits++;
@@ -214,6 +215,8 @@ static int TemporalParamsOf(const rt2_temporal_params* p, TemporalParams* k) {
   return RT2_OK;
 }
 
+static int EnqueueBlend(rt2_tracer* t, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev);
+
 // The blend of the tracer's current estimate with its history, left on the device: colour and variance at
 // the head of the denoise scratch (where LaunchDenoise takes them), the length in d_tp_len. The checks of
 // rt2_tracer_denoise; push: the result then replaces the history. ev (or null): takes its two events from the
@@ -230,8 +233,17 @@ static int TemporalBlend(rt2_tracer* t, const rt2_temporal_params* params, bool 
   if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
   const size_t n = (size_t)t->width * (size_t)t->local_rows;
   if (n == 0) return RT2_OK;
+  return EnqueueBlend(t, k, with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float), push, ev);
+}
+
+// TemporalBlend's kernels, enqueued on the tracer's stream over a tracer that has passed its checks, with its
+// frames launched and its features current; n > 0. The host does not wait. scratch_bytes: what the denoise
+// scratch must hold at least.
+static int EnqueueBlend(rt2_tracer* t, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev) {
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  int rc;
   HIP_TRY(hipSetDevice(t->device));
-  if ((rc = EnsureScratch(t, with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float))) != RT2_OK) return rc;
+  if ((rc = EnsureScratch(t, scratch_bytes)) != RT2_OK) return rc;
   if (!t->d_tp_hist) {
     t->tp_valid = false;
     HIP_TRY(t->d_tp_hist.Alloc(TemporalHistoryBytes(n)));
@@ -386,6 +398,132 @@ int rt2_temporal_buffers(int device, int width, int height, const float* color, 
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (stream) (void)hipStreamDestroy(stream);
   if (e != hipSuccess) return HipFail(e, "temporal_buffers");
+  return RT2_OK;
+}
+
+// ---- presenting reconstructed frames (rt2.h "Presenting reconstructed frames") ----
+void rt2_present_defaults(rt2_present_params* out) {
+  if (!out) return;
+  out->temporal = 1;
+  out->denoise = 1;
+  rt2_temporal_defaults(&out->tp);
+  rt2_denoise_defaults(&out->dp);
+}
+
+static const char kPresentTracerMsg[] = "present: needs an unpartitioned one-GPU tracer (world 1, not joined)";
+
+// The chain of rt2.h, enqueued on the tracer's stream; every refusal comes before the first enqueue. Nothing
+// here blocks the host: no stream or event synchronisation, no synchronous copy (growing a buffer at the first
+// call is the exception every first call has).
+int rt2_tracer_present_async(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
+  if (!t || !out_rgba) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || t->comm || t->world != 1) return Fail(RT2_ERR_INVALID, kPresentTracerMsg);
+  const bool temporal = params ? params->temporal != 0 : true;
+  const bool denoise = params ? params->denoise != 0 : true;
+  TemporalParams tk = TemporalDefaults();
+  DenoiseParams dk = DenoiseDefaults();
+  int rc;
+  if (temporal && (rc = TemporalParamsOf(params ? &params->tp : nullptr, &tk)) != RT2_OK) return rc;
+  if (denoise && (rc = DenoiseParamsOf(params ? &params->dp : nullptr, &dk)) != RT2_OK) return rc;
+  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "present: moments not enabled (rt2_tracer_enable_moments)");
+  if (t->frame_idx + t->queued < 2) return Fail(RT2_ERR_INVALID, "present needs at least 2 frames");
+  if ((rc = Flush(t)) != RT2_OK) return rc;
+  bool launched = false;
+  if ((rc = EnsureFeatures(t, &launched, nullptr)) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  // colour float3 and variance at the scratch's head, as the filter takes them; the RGBA8 words behind them, in
+  // the filter's first plane, which is free again once the filter's last kernel (unpack) has run
+  const size_t need = denoise ? DenoiseScratchBytes(n) : n * 5 * sizeof(float);
+  if ((rc = EnsureScratch(t, need)) != RT2_OK) return rc;
+  if (!t->present_e0 && hipEventCreate(&t->present_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  if (!t->present_e1 && hipEventCreate(&t->present_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  t->present_pending = false;
+  t->present_ms = -1.0;
+  HIP_TRY(hipEventRecord(t->present_e0, t->stream));
+  if (temporal) {
+    if ((rc = EnqueueBlend(t, tk, need, false, nullptr)) != RT2_OK) return rc;
+  } else {
+    HIP_TRY(LaunchDenoiseInputs(t->d_accum.get<float>(), t->d_moment2.get<float>(),
+                                t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr, t->d_dn_scratch.get<float>(),
+                                (uint32_t)n, t->frame_idx, t->stream));
+  }
+  float* d_color = t->d_dn_scratch.get<float>();
+  uint8_t* d_rgba = reinterpret_cast<uint8_t*>(d_color + 4 * n);
+  if (denoise) HIP_TRY(LaunchDenoise(d_color, t->d_features.get<float>(), t->width, t->local_rows, dk, DenoiseLds(), t->stream));
+  HIP_TRY(LaunchPresent(d_color, d_rgba, (uint32_t)n, t->stream));
+  HIP_TRY(hipEventRecord(t->present_e1, t->stream));
+  t->present_pending = true;
+  HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, n * 4, hipMemcpyDeviceToHost, t->stream));
+  return RT2_OK;
+}
+
+int rt2_tracer_present(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
+  int rc = rt2_tracer_present_async(t, params, out_rgba);
+  return rc != RT2_OK ? rc : Sync(t);
+}
+
+int rt2_tracer_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, const rt2_temporal_params* params) {
+  if (!t || !cam) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || t->comm) return Fail(RT2_ERR_INVALID, "move_camera: not on a multi-GPU or joined tracer");
+  TemporalParams k;
+  int rc = TemporalParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (t->world == 1 && t->moments_on && t->frame_idx + t->queued >= 2 && n > 0) {
+    // the push of rt2_tracer_temporal_push without its wait: blend and pack are on the tracer's stream, and so
+    // is every memset of ResetFrame below, so the sums are zeroed after the pack's inputs kernel has read them
+    if ((rc = Flush(t)) != RT2_OK) return rc;
+    bool launched = false;
+    if ((rc = EnsureFeatures(t, &launched, nullptr)) != RT2_OK) return rc;
+    if ((rc = EnqueueBlend(t, k, n * 4 * sizeof(float), true, nullptr)) != RT2_OK) return rc;
+    CameraWords(t->camera.Params(), t->tp_cam);
+    t->tp_valid = true;
+  }
+  if ((rc = rt2_tracer_set_camera(t, cam)) != RT2_OK) return rc;
+  return rt2_tracer_reset(t);
+}
+
+int rt2_tracer_present_time(rt2_tracer* t, double* ms) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t) || t->comm || t->world != 1) return Fail(RT2_ERR_INVALID, kPresentTracerMsg);
+  if (t->present_pending) {
+    HIP_TRY(hipSetDevice(t->device));
+    const hipError_t q = hipEventQuery(t->present_e1);
+    if (q == hipSuccess) {
+      float f = -1.0f;
+      if (hipEventElapsedTime(&f, t->present_e0, t->present_e1) != hipSuccess) f = -1.0f;
+      t->present_ms = (double)f;
+      t->present_pending = false;
+    } else if (q != hipErrorNotReady) {
+      return HipFail(q, "present_time");
+    }
+  }
+  if (ms) *ms = t->present_pending ? -1.0 : t->present_ms;
+  return RT2_OK;
+}
+
+int rt2_present_buffers(int device, int width, int height, const float* color, uint8_t* out_rgba) {
+  if (!color || !out_rgba) return Fail(RT2_ERR_INVALID, "null argument");
+  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
+    return Fail(RT2_ERR_INVALID, "present_buffers: need width, height > 0 and width * height below 2^26");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
+  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  const size_t n = (size_t)width * (size_t)height;
+  DeviceBuffer col, px;  // (freed in the reverse order)
+  hipStream_t stream = nullptr;
+  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = col.Alloc(n * 3 * sizeof(float));
+  if (e == hipSuccess) e = px.Alloc(n * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(col.get<float>(), color, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = LaunchPresent(col.get<float>(), px.get<void>(), (uint32_t)n, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, px.get<uint8_t>(), n * 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (e != hipSuccess) return HipFail(e, "present_buffers");
   return RT2_OK;
 }
 }  // extern "C"

@@ -1,5 +1,5 @@
-// kernels.h — the host-callable functions the six .hip files define (render, gather, noise, adaptive,
-// denoise, temporal): kernel launchers and the small queries beside them. Included by the host side and
+// kernels.h — the host-callable functions the seven .hip files define (render, gather, noise, adaptive,
+// denoise, temporal, present): kernel launchers and the small queries beside them. Included by the host side and
 // by every .hip file, so the compiler checks each definition against the one declaration here.
 #pragma once
 
@@ -59,4 +59,6 @@ hipError_t LaunchTemporalBlend(float* color, float* variance, const float* lengt
                                const float* features, const void* hist, const float* camera, const float* materials,
                                int n_materials, bool type_bits, const TemporalParams& k, float* out_length, int width,
                                int height, hipStream_t stream);
+// present.hip
+hipError_t LaunchPresent(const float* color, void* rgba, uint32_t npix, hipStream_t stream);
 }  // namespace rt2

@@ -203,6 +203,12 @@ struct rt2_tracer {
   float tp_cam[rt2::kTemporalCameraWords] = {};
   int n_materials = 0;  // materials in d_materials
   double temporal_ms = -1.0;
+  // presenting (rt2.h "Presenting reconstructed frames"): the events around the last present's kernels (created
+  // at the first present, re-recorded by every later one), whether that present's time is still to be read from
+  // them (rt2_tracer_present_time polls, never waits), and the last time read (-1: none)
+  hipEvent_t present_e0 = nullptr, present_e1 = nullptr;
+  bool present_pending = false;
+  double present_ms = -1.0;
   rt2::DeviceBuffer d_work;  // one work counter per launch slot (words 0 and 16)
   rt2::DeviceBuffer d_stats;
   bool stats_on = false;

@@ -44,12 +44,19 @@ class PinnedBuffer:
 class ProgressiveLoop:
     """Ticks of `frames_per_tick` frames, adapted so that a tick takes about `budget_ms`. With
     `target_rms` (the tracer must have moments enabled) every tick also takes the noise estimate
-    (`self.noise`, RayTracer.noise), and the loop is done once its rms is at most the target."""
+    (`self.noise`, RayTracer.noise), and the loop is done once its rms is at most the target. With
+    `reconstruct` (a dict of RayTracer.present's keyword arguments, {} = its defaults; the tracer must
+    have moments enabled) a tick shows the reconstructed frame (rt2_tracer_present_async) once two
+    frames are done, and Pixels() before that; `move(cam)` moves the camera and keeps the history."""
 
     def __init__(self, tracer, total_frames: int, budget_ms: float = 16.0, first_frames: int = 1,
-                 max_frames_per_tick: int = 4096, target_rms: Optional[float] = None):
+                 max_frames_per_tick: int = 4096, target_rms: Optional[float] = None,
+                 reconstruct: Optional[dict] = None):
         if target_rms is not None and not getattr(tracer, "_moments", False):
             raise ValueError("ProgressiveLoop: target_rms needs tracer.enable_moments()")
+        if reconstruct is not None and not getattr(tracer, "_moments", False):
+            raise ValueError("ProgressiveLoop: reconstruct needs tracer.enable_moments()")
+        self.reconstruct = None if reconstruct is None else dict(reconstruct)
         self.target_rms = None if target_rms is None else float(target_rms)
         self.noise: Optional[dict] = None
         self.converged = False
@@ -58,7 +65,8 @@ class ProgressiveLoop:
         self.pixels = PinnedBuffer((tracer.local_rows(), w, 4))
         self.total = int(total_frames)
         self.budget = float(budget_ms)
-        self.n = max(1, int(first_frames))
+        self.first = max(1, int(first_frames))
+        self.n = self.first
         self.cap = int(max_frames_per_tick)
         self.ticks = 0
         self.frames_done = 0
@@ -73,8 +81,11 @@ class ProgressiveLoop:
         n = min(self.n, self.total - self.frames_done)
         t0 = time.perf_counter()
         self.tr.Render(n)
-        check(lib.rt2_tracer_pixels_async(self.tr._h, self.pixels.array.ctypes.data_as(
-            ctypes.POINTER(ctypes.c_uint8))))
+        if self.reconstruct is not None and self.tr.FrameIdx() >= 2:
+            self.tr.present_async(self.pixels.array, **self.reconstruct)
+        else:
+            check(lib.rt2_tracer_pixels_async(self.tr._h, self.pixels.array.ctypes.data_as(
+                ctypes.POINTER(ctypes.c_uint8))))
         self.tr.synchronize()
         if self.target_rms is not None and self.tr.FrameIdx() >= 2:
             self.noise = self.tr.noise(self.target_rms)
@@ -86,6 +97,14 @@ class ProgressiveLoop:
         scale = self.budget / max(dt_ms, 1e-3)
         self.n = int(max(1, min(self.cap, 2 * n, round(n * scale))))
         return self.pixels.array
+
+    def move(self, cam) -> None:
+        """Moves the camera (RayTracer.move_camera: the history is kept, the accumulation starts again)
+        and restarts the loop's frame count at `first_frames` per tick."""
+        self.tr.move_camera(cam)
+        self.frames_done = 0
+        self.converged = False
+        self.n = self.first
 
     def run(self, on_tick=None) -> None:
         while not self.done():

@@ -17,7 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._native import AppSettings as _AppSettings
-from ._native import UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Noise, SceneInfo, Stats, TemporalParams, check, lib
+from ._native import (UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Noise, PresentParams, SceneInfo, Stats,
+                      TemporalParams, check, lib)
 
 DEFAULT_SEED = 0x5EED2024
 
@@ -277,6 +278,51 @@ def temporal_buffers(color, variance, length, features, hist_color, hist_varianc
                                    _fp(mats) if n_mats else None, n_mats, _temporal_params(params), _fp(out), _fp(var),
                                    _fp(ln)))
     return out, var, ln
+
+
+def present_defaults() -> dict:
+    """rt2_present_defaults as a dict: temporal, denoise, tp (temporal_defaults()), dp (denoise_defaults())."""
+    p = PresentParams()
+    lib.rt2_present_defaults(ctypes.byref(p))
+    return p.as_dict()
+
+
+def _present_params(params: dict):
+    """A rt2_present_params pointer for the keyword arguments of RayTracer.present (None = NULL: the defaults):
+    temporal, denoise (switches) and tp, dp (dicts of the rt2_temporal_params / rt2_denoise_params fields that
+    differ from the defaults)."""
+    if not params:
+        return None
+    p = PresentParams()
+    lib.rt2_present_defaults(ctypes.byref(p))
+    for k, v in params.items():
+        if k in ("temporal", "denoise"):
+            setattr(p, k, 1 if v else 0)
+        elif k == "tp":
+            for f, x in (v or {}).items():
+                if f not in dict(TemporalParams._fields_):
+                    raise TypeError(f"present: unknown temporal parameter {f!r}")
+                setattr(p.tp, f, float(x))
+        elif k == "dp":
+            for f, x in (v or {}).items():
+                if f not in dict(DenoiseParams._fields_):
+                    raise TypeError(f"present: unknown denoise parameter {f!r}")
+                setattr(p.dp, f, int(x) if f in ("iterations", "normal_power_log2") else float(x))
+        else:
+            raise TypeError(f"present: unknown parameter {k!r}")
+    return ctypes.byref(p)
+
+
+def present_buffers(color, device: int = 0) -> np.ndarray:
+    """rt2_present_buffers: the tone map of present() over a caller image, color (H, W, 3) float32, on `device`.
+    Returns (H, W, 4) uint8."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise ValueError("present_buffers: need color (H, W, 3)")
+    h, w = color.shape[:2]
+    out = np.zeros((h, w, 4), np.uint8)
+    check(lib.rt2_present_buffers(int(device), w, h, _fp(color), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+    return out
 
 
 class RayTracer:
@@ -599,6 +645,43 @@ class RayTracer:
         """GPU ms of the last temporal_resolve's temporal kernels (-1: none yet)."""
         ms = ctypes.c_double(-1.0)
         check(lib.rt2_tracer_temporal_time(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    # -- presenting reconstructed frames (rt2.h "Presenting reconstructed frames") ---------------
+    def present(self, **params) -> np.ndarray:
+        """The reconstructed frame as RGBA8, (H, W, 4) uint8: the estimate blended with the history (temporal,
+        default on), filtered (denoise, default on) and tone-mapped like Pixels(). Needs what temporal_resolve()
+        needs. params: temporal, denoise (switches), tp, dp (dicts of temporal / denoise parameter fields).
+        Changes nothing."""
+        self._push_camera()
+        w, _ = self.Dims()
+        out = np.zeros((max(self.local_rows(), 0), w, 4), np.uint8)
+        check(lib.rt2_tracer_present(self._h, _present_params(params), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return out
+
+    def present_async(self, pinned_array: np.ndarray, **params) -> None:
+        """present() enqueued into `pinned_array` ((H, W, 4) uint8 of a progressive.PinnedBuffer), returning at
+        once: the bytes are complete after synchronize() or once query() returns 1."""
+        w, _ = self.Dims()
+        a = pinned_array
+        if a.dtype != np.uint8 or not a.flags["C_CONTIGUOUS"] or a.nbytes != max(self.local_rows(), 0) * w * 4:
+            raise ValueError("present_async: need a C-contiguous uint8 array of H * W * 4 bytes")
+        self._push_camera()
+        check(lib.rt2_tracer_present_async(self._h, _present_params(params), a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+
+    def move_camera(self, cam: Camera, **temporal_params) -> None:
+        """temporal_push(), set_camera(cam) and Reset() in one call that does not wait for the GPU: the history is
+        kept across the move (with moments off or fewer than 2 frames it is set_camera + Reset). The history is
+        taken under the camera of the last Render(); `self.camera`, when set, becomes `cam`."""
+        d = cam._desc()
+        check(lib.rt2_tracer_move_camera(self._h, ctypes.byref(d), _temporal_params(temporal_params)))
+        if self.camera is not None:
+            self.camera = cam
+
+    def present_time(self) -> float:
+        """GPU ms of the last present's kernels (-1: not finished yet, or none). Never waits."""
+        ms = ctypes.c_double(-1.0)
+        check(lib.rt2_tracer_present_time(self._h, ctypes.byref(ms)))
         return ms.value
 
     def enable_stats(self, on: bool = True) -> None:
