@@ -1153,7 +1153,8 @@ bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool
   // Flat program (rt2_layout.h): the BVH program's leaf steps in their order, without its kBvh steps; quad
   // runs formed again over the new adjacency (a MakeBox run still exactly its six faces, flagged); the
   // certificate box of each leaf = its parent BVH node's record, bit for bit, in the kXform step's wide
-  // entry and in the certificate table at each world-space quad's record offset.
+  // entry and in the certificate table at each quad's record offset (a quad under a transform: its
+  // transform's box, flagged).
   if (flat && !out.lin.empty()) {
     const size_t n = out.lin.size() / 4;
     std::vector<uint32_t> fmap(n + 1, 0), flin;
@@ -1210,6 +1211,7 @@ bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool
       out.flat_wide.assign(16 * (m + 1), 0u);
       out.flat_wide[16 * m] = kProgramEnd;
       out.flat_cert.assign(out.lind.size(), 0.0f);
+      const uint32_t* xbox = nullptr;  // wide entry of the transform step last entered (under[j]: the one j lies in)
       for (size_t j = 0; j < m; j++) {
         uint32_t* w = &out.flat_wide[16 * j];
         for (int k = 0; k < 4; k++) w[k] = flin[4 * j + k];
@@ -1218,13 +1220,17 @@ bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool
         if (flin[4 * j] == kXform) {
           memcpy(&w[4], &box[0], 12);
           memcpy(&w[7], &box[4], 12);
+          xbox = w;
         } else {
           for (size_t k = 0; k < 12 && rec + k < out.lind.size(); k++) memcpy(&w[4 + k], &out.lind[rec + k], 4);
         }
         if (flin[4 * j] == kQuad) {
           float* c = &out.flat_cert[rec];
           if (under[j]) {
+            // its transform's certificate box, bit for bit words 4-9 of that step's wide entry, and the flag
             const uint32_t f = kFlatCertXform;
+            memcpy(&c[0], &xbox[4], 12);
+            memcpy(&c[4], &xbox[7], 12);
             memcpy(&c[3], &f, 4);
           } else {
             memcpy(&c[0], &box[0], 12);

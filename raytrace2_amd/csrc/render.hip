@@ -57,7 +57,7 @@ constexpr int kBlock = 256;
                          // queries, 256 a Philox block (at every refill), 512 the sample store /
                          // staging, 2048 a threaded transform entry (ray into model space, its reciprocal),
                          // 4096 an accelerated list's lane walk, 8192 the box-level test of a MakeBox run,
-                         // 16384 the flat walk's certificate rule (each entry rule and the end rule)
+                         // 16384 the flat walk's certificate rule (the one evaluation after the walk)
 #endif
 #ifndef RT2_EXP_WAVESTEPS
 #define RT2_EXP_WAVESTEPS 0  // diagnostic build: per-wave linear-traversal step counts into diag slots
@@ -1571,9 +1571,10 @@ constexpr bool BoxOn() {
 // kFlat (the kernels with kFeatFlat): the walk of the launch's flat program (rt2_layout.h "Flat program":
 // no kBvh steps, so no slab test, no next-index search between leaves) with the certificate of DESIGN.md §4
 // "Flat walk of small BVHs": `uncert` returns whether this lane's hit is not proven to be the hit of the
-// BVH program's walk (the caller then traces that program for the lane). Entry rule at every kXform step
-// (the step's certificate box, the world ray, the lane's tmax there); end rule for a winner in world space
-// (its certificate box from the table, T = its t).
+// BVH program's walk (the caller then traces that program for the lane). One rule per trace, after the walk,
+// on the winner's certificate box from the table with the world ray: for a winner under a transform the box
+// is its transform's and T = the lane's tmax at that transform's entry (the entry rule, evaluated lazily:
+// only the winner's transform's verdict is ever read); for a winner in world space T = its t (the end rule).
 template <uint32_t F, bool kStats, bool kFlat = false, class W, class G>
 __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wray, float time, G& path, HitRef& h,
                                              lds_u32* cand, lds_u32* xray, Counters& cnt, bool tab = false,
@@ -1581,8 +1582,8 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   const Nodes<kModeLinear> N{reinterpret_cast<const float4*>(P.lind)};  // boundaries / nested xforms
   const void* recs = P.lind;
   const void* prog = kFlat ? P.flat_wide : P.lin_wide;
-  bool xfail = false;  // kFlat: the entry rule failed at the transform the lane is in
-  bool xunc = false;   // kFlat: the closest hit so far under a transform was accepted after a failed entry rule
+  float t_entry = FLT_MAX;  // kFlat: the lane's tmax at the entry of the transform it is in
+  float t_keep = FLT_MAX;   // kFlat: t_entry of the transform the closest hit so far lies under
   // the world ray's reciprocal stays in registers for the transforms' exits to world space (three
   // VGPRs live across the trace), except with the parked ray (book 2), which recomputes it there
   constexpr bool kKeepW = !__is_same(W, ParkRay);
@@ -1791,18 +1792,11 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
       if (kStats) cnt.xform++;
       const u32x16 m = sld16(recs, off * 16u);  // inverse-model columns
       if constexpr (kFlat) {
-        // the entry rule on the step's certificate box (words 4-9) with the world ray (flat programs nest
-        // no transform: o, inv are the world ray's) and T = this lane's tmax here
-        const float clo[3] = {uf(sw[4]), uf(sw[5]), uf(sw[6])}, chi[3] = {uf(sw[7]), uf(sw[8]), uf(sw[9])};
-        xfail = !FlatCertRule<BoxMath>(clo, chi, o.x, o.y, o.z, inv.x, inv.y, inv.z, tmin, tmax);
-#if RT2_EXP_TWICE & 16384
-        {
-          float ox2 = o.x;
-          asm volatile("" : "+v"(ox2));
-          const bool r2 = FlatCertRule<BoxMath>(clo, chi, ox2, o.y, o.z, inv.x, inv.y, inv.z, tmin, tmax);
-          asm volatile("" ::"v"((int)r2));
-        }
-#endif
+        // the entry rule's T = this lane's tmax here. The rule itself (the step's certificate box, which the
+        // table repeats in the rows of the quads under this transform, and the world ray: flat programs nest
+        // no transform) waits for the end of the walk, where it runs only for a winner under this transform;
+        // a flat program enters a transform once per trace, so one t_entry suffices
+        t_entry = tmax;
       }
       f3 no, nd;
       if (m[11] == kXformYAxis) {
@@ -1852,7 +1846,7 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
         pk_st3(xray, 3u, d);
         // (kFlat kernels keep the model-space ray, so this is every hit under the transform; a transform is
         // entered once per trace, so the hit is this visit's)
-        if constexpr (kFlat) xunc = xfail;
+        if constexpr (kFlat) t_keep = t_entry;
       }
       cur_xf = st.w;
       if (cur_xf == kRefNone) {
@@ -1992,24 +1986,26 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   h.prim = prim;
   if constexpr (kFlat) {
     // The certificate. No hit here is no hit there. A hit needs the world ray's reciprocal finite, and the
-    // winner's certificate (rt2_layout.h: the table has the shape of lind): under a transform, that its
-    // entry rule passed; in world space, the end rule on its box with T = its t.
+    // winner's certificate (rt2_layout.h: the table has the shape of lind): the rule on its row's box with the
+    // world ray; under a transform the box is the transform's and T = the lane's tmax at its entry (the entry
+    // rule with the inputs it has there), in world space T = the winner's t (the end rule).
     bool u = false;
     if (prim != kRefNone) {
       const float4* ct = reinterpret_cast<const float4*>(P.flat_cert) + (prim & kOffsetMask);
       const float4 c0 = ct[0], c1 = ct[1];
       const float clo[3] = {c0.x, c0.y, c0.z}, chi[3] = {c1.x, c1.y, c1.z};
-      const bool end_ok = FlatCertRule<BoxMath>(clo, chi, wray.wo().x, wray.wo().y, wray.wo().z, winv.x, winv.y,
-                                                winv.z, tmin, tmax);
+      const float T = bits(c0.w) == kFlatCertXform ? t_keep : tmax;
+      const bool rule = FlatCertRule<BoxMath>(clo, chi, wray.wo().x, wray.wo().y, wray.wo().z, winv.x, winv.y,
+                                              winv.z, tmin, T);
 #if RT2_EXP_TWICE & 16384
       {
         float ox2 = wray.wo().x;
         asm volatile("" : "+v"(ox2));
-        const bool r2 = FlatCertRule<BoxMath>(clo, chi, ox2, wray.wo().y, wray.wo().z, winv.x, winv.y, winv.z, tmin, tmax);
+        const bool r2 = FlatCertRule<BoxMath>(clo, chi, ox2, wray.wo().y, wray.wo().z, winv.x, winv.y, winv.z, tmin, T);
         asm volatile("" ::"v"((int)r2));
       }
 #endif
-      u = !wfin || P.flat_mode == kFlatCertifyNothing || (bits(c0.w) == kFlatCertXform ? xunc : !end_ok);
+      u = !wfin || P.flat_mode == kFlatCertifyNothing || !rule;
     }
     *uncert = u;
   }

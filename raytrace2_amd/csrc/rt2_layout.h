@@ -230,10 +230,11 @@ constexpr int kLinearMaxXformDepth = 8;  // deeper transform nesting uses the st
 // would have culled nothing the lane's answer depends on, and the lanes it cannot certify trace the BVH
 // program again. Certificate boxes are bit copies of each leaf's parent BVH node's bounds:
 //   kXform step: words 4-9 of its wide entry (lo.xyz, hi.xyz) instead of the record's first words (the
-//     step loads its record itself)
+//     step loads its record itself; the kernel reads the box from the table, the host checks read it here)
 //   quads: the certificate table (CompiledScene::flat_cert, RenderParams::flat_cert), which has the shape
 //     of `lind`: at a quad record's offset (lo.xyz, flag bits) (hi.xyz, 0), flag = kFlatCertXform for a
-//     quad under a transform (no box: its transform's entry test decides)
+//     quad under a transform, whose box is a bit copy of its transform step's words 4-9 (that transform's
+//     entry test decides, evaluated once after the walk with the lane's tmax at the entry)
 // 8 is the headline's leaf count, the only size with a wave-step measurement behind it.
 constexpr int kFlatBvhMaxLeaves = 8;
 constexpr uint32_t kFlatCertXform = 1u;
