@@ -534,6 +534,69 @@ RT2_API int rt2_tracer_move_camera(rt2_tracer* tr, const rt2_camera_desc* cam, c
 RT2_API int rt2_tracer_present_time(rt2_tracer* tr, double* ms);
 RT2_API int rt2_present_buffers(int device, int width, int height, const float* color, uint8_t* out_rgba);
 
+/* ---- Reconstructing the gathered image ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before
+ * (rt2_tracer_gather included). The three sections above, for the image a create_multi or joined tracer gathers
+ * on rank 0: the rt2_tracer_image_* family means "of the gathered image, on its root". They also work on a plain
+ * one-GPU tracer (world 1), whose gather is a device-local copy. The calls above keep their refusals on these
+ * tracers. Every result is bit for bit what a one-GPU tracer returns from the call named beside it at the same
+ * seed, size, camera and frame count.
+ * gather_estimate: rt2_tracer_gather with the sums of squares: every rank's stack of moments travels with its
+ *   accumulation (the same RCCL group; on one GPU, copies on the root's stream, and every part's stream waits for
+ *   an event recorded after both copies), and one kernel on the root writes what gather's kernel writes
+ *   (image_accumulation, image_non_converted_pixels and image_pixels read the same bytes) and the variance of the
+ *   mean. Collective on joined tracers: every rank calls it. It enqueues and does not wait. Needs moments on on
+ *   every rank, FrameIdx() >= 2 and adaptive sampling off.
+ * image_variance: blocking readback of v = ((sem_r^2 + sem_g^2) + sem_b^2) / 3 in float32, float per image pixel:
+ *   what rt2_tracer_denoise takes from standard_error.
+ * image_features: rt2_tracer_features of the whole image, 16 floats per image pixel, traced on the root alone (the
+ *   records are not gathered: DESIGN.md §6h) and cached there per (camera, seed, size). Blocks. Needs no gather
+ *   and no moments.
+ * image_resolve: rt2_tracer_temporal_resolve and rt2_tracer_denoise in one, over c = image_non_converted_pixels and
+ *   v = image_variance: if p->temporal the blend with the root's whole-image history (none held: the current
+ *   estimate, length (float)FrameIdx()), if p->denoise the filter over the result. p NULL = the defaults (both on).
+ *   Blocks. out_variance, out_length may be NULL; out_length is the blend's length and is left untouched with
+ *   temporal = 0. The history and the estimate are unchanged.
+ * image_present_async / image_present / image_present_time: rt2_tracer_present_async, present and present_time
+ *   over the same buffers: inputs, blend, filter, tone map and the copy of 4 * width * height bytes, enqueued on
+ *   the root's stream; complete when rt2_tracer_query returns 1 or after rt2_tracer_synchronize. The async form
+ *   only enqueues, refuses before its first enqueue and adds nothing to rt2_stats.host_waits. With both stages off
+ *   the bytes are those of image_pixels.
+ * image_move_camera: rt2_tracer_move_camera: with moments on and FrameIdx() >= 2 the blend (tp, NULL = defaults)
+ *   of the current gathered estimate becomes the root's history under the camera it was rendered with; then
+ *   set_camera and reset on every part. Otherwise set_camera + reset, and a history held is kept. The host does
+ *   not wait. Collective on joined tracers: every rank calls it, a rank whose last gather_estimate is not of the
+ *   current FrameIdx() takes part in one, and ranks other than 0 then set the camera and reset.
+ * The history survives reset and set_camera; on_resize, enable_moments and set_partition drop it.
+ * When the estimate must be current: on a create_multi or plain tracer image_resolve, image_present* and
+ *   image_move_camera run gather_estimate themselves when the estimate held is not that of the current FrameIdx()
+ *   (queued frames included). On a joined tracer image_resolve and image_present* are refused unless a
+ *   gather_estimate of the current FrameIdx() has been enqueued (the other ranks are not in this process).
+ * deinterleave_estimate_host: the CPU statement of gather_estimate's kernel, beside rt2_deinterleave_host: the
+ *   rank-major stacks [world][rt2_band_rows_max][width][3] of the sums and of the sums of squares -> the image-order
+ *   sums `image`, the means `image_nc` = sum / (float)frames (float3 each) and `variance` (float). No GPU needed.
+ * RT2_ERR_INVALID: a NULL tracer, camera or output (out_variance, out_length excepted); a readback, resolve,
+ *   present or present_time on a rank other than 0; gather_estimate (and the calls that run it) with moments off,
+ *   fewer than 2 frames, adaptive sampling on, on a set_partition tracer (world > 1) that is not joined, or with
+ *   ranks that disagree on dims or frame index; image_variance before any gather_estimate; image_resolve /
+ *   image_present* on a joined tracer without a gather_estimate of the current FrameIdx(); invalid temporal or
+ *   denoise parameters, checked only for the stages switched on (image_move_camera: its temporal parameters);
+ *   image_features, resolve, present and a pushing move_camera on a scene only the threaded traversal can render;
+ *   image_move_camera with adaptive sampling on or on an unjoined partition; deinterleave_estimate_host with a
+ *   NULL argument, a negative size, world < 1 or frames outside [2, 2^31). A refused call changes nothing. */
+RT2_API int rt2_tracer_gather_estimate(rt2_tracer* tr);
+RT2_API int rt2_tracer_image_variance(rt2_tracer* tr, float* out);  /* float per image pixel */
+RT2_API int rt2_tracer_image_features(rt2_tracer* tr, float* out);  /* 16 floats per image pixel */
+RT2_API int rt2_tracer_image_resolve(rt2_tracer* tr, const rt2_present_params* p, float* out_color,
+                                     float* out_variance /* may be NULL */, float* out_length /* may be NULL */);
+RT2_API int rt2_tracer_image_present_async(rt2_tracer* tr, const rt2_present_params* p, uint8_t* out_rgba);
+RT2_API int rt2_tracer_image_present(rt2_tracer* tr, const rt2_present_params* p, uint8_t* out_rgba);
+RT2_API int rt2_tracer_image_move_camera(rt2_tracer* tr, const rt2_camera_desc* cam, const rt2_temporal_params* tp);
+RT2_API int rt2_tracer_image_present_time(rt2_tracer* tr, double* ms);
+RT2_API int rt2_deinterleave_estimate_host(const float* stacks, const float* stacks2, float* image, float* image_nc,
+                                           float* variance, int width, int height, int band_h, int world,
+                                           int64_t frames);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -347,6 +347,62 @@ class RayTracer {
     Check(rt2_tracer_present_time(t_.get(), &ms));
     return ms;
   }
+  // Reconstructing the gathered image (rt2.h "Reconstructing the gathered image"): the three groups above for a
+  // tracer over several GPUs (n_gpus >= 1) or a joined one, where the members above are refused; vectors hold the
+  // whole image, Dims().x * Dims().y pixels, on rank 0. GatherEstimate gathers the sums and the sums of squares
+  // (needs EnableMoments, FrameIdx() >= 2) and does not wait; ImageResolve, ImagePresent* and ImageMoveCamera run
+  // it themselves when the estimate held is not the current frame's (a joined tracer must have called it).
+  // ImageResolve is TemporalResolve and Denoise in one (params null: both stages on, at their defaults).
+  void GatherEstimate() {
+    Sync();
+    Check(rt2_tracer_gather_estimate(t_.get()));
+  }
+  [[nodiscard]] std::vector<float> ImageVariance() {
+    std::vector<float> out(ImagePixels());
+    Check(rt2_tracer_image_variance(t_.get(), out.data()));
+    return out;
+  }
+  [[nodiscard]] std::vector<float> ImageFeatures() {
+    Sync();
+    std::vector<float> out(ImagePixels() * 16);
+    Check(rt2_tracer_image_features(t_.get(), out.data()));
+    return out;
+  }
+  [[nodiscard]] std::vector<vec3> ImageResolve(const rt2_present_params* params = nullptr,
+                                               std::vector<float>* variance = nullptr,
+                                               std::vector<float>* length = nullptr) {
+    Sync();
+    std::vector<vec3> out(ImagePixels());
+    if (variance) variance->assign(out.size(), 0.0f);
+    if (length) length->assign(out.size(), 0.0f);
+    Check(rt2_tracer_image_resolve(t_.get(), params, reinterpret_cast<float*>(out.data()),
+                                   variance ? variance->data() : nullptr, length ? length->data() : nullptr));
+    return out;
+  }
+  void ImagePresentAsync(u8vec4* out, const rt2_present_params* params = nullptr) {
+    Sync();
+    Check(rt2_tracer_image_present_async(t_.get(), params, reinterpret_cast<uint8_t*>(out)));
+  }
+  [[nodiscard]] const PixelArray& ImagePresent(const rt2_present_params* params = nullptr) {
+    Sync();
+    pixels_.resize(ImagePixels());
+    Check(rt2_tracer_image_present(t_.get(), params, reinterpret_cast<uint8_t*>(pixels_.data())));
+    return pixels_;
+  }
+  void ImageMoveCamera(const Camera& to, const rt2_temporal_params* params = nullptr) {
+    const rt2_camera_desc d = to.Desc();
+    Check(rt2_tracer_image_move_camera(t_.get(), &d, params));
+    if (camera && camera != &to) {
+      const int spp = camera->samples_per_pixel_;
+      *camera = to;
+      camera->samples_per_pixel_ = spp;
+    }
+  }
+  [[nodiscard]] double ImagePresentTime() {  // GPU ms of the last image present's kernels; -1: not finished, or none
+    double ms = -1.0;
+    Check(rt2_tracer_image_present_time(t_.get(), &ms));
+    return ms;
+  }
   [[nodiscard]] bool Query() {
     const int q = rt2_tracer_query(t_.get());
     Check(q);
@@ -373,6 +429,7 @@ class RayTracer {
   ivec2 dims_;
   mutable PixelArray pixels_;
   int LocalRows() const { return rt2_tracer_local_rows(t_.get()); }
+  size_t ImagePixels() const { return (size_t)dims_.x * (size_t)dims_.y; }
 };
 
 }  // namespace rt2

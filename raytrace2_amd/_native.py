@@ -252,6 +252,15 @@ def _load():
         "rt2_tracer_move_camera": (i32, [vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(TemporalParams)]),
         "rt2_tracer_present_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
         "rt2_present_buffers": (i32, [i32, i32, i32, fp, ctypes.POINTER(ctypes.c_uint8)]),
+        "rt2_tracer_gather_estimate": (i32, [vp]),
+        "rt2_tracer_image_variance": (i32, [vp, fp]),
+        "rt2_tracer_image_features": (i32, [vp, fp]),
+        "rt2_tracer_image_resolve": (i32, [vp, ctypes.POINTER(PresentParams), fp, fp, fp]),
+        "rt2_tracer_image_present_async": (i32, [vp, ctypes.POINTER(PresentParams), ctypes.POINTER(ctypes.c_uint8)]),
+        "rt2_tracer_image_present": (i32, [vp, ctypes.POINTER(PresentParams), ctypes.POINTER(ctypes.c_uint8)]),
+        "rt2_tracer_image_move_camera": (i32, [vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(TemporalParams)]),
+        "rt2_tracer_image_present_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
+        "rt2_deinterleave_estimate_host": (i32, [fp, fp, fp, fp, fp, i32, i32, i32, i32, i64]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

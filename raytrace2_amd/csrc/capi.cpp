@@ -53,6 +53,16 @@ void FreeImage(rt2_tracer* t) {
   t->d_image_nc.reset();
   t->d_image_px.reset();
   t->image_frame = -1;
+  // the gathered image's reconstruction (capi_multi.cpp, capi_filter.cpp): the history goes with the image
+  t->d_stacks2.reset();
+  t->d_image_var.reset();
+  t->estimate_frame = -1;
+  t->d_img_features.reset();
+  t->img_features_valid = false;
+  t->d_img_scratch.reset();
+  t->d_img_hist.reset();
+  t->d_img_len.reset();
+  t->img_tp_valid = false;
 }
 
 static void FreeFrame(rt2_tracer* t) {
@@ -103,7 +113,8 @@ static size_t DeviceBytes(const rt2_tracer* t) {
         &t->d_lind, &t->d_hit, &t->d_flat_wide, &t->d_flat_cert, &t->d_work, &t->d_clock, &t->d_stats, &t->d_accum,
         &t->d_pixels, &t->d_ray_counts, &t->d_moment2, &t->d_noise, &t->d_counts, &t->d_active, &t->d_over, &t->d_list,
         &t->d_slot_of, &t->d_ad_scratch, &t->d_features, &t->d_dn_scratch, &t->d_tp_hist, &t->d_tp_len, &t->d_stacks,
-        &t->d_image, &t->d_image_nc, &t->d_image_px})
+        &t->d_image, &t->d_image_nc, &t->d_image_px, &t->d_stacks2, &t->d_image_var, &t->d_img_features,
+        &t->d_img_scratch, &t->d_img_hist, &t->d_img_len})
     b += d->bytes();
   for (const auto& sl : t->slots) b += sl.samples.bytes() + sl.chunks.bytes();
   return b;
@@ -139,6 +150,7 @@ int ResetFrame(rt2_tracer* t) {
   t->frame_idx = 0;
   t->queued = 0;  // queued frames would only be accumulated and zeroed again
   t->image_frame = -1;
+  t->estimate_frame = -1;
   t->n_active = (uint32_t)((size_t)t->width * (size_t)t->local_rows);  // adaptive: every pixel active again
   if (n == 0) return RT2_OK;
   HIP_TRY(hipSetDevice(t->device));
@@ -537,6 +549,8 @@ rt2_tracer::~rt2_tracer() {
   for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
   if (present_e0) (void)hipEventDestroy(present_e0);
   if (present_e1) (void)hipEventDestroy(present_e1);
+  if (img_present_e0) (void)hipEventDestroy(img_present_e0);
+  if (img_present_e1) (void)hipEventDestroy(img_present_e1);
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
   FreeFrame(this);

@@ -47,14 +47,58 @@ static double EventMs(const EventPair& ev) {
   return (double)ms;
 }
 
+// What the reconstruction chain (inputs, temporal blend, filter, tone map) runs over: a one-GPU tracer's local
+// image, or the gathered image on its root (rt2.h "Reconstructing the gathered image"). The kernels take
+// pointers and dimensions, so the two differ only in where the estimate comes from and which of the tracer's
+// buffers hold the scratch and the history.
+struct Chain {
+  rt2_tracer* t;  // device, stream, material table, event pool
+  int width, rows;
+  // the estimate: the sums (LaunchDenoiseInputs divides and takes the variance), or with accum null the
+  // resolved colour and variance of the mean (the gather's kernel has done both; they are copied)
+  const float *accum, *moment2;
+  const uint32_t* counts;
+  const float *color, *variance;
+  int64_t frames;
+  const float* features;  // current, 16 floats per pixel
+  DeviceBuffer *scratch, *hist, *len;
+  bool* tp_valid;
+  float* tp_cam;
+  // the events around the last present's kernels and its time (rt2_tracer_present_time)
+  hipEvent_t *present_e0, *present_e1;
+  bool* present_pending;
+  double* present_ms;
+  size_t n() const { return (size_t)width * (size_t)rows; }
+};
+
+static Chain LocalChain(rt2_tracer* t) {
+  return Chain{t, t->width, t->local_rows, t->d_accum.get<float>(), t->d_moment2.get<float>(),
+               t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr, nullptr, nullptr, t->frame_idx,
+               t->d_features.get<float>(), &t->d_dn_scratch, &t->d_tp_hist, &t->d_tp_len, &t->tp_valid, t->tp_cam,
+               &t->present_e0, &t->present_e1, &t->present_pending, &t->present_ms};
+}
+
+// The gathered image on its root r, whose estimate (rt2_tracer_gather_estimate) and whole-image features
+// (EnsureImageFeatures) are current.
+static Chain ImageChain(rt2_tracer* r) {
+  return Chain{r, r->width, r->height, nullptr, nullptr, nullptr, r->d_image_nc.get<float>(),
+               r->d_image_var.get<float>(), r->estimate_frame, r->d_img_features.get<float>(), &r->d_img_scratch,
+               &r->d_img_hist, &r->d_img_len, &r->img_tp_valid, r->img_tp_cam, &r->img_present_e0, &r->img_present_e1,
+               &r->img_present_pending, &r->img_present_ms};
+}
+
+// The feature pass runs the stack traversal: a scene only the threaded program can render is refused.
+static int StackRefusal(const rt2_tracer* t) {
+  return Fail(RT2_ERR_INVALID, "features: the scene needs a traversal stack of " + std::to_string(t->max_stack) +
+                                   " entries (kernel has " + std::to_string(kTraversalStack) + ")");
+}
+
 // The tracer's feature records on its device, traced again when the camera, the seed, the size or the
 // partition have changed since (Realloc drops the buffer). ev: events recorded around the pass, or null. Enqueued
 // on the tracer's stream; the host does not wait.
 static int EnsureFeatures(rt2_tracer* t, bool* launched, const EventPair* ev) {
   *launched = false;
-  if (!t->stack_ok)
-    return Fail(RT2_ERR_INVALID, "features: the scene needs a traversal stack of " + std::to_string(t->max_stack) +
-                                     " entries (kernel has " + std::to_string(kTraversalStack) + ")");
+  if (!t->stack_ok) return StackRefusal(t);
   const size_t n = (size_t)t->width * (size_t)t->local_rows;
   const CameraParams cam = t->camera.Params();
   if (n == 0) return RT2_OK;
@@ -93,13 +137,55 @@ static int FeaturesTimed(rt2_tracer* t) {
   return RT2_OK;
 }
 
-// The denoise scratch, grown to `need` bytes.
-static int EnsureScratch(rt2_tracer* t, size_t need) {
-  if (need > t->d_dn_scratch.bytes()) {
-    HIP_TRY(t->d_dn_scratch.Grow(need));
-    NoteDeviceBytes(t);
+// The whole-image feature records on the root of a gathered image, cached like EnsureFeatures' per (camera, seed;
+// FreeImage drops the buffer with the size). The root traces every pixel itself: with world 1, rank 0 and one
+// band of the image's height, features_kernel's map from local to image rows is the identity.
+static int EnsureImageFeatures(rt2_tracer* r) {
+  if (!r->stack_ok) return StackRefusal(r);
+  const size_t n = (size_t)r->width * (size_t)r->height;
+  const CameraParams cam = r->camera.Params();
+  if (n == 0) return RT2_OK;
+  if (r->d_img_features && r->img_features_valid && r->img_features_seed == r->seed &&
+      memcmp(&r->img_features_cam, &cam, sizeof(cam)) == 0)
+    return RT2_OK;
+  HIP_TRY(hipSetDevice(r->device));
+  if (!r->d_img_features) {
+    HIP_TRY(r->d_img_features.Alloc(n * kDenoiseFeatureFloats * sizeof(float)));
+    NoteDeviceBytes(r);
+  }
+  RenderParams p;
+  BaseParams(r, cam, &p);
+  p.local_rows = r->height;
+  p.band_h = r->height;
+  p.rank = 0;
+  p.world = 1;
+  p.local_pixels = (uint32_t)n;
+  HIP_TRY(LaunchFeatures(p, r->d_img_features.get<float>(), r->stream));
+  r->img_features_valid = true;
+  r->img_features_cam = cam;
+  r->img_features_seed = r->seed;
+  return RT2_OK;
+}
+
+// The chain's scratch, grown to `need` bytes.
+static int EnsureScratch(const Chain& c, size_t need) {
+  if (need > c.scratch->bytes()) {
+    HIP_TRY(c.scratch->Grow(need));
+    NoteDeviceBytes(c.t);
   }
   return RT2_OK;
+}
+
+// The chain's inputs at the head of its scratch, as the filter takes them: colour float3, then the variance of
+// the mean. Enqueued on the tracer's stream.
+static hipError_t EnqueueInputs(const Chain& c) {
+  const size_t n = c.n();
+  float* d_color = c.scratch->get<float>();
+  if (c.accum) return LaunchDenoiseInputs(c.accum, c.moment2, c.counts, d_color, (uint32_t)n, c.frames, c.t->stream);
+  hipError_t e = hipMemcpyAsync(d_color, c.color, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c.t->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_color + 3 * n, c.variance, n * sizeof(float), hipMemcpyDeviceToDevice, c.t->stream);
+  return e;
 }
 
 int rt2_tracer_features(rt2_tracer* t, float* out) {
@@ -133,14 +219,13 @@ int rt2_tracer_denoise(rt2_tracer* t, const rt2_denoise_params* params, float* o
   const size_t n = (size_t)t->width * (size_t)t->local_rows;
   if (n == 0) return RT2_OK;
   HIP_TRY(hipSetDevice(t->device));
-  if ((rc = EnsureScratch(t, DenoiseScratchBytes(n))) != RT2_OK) return rc;
+  const Chain c = LocalChain(t);
+  if ((rc = EnsureScratch(c, DenoiseScratchBytes(n))) != RT2_OK) return rc;
   EventPair ev(t);
   if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
   float* d_color = t->d_dn_scratch.get<float>();
   hipError_t e = hipEventRecord(ev.e0, t->stream);
-  if (e == hipSuccess)
-    e = LaunchDenoiseInputs(t->d_accum.get<float>(), t->d_moment2.get<float>(),
-                            t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr, d_color, (uint32_t)n, t->frame_idx, t->stream);
+  if (e == hipSuccess) e = EnqueueInputs(c);
   if (e == hipSuccess) e = LaunchDenoise(d_color, t->d_features.get<float>(), t->width, t->local_rows, k, DenoiseLds(), t->stream);
   if (e == hipSuccess) e = hipEventRecord(ev.e1, t->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
@@ -215,7 +300,7 @@ static int TemporalParamsOf(const rt2_temporal_params* p, TemporalParams* k) {
   return RT2_OK;
 }
 
-static int EnqueueBlend(rt2_tracer* t, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev);
+static int EnqueueBlend(const Chain& c, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev);
 
 // The blend of the tracer's current estimate with its history, left on the device: colour and variance at
 // the head of the denoise scratch (where LaunchDenoise takes them), the length in d_tp_len. The checks of
@@ -233,42 +318,40 @@ static int TemporalBlend(rt2_tracer* t, const rt2_temporal_params* params, bool 
   if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
   const size_t n = (size_t)t->width * (size_t)t->local_rows;
   if (n == 0) return RT2_OK;
-  return EnqueueBlend(t, k, with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float), push, ev);
+  return EnqueueBlend(LocalChain(t), k, with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float), push, ev);
 }
 
-// TemporalBlend's kernels, enqueued on the tracer's stream over a tracer that has passed its checks, with its
-// frames launched and its features current; n > 0. The host does not wait. scratch_bytes: what the denoise
-// scratch must hold at least.
-static int EnqueueBlend(rt2_tracer* t, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev) {
-  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+// The blend's kernels, enqueued on the chain's stream over a tracer that has passed its checks, with its frames
+// launched (or its estimate gathered) and its features current; n > 0. The host does not wait. scratch_bytes:
+// what the scratch must hold at least.
+static int EnqueueBlend(const Chain& c, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev) {
+  rt2_tracer* t = c.t;
+  const size_t n = c.n();
   int rc;
   HIP_TRY(hipSetDevice(t->device));
-  if ((rc = EnsureScratch(t, scratch_bytes)) != RT2_OK) return rc;
-  if (!t->d_tp_hist) {
-    t->tp_valid = false;
-    HIP_TRY(t->d_tp_hist.Alloc(TemporalHistoryBytes(n)));
-    if (t->d_tp_len.Alloc(n * sizeof(float)) != hipSuccess) {
-      t->d_tp_hist.reset();
+  if ((rc = EnsureScratch(c, scratch_bytes)) != RT2_OK) return rc;
+  if (!*c.hist) {
+    *c.tp_valid = false;
+    HIP_TRY(c.hist->Alloc(TemporalHistoryBytes(n)));
+    if (c.len->Alloc(n * sizeof(float)) != hipSuccess) {
+      c.hist->reset();
       return Fail(RT2_ERR_HIP, "temporal: out of device memory");
     }
     NoteDeviceBytes(t);
   }
-  float* d_color = t->d_dn_scratch.get<float>();
-  const uint32_t* counts = t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr;
+  float* d_color = c.scratch->get<float>();
   if (ev && !ev->Take()) return Fail(RT2_ERR_HIP, "event create failed");
   hipError_t e = ev ? hipEventRecord(ev->e0, t->stream) : hipSuccess;
+  if (e == hipSuccess) e = EnqueueInputs(c);
   if (e == hipSuccess)
-    e = LaunchDenoiseInputs(t->d_accum.get<float>(), t->d_moment2.get<float>(), counts, d_color, (uint32_t)n, t->frame_idx,
-                            t->stream);
-  if (e == hipSuccess)
-    e = LaunchTemporalBlend(d_color, d_color + 3 * n, nullptr, counts, (float)t->frame_idx, t->d_features.get<float>(),
-                            t->tp_valid ? t->d_tp_hist.get<void>() : nullptr, t->tp_cam, t->d_materials.get<float>(),
-                            t->n_materials, true, k, t->d_tp_len.get<float>(), t->width, t->local_rows, t->stream);
+    e = LaunchTemporalBlend(d_color, d_color + 3 * n, nullptr, c.counts, (float)c.frames, c.features,
+                            *c.tp_valid ? c.hist->get<void>() : nullptr, c.tp_cam, t->d_materials.get<float>(),
+                            t->n_materials, true, k, c.len->get<float>(), c.width, c.rows, t->stream);
   if (e == hipSuccess && ev) e = hipEventRecord(ev->e1, t->stream);
   if (e == hipSuccess && push) {
-    t->tp_valid = false;  // until the pack has run
-    e = LaunchTemporalPack(d_color, d_color + 3 * n, t->d_tp_len.get<float>(), t->d_features.get<float>(),
-                           t->d_tp_hist.get<void>(), (uint32_t)n, t->stream);
+    *c.tp_valid = false;  // until the pack has run
+    e = LaunchTemporalPack(d_color, d_color + 3 * n, c.len->get<float>(), c.features, c.hist->get<void>(), (uint32_t)n,
+                           t->stream);
   }
   if (e != hipSuccess) return HipFail(e, "temporal");
   return RT2_OK;
@@ -410,6 +493,57 @@ void rt2_present_defaults(rt2_present_params* out) {
   rt2_denoise_defaults(&out->dp);
 }
 
+// The chain of rt2.h from the inputs to the copy into out_rgba, enqueued on the chain's stream over a tracer that
+// has passed its checks, with its frames launched (or its estimate gathered) and its features current; n > 0.
+// Nothing here blocks the host.
+static int EnqueuePresent(const Chain& c, bool temporal, const TemporalParams& tk, bool denoise, const DenoiseParams& dk,
+                          uint8_t* out_rgba) {
+  rt2_tracer* t = c.t;
+  const size_t n = c.n();
+  int rc;
+  HIP_TRY(hipSetDevice(t->device));
+  // colour float3 and variance at the scratch's head, as the filter takes them; the RGBA8 words behind them, in
+  // the filter's first plane, which is free again once the filter's last kernel (unpack) has run
+  const size_t need = denoise ? DenoiseScratchBytes(n) : n * 5 * sizeof(float);
+  if ((rc = EnsureScratch(c, need)) != RT2_OK) return rc;
+  if (!*c.present_e0 && hipEventCreate(c.present_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  if (!*c.present_e1 && hipEventCreate(c.present_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  *c.present_pending = false;
+  *c.present_ms = -1.0;
+  HIP_TRY(hipEventRecord(*c.present_e0, t->stream));
+  if (temporal) {
+    if ((rc = EnqueueBlend(c, tk, need, false, nullptr)) != RT2_OK) return rc;
+  } else {
+    HIP_TRY(EnqueueInputs(c));
+  }
+  float* d_color = c.scratch->get<float>();
+  uint8_t* d_rgba = reinterpret_cast<uint8_t*>(d_color + 4 * n);
+  if (denoise) HIP_TRY(LaunchDenoise(d_color, c.features, c.width, c.rows, dk, DenoiseLds(), t->stream));
+  HIP_TRY(LaunchPresent(d_color, d_rgba, (uint32_t)n, t->stream));
+  HIP_TRY(hipEventRecord(*c.present_e1, t->stream));
+  *c.present_pending = true;
+  HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, n * 4, hipMemcpyDeviceToHost, t->stream));
+  return RT2_OK;
+}
+
+// rt2_tracer_present_time over the chain's events: polls, never waits.
+static int PresentTime(const Chain& c, double* ms) {
+  if (*c.present_pending) {
+    HIP_TRY(hipSetDevice(c.t->device));
+    const hipError_t q = hipEventQuery(*c.present_e1);
+    if (q == hipSuccess) {
+      float f = -1.0f;
+      if (hipEventElapsedTime(&f, *c.present_e0, *c.present_e1) != hipSuccess) f = -1.0f;
+      *c.present_ms = (double)f;
+      *c.present_pending = false;
+    } else if (q != hipErrorNotReady) {
+      return HipFail(q, "present_time");
+    }
+  }
+  if (ms) *ms = *c.present_pending ? -1.0 : *c.present_ms;
+  return RT2_OK;
+}
+
 static const char kPresentTracerMsg[] = "present: needs an unpartitioned one-GPU tracer (world 1, not joined)";
 
 // The chain of rt2.h, enqueued on the tracer's stream; every refusal comes before the first enqueue. Nothing
@@ -430,33 +564,8 @@ int rt2_tracer_present_async(rt2_tracer* t, const rt2_present_params* params, ui
   if ((rc = Flush(t)) != RT2_OK) return rc;
   bool launched = false;
   if ((rc = EnsureFeatures(t, &launched, nullptr)) != RT2_OK) return rc;
-  const size_t n = (size_t)t->width * (size_t)t->local_rows;
-  if (n == 0) return RT2_OK;
-  HIP_TRY(hipSetDevice(t->device));
-  // colour float3 and variance at the scratch's head, as the filter takes them; the RGBA8 words behind them, in
-  // the filter's first plane, which is free again once the filter's last kernel (unpack) has run
-  const size_t need = denoise ? DenoiseScratchBytes(n) : n * 5 * sizeof(float);
-  if ((rc = EnsureScratch(t, need)) != RT2_OK) return rc;
-  if (!t->present_e0 && hipEventCreate(&t->present_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  if (!t->present_e1 && hipEventCreate(&t->present_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  t->present_pending = false;
-  t->present_ms = -1.0;
-  HIP_TRY(hipEventRecord(t->present_e0, t->stream));
-  if (temporal) {
-    if ((rc = EnqueueBlend(t, tk, need, false, nullptr)) != RT2_OK) return rc;
-  } else {
-    HIP_TRY(LaunchDenoiseInputs(t->d_accum.get<float>(), t->d_moment2.get<float>(),
-                                t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr, t->d_dn_scratch.get<float>(),
-                                (uint32_t)n, t->frame_idx, t->stream));
-  }
-  float* d_color = t->d_dn_scratch.get<float>();
-  uint8_t* d_rgba = reinterpret_cast<uint8_t*>(d_color + 4 * n);
-  if (denoise) HIP_TRY(LaunchDenoise(d_color, t->d_features.get<float>(), t->width, t->local_rows, dk, DenoiseLds(), t->stream));
-  HIP_TRY(LaunchPresent(d_color, d_rgba, (uint32_t)n, t->stream));
-  HIP_TRY(hipEventRecord(t->present_e1, t->stream));
-  t->present_pending = true;
-  HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, n * 4, hipMemcpyDeviceToHost, t->stream));
-  return RT2_OK;
+  if ((size_t)t->width * (size_t)t->local_rows == 0) return RT2_OK;
+  return EnqueuePresent(LocalChain(t), temporal, tk, denoise, dk, out_rgba);
 }
 
 int rt2_tracer_present(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
@@ -477,7 +586,7 @@ int rt2_tracer_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, const rt2_
     if ((rc = Flush(t)) != RT2_OK) return rc;
     bool launched = false;
     if ((rc = EnsureFeatures(t, &launched, nullptr)) != RT2_OK) return rc;
-    if ((rc = EnqueueBlend(t, k, n * 4 * sizeof(float), true, nullptr)) != RT2_OK) return rc;
+    if ((rc = EnqueueBlend(LocalChain(t), k, n * 4 * sizeof(float), true, nullptr)) != RT2_OK) return rc;
     CameraWords(t->camera.Params(), t->tp_cam);
     t->tp_valid = true;
   }
@@ -488,20 +597,7 @@ int rt2_tracer_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, const rt2_
 int rt2_tracer_present_time(rt2_tracer* t, double* ms) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
   if (IsMulti(t) || t->comm || t->world != 1) return Fail(RT2_ERR_INVALID, kPresentTracerMsg);
-  if (t->present_pending) {
-    HIP_TRY(hipSetDevice(t->device));
-    const hipError_t q = hipEventQuery(t->present_e1);
-    if (q == hipSuccess) {
-      float f = -1.0f;
-      if (hipEventElapsedTime(&f, t->present_e0, t->present_e1) != hipSuccess) f = -1.0f;
-      t->present_ms = (double)f;
-      t->present_pending = false;
-    } else if (q != hipErrorNotReady) {
-      return HipFail(q, "present_time");
-    }
-  }
-  if (ms) *ms = t->present_pending ? -1.0 : t->present_ms;
-  return RT2_OK;
+  return PresentTime(LocalChain(t), ms);
 }
 
 int rt2_present_buffers(int device, int width, int height, const float* color, uint8_t* out_rgba) {
@@ -525,5 +621,137 @@ int rt2_present_buffers(int device, int width, int height, const float* color, u
   if (stream) (void)hipStreamDestroy(stream);
   if (e != hipSuccess) return HipFail(e, "present_buffers");
   return RT2_OK;
+}
+
+// ---- reconstructing the gathered image (rt2.h "Reconstructing the gathered image") ----
+// The stages a rt2_present_params switches on and their parameters, checked only for those stages.
+struct PresentStages {
+  bool temporal = true, denoise = true;
+  TemporalParams tk = TemporalDefaults();
+  DenoiseParams dk = DenoiseDefaults();
+};
+static int PresentStagesOf(const rt2_present_params* params, PresentStages* s) {
+  int rc;
+  if (params) {
+    s->temporal = params->temporal != 0;
+    s->denoise = params->denoise != 0;
+  }
+  if (s->temporal && (rc = TemporalParamsOf(params ? &params->tp : nullptr, &s->tk)) != RT2_OK) return rc;
+  if (s->denoise && (rc = DenoiseParamsOf(params ? &params->dp : nullptr, &s->dk)) != RT2_OK) return rc;
+  return RT2_OK;
+}
+
+// The root of the gathered image, with the estimate of the current FrameIdx() and the whole-image features
+// enqueued on its stream. Every refusal comes before the first enqueue.
+static int ImageReady(rt2_tracer* t, rt2_tracer** root) {
+  const rt2_tracer* first = IsMulti(t) ? t->parts[0] : t;
+  if (first->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  if (!first->stack_ok) return StackRefusal(first);
+  int rc = CurrentEstimate(t, false, root);
+  if (rc != RT2_OK) return rc;
+  return EnsureImageFeatures(*root);
+}
+
+int rt2_tracer_image_features(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
+  if (r->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  int rc = EnsureImageFeatures(r);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)r->width * (size_t)r->height;
+  if (n) {
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipMemcpyAsync(out, r->d_img_features.get<float>(), n * kDenoiseFeatureFloats * sizeof(float),
+                           hipMemcpyDeviceToHost, r->stream));
+    r->host_waits++;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+  }
+  return RT2_OK;
+}
+
+int rt2_tracer_image_resolve(rt2_tracer* t, const rt2_present_params* params, float* out_color, float* out_variance,
+                             float* out_length) {
+  if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  PresentStages st;
+  int rc = PresentStagesOf(params, &st);
+  if (rc != RT2_OK) return rc;
+  rt2_tracer* r = nullptr;
+  if ((rc = ImageReady(t, &r)) != RT2_OK) return rc;
+  const Chain c = ImageChain(r);
+  const size_t n = c.n();
+  if (n == 0) return RT2_OK;
+  const size_t need = st.denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float);
+  if (st.temporal) {
+    if ((rc = EnqueueBlend(c, st.tk, need, false, nullptr)) != RT2_OK) return rc;
+  } else {
+    HIP_TRY(hipSetDevice(r->device));
+    if ((rc = EnsureScratch(c, need)) != RT2_OK) return rc;
+    HIP_TRY(EnqueueInputs(c));
+  }
+  float* d_color = c.scratch->get<float>();
+  hipError_t e = hipSuccess;
+  if (st.denoise) e = LaunchDenoise(d_color, c.features, c.width, c.rows, st.dk, DenoiseLds(), r->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, r->stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, r->stream);
+  if (e == hipSuccess && out_length && st.temporal)
+    e = hipMemcpyAsync(out_length, c.len->get<float>(), n * sizeof(float), hipMemcpyDeviceToHost, r->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+  r->host_waits++;
+  if (e != hipSuccess) return HipFail(e, "image_resolve");
+  return RT2_OK;
+}
+
+int rt2_tracer_image_present_async(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
+  if (!t || !out_rgba) return Fail(RT2_ERR_INVALID, "null argument");
+  PresentStages st;
+  int rc = PresentStagesOf(params, &st);
+  if (rc != RT2_OK) return rc;
+  rt2_tracer* r = nullptr;
+  if ((rc = ImageReady(t, &r)) != RT2_OK) return rc;
+  const Chain c = ImageChain(r);
+  if (c.n() == 0) return RT2_OK;
+  return EnqueuePresent(c, st.temporal, st.tk, st.denoise, st.dk, out_rgba);
+}
+
+int rt2_tracer_image_present(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
+  int rc = rt2_tracer_image_present_async(t, params, out_rgba);
+  return rc != RT2_OK ? rc : rt2_tracer_synchronize(t);
+}
+
+int rt2_tracer_image_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, const rt2_temporal_params* params) {
+  if (!t || !cam) return Fail(RT2_ERR_INVALID, "null argument");
+  TemporalParams k;
+  int rc = TemporalParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  const rt2_tracer* first = IsMulti(t) ? t->parts[0] : t;
+  if (!IsMulti(t) && !t->comm && t->world > 1)
+    return Fail(RT2_ERR_INVALID, "image_move_camera: a partitioned tracer must be joined to a communicator");
+  if (first->adaptive_on)
+    return Fail(RT2_ERR_INVALID, "image_move_camera: adaptive sampling is on (rt2_tracer_move_camera keeps its history)");
+  const size_t n = (size_t)first->width * (size_t)first->height;
+  if (first->moments_on && first->frame_idx + first->queued >= 2 && n > 0) {
+    if (!first->stack_ok) return StackRefusal(first);
+    // the estimate's kernel, the blend and the pack run on the root's stream and read only the root's gathered
+    // buffers; the parts' sums were read by the gather, which every part's stream is ordered behind (its own
+    // ncclGather, or the event after the root's copies), so the memsets of the reset below come after it
+    rt2_tracer* r = nullptr;
+    if ((rc = CurrentEstimate(t, true, &r)) != RT2_OK) return rc;
+    if (r->rank == 0) {
+      if ((rc = EnsureImageFeatures(r)) != RT2_OK) return rc;
+      if ((rc = EnqueueBlend(ImageChain(r), k, n * 4 * sizeof(float), true, nullptr)) != RT2_OK) return rc;
+      CameraWords(r->camera.Params(), r->img_tp_cam);
+      r->img_tp_valid = true;
+    }
+  }
+  if ((rc = rt2_tracer_set_camera(t, cam)) != RT2_OK) return rc;
+  return rt2_tracer_reset(t);
+}
+
+int rt2_tracer_image_present_time(rt2_tracer* t, double* ms) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
+  if (r->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  return PresentTime(ImageChain(r), ms);
 }
 }  // extern "C"

@@ -40,11 +40,40 @@ int EnsureImage(rt2_tracer* root) {
   return RT2_OK;
 }
 
+// The root's stacks of the gathered sums of squares and the variance plane (rt2_tracer_gather_estimate), sized
+// like EnsureImage's buffers, which it runs after (EnsureImage frees these with the image).
+int EnsureEstimate(rt2_tracer* root) {
+  const size_t npix = (size_t)root->width * (size_t)root->height;
+  if (root->d_stacks2.bytes() == root->d_stacks.bytes() && root->d_image_var.bytes() == npix * sizeof(float))
+    return RT2_OK;
+  HIP_TRY(hipSetDevice(root->device));
+  HIP_TRY(root->d_stacks2.Alloc(root->d_stacks.bytes()));
+  HIP_TRY(root->d_image_var.Alloc(npix * sizeof(float)));
+  NoteDeviceBytes(root);
+  return RT2_OK;
+}
+
 // Gathers the band stacks of `ranks` (every rank this thread drives: a multi tracer's parts, or
 // one joined tracer) to rank 0 and de-interleaves them there. RCCL unless `loopback` (the ranks
 // share one GPU and their stacks are copied on it). Enqueued on the streams; does not wait.
-int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback) {
+// estimate: the stacks of the sums of squares travel with them (the same RCCL group, or copies on the
+// root's stream), and the root's kernel also writes the variance of the mean (rt2_tracer_gather_estimate);
+// its refusals come before anything is enqueued.
+int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback, bool estimate) {
   rt2_tracer* root = nullptr;
+  if (estimate) {
+    for (const rt2_tracer* p : ranks) {
+      if (p->adaptive_on)
+        return Fail(RT2_ERR_INVALID, "gather_estimate: adaptive sampling is on (the gathered estimate divides by one "
+                                     "frame index)");
+      if (!p->moments_on) return Fail(RT2_ERR_INVALID, "gather_estimate: moments not enabled (rt2_tracer_enable_moments)");
+      if (p->frame_idx + p->queued < 2) return Fail(RT2_ERR_INVALID, "gather_estimate needs at least 2 frames");
+      if (!loopback && !p->comm) return Fail(RT2_ERR_INVALID, "gather: tracer is not part of a communicator");
+      if (p->width != ranks[0]->width || p->height != ranks[0]->height ||
+          p->frame_idx + p->queued != ranks[0]->frame_idx + ranks[0]->queued)
+        return Fail(RT2_ERR_INVALID, "gather: the ranks disagree on dims or frame index");
+    }
+  }
   for (rt2_tracer* p : ranks) {
     int rc = Flush(p);
     if (rc != RT2_OK) return rc;
@@ -59,6 +88,7 @@ int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback) {
   if (root) {
     int rc = EnsureImage(root);
     if (rc != RT2_OK) return rc;
+    if (estimate && (rc = EnsureEstimate(root)) != RT2_OK) return rc;
     HIP_TRY(hipSetDevice(root->device));
     e0 = TakeEvent(root);
     e1 = TakeEvent(root);
@@ -77,9 +107,12 @@ int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback) {
         }
         HIP_TRY(hipMemcpyAsync(root->d_stacks.get<float>() + (size_t)p->rank * count, p->d_accum.get<float>(),
                                count * sizeof(float), hipMemcpyDeviceToDevice, root->stream));
+        if (estimate)
+          HIP_TRY(hipMemcpyAsync(root->d_stacks2.get<float>() + (size_t)p->rank * count, p->d_moment2.get<float>(),
+                                 count * sizeof(float), hipMemcpyDeviceToDevice, root->stream));
       }
-      // later work on a part's stream (Render, Reset) must not overwrite its accumulation while the
-      // root's copy may still read it: every part stream waits for the copies
+      // later work on a part's stream (Render, Reset) must not overwrite its accumulation (or its sums of
+      // squares) while the root's copy may still read it: every part stream waits for all the copies
       if (ranks.size() > 1) {
         HIP_TRY(hipSetDevice(root->device));
         hipEvent_t e = TakeEvent(root);
@@ -100,29 +133,67 @@ int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback) {
           (void)ncclGroupEnd();
           return Fail(RT2_ERR_HIP, std::string("ncclGather: ") + ncclGetErrorString(r));
         }
+        if (estimate)
+          r = ncclGather(p->d_moment2.get<float>(), p == root ? root->d_stacks2.get<float>() : nullptr, count,
+                         ncclFloat32, 0, p->comm, p->stream);
+        if (r != ncclSuccess) {
+          (void)ncclGroupEnd();
+          return Fail(RT2_ERR_HIP, std::string("ncclGather: ") + ncclGetErrorString(r));
+        }
       }
       NCCL_TRY(ncclGroupEnd());
     }
   }
   if (root) {
     HIP_TRY(hipSetDevice(root->device));
-    HIP_TRY(LaunchDeinterleave(root->d_stacks.get<float>(), root->d_image.get<float>(), root->d_image_nc.get<float>(),
-                               root->d_image_px.get<uint8_t>(), root->width, root->height, BandH(root), root->world,
-                               BandRowsMax(root), (int)root->frame_idx, root->stream));
+    if (estimate)
+      HIP_TRY(LaunchDeinterleaveEstimate(root->d_stacks.get<float>(), root->d_stacks2.get<float>(),
+                                         root->d_image.get<float>(), root->d_image_nc.get<float>(),
+                                         root->d_image_px.get<uint8_t>(), root->d_image_var.get<float>(), root->width,
+                                         root->height, BandH(root), root->world, BandRowsMax(root), (int)root->frame_idx,
+                                         root->stream));
+    else
+      HIP_TRY(LaunchDeinterleave(root->d_stacks.get<float>(), root->d_image.get<float>(), root->d_image_nc.get<float>(),
+                                 root->d_image_px.get<uint8_t>(), root->width, root->height, BandH(root), root->world,
+                                 BandRowsMax(root), (int)root->frame_idx, root->stream));
     if (e1) HIP_TRY(hipEventRecord(e1, root->stream));
     if (e0 && e1) root->gpending.emplace_back(e0, e1);
     root->image_frame = root->frame_idx;
     root->gathers++;
   }
+  // every rank notes the estimate it took part in (the root's is the one its variance plane holds)
+  if (estimate)
+    for (rt2_tracer* p : ranks) p->estimate_frame = p->frame_idx;
   return RT2_OK;
+}
+
+int GatherAny(rt2_tracer* t, bool estimate) {
+  if (IsMulti(t)) return GatherRanks(t->parts, t->loopback, estimate);
+  if (t->comm) return GatherRanks({t}, false, estimate);
+  if (t->world > 1) return Fail(RT2_ERR_INVALID, "gather: a partitioned tracer must be joined to a communicator");
+  return GatherRanks({t}, true, estimate);  // one GPU, whole image: the "gather" is a device-local copy
 }
 }  // namespace
 
-int rt2::detail::GatherMulti(rt2_tracer* t) {
-  if (IsMulti(t)) return GatherRanks(t->parts, t->loopback);
-  if (t->comm) return GatherRanks({t}, false);
-  if (t->world > 1) return Fail(RT2_ERR_INVALID, "gather: a partitioned tracer must be joined to a communicator");
-  return GatherRanks({t}, true);  // one GPU, whole image: the "gather" is a device-local copy
+int rt2::detail::GatherMulti(rt2_tracer* t) { return GatherAny(t, false); }
+int rt2::detail::GatherEstimate(rt2_tracer* t) { return GatherAny(t, true); }
+
+int rt2::detail::CurrentEstimate(rt2_tracer* t, bool collective, rt2_tracer** root) {
+  rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
+  const bool joined = !IsMulti(t) && t->comm;
+  if (r->rank != 0 && !(collective && joined)) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  const int64_t cur = r->frame_idx + r->queued;
+  if (r->estimate_frame < 0 || r->estimate_frame != cur) {
+    if (joined && !collective)
+      return Fail(RT2_ERR_INVALID, r->estimate_frame < 0
+                                       ? "no gathered estimate (every rank calls rt2_tracer_gather_estimate first)"
+                                       : "the gathered estimate is stale: frames were rendered since "
+                                         "rt2_tracer_gather_estimate (every rank calls it again)");
+    int rc = GatherAny(t, true);
+    if (rc != RT2_OK) return rc;
+  }
+  *root = r;
+  return RT2_OK;
 }
 
 namespace {
@@ -285,6 +356,49 @@ int rt2_tracer_image_pixels(rt2_tracer* t, uint8_t* out) {
   if (rc != RT2_OK) return rc;
   size_t n = (size_t)r->width * (size_t)r->height;
   if (n) HIP_TRY(hipMemcpy(out, r->d_image_px.get<uint8_t>(), n * 4, hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+
+// ---- reconstructing the gathered image (rt2.h): the gather's side; the chain is in capi_filter.cpp ----
+int rt2_tracer_gather_estimate(rt2_tracer* t) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  return GatherEstimate(t);
+}
+
+int rt2_tracer_image_variance(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
+  if (r->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  if (r->estimate_frame < 0)
+    return Fail(RT2_ERR_INVALID, "no gathered estimate (call rt2_tracer_gather_estimate first)");
+  int rc = Sync(r);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)r->width * (size_t)r->height;
+  if (n) HIP_TRY(hipMemcpy(out, r->d_image_var.get<float>(), n * sizeof(float), hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+
+int rt2_deinterleave_estimate_host(const float* stacks, const float* stacks2, float* image, float* image_nc,
+                                   float* variance, int width, int height, int band_h, int world, int64_t frames) {
+  if (!stacks || !stacks2 || !image || !image_nc || !variance || width < 0 || height < 0 || band_h < 0 || world < 1)
+    return Fail(RT2_ERR_INVALID, "bad de-interleave arguments");
+  if (frames < 2 || frames > 0x7FFFFFFF) return Fail(RT2_ERR_INVALID, "deinterleave_estimate: need 2 <= frames < 2^31");
+  const size_t max_rows = (size_t)rt2::BandRowsMax(height, band_h, world);
+  const float fi = (float)frames;
+  for (int y = 0; y < height; y++) {
+    const BandRow src = BandSource(y, band_h, world);
+    for (int x = 0; x < width; x++) {
+      const size_t at = 3 * (((size_t)src.rank * max_rows + (size_t)src.row) * (size_t)width + (size_t)x);
+      const size_t i = (size_t)y * (size_t)width + (size_t)x;
+      const float a[3] = {stacks[at], stacks[at + 1], stacks[at + 2]};
+      const float q[3] = {stacks2[at], stacks2[at + 1], stacks2[at + 2]};
+      for (int c = 0; c < 3; c++) {
+        image[3 * i + c] = a[c];
+        image_nc[3 * i + c] = a[c] / fi;
+      }
+      variance[i] = DenoiseVarianceOfSem(NoiseOfPixel(a, q, frames).sem);
+    }
+  }
   return RT2_OK;
 }
 }  // extern "C"

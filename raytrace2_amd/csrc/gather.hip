@@ -6,6 +6,11 @@
 // back to image order and derives Pixels() = ToColor(clamp(accum / frame_idx, 0, 1))
 // (RayTracer.cpp:16-18,65-66) with the same operations as accumulate_kernel, so the gathered image
 // is bit-identical to a one-GPU render.
+//
+// deinterleave_estimate_kernel is the same pass over two stacks, the sums and the sums of squares
+// (rt2_tracer_gather_estimate): beside the image it writes the variance of the mean the denoiser takes
+// (denoise.h DenoiseVarianceOfSem over noise.h NoiseOfPixel), so the image-order sums of squares are
+// never stored.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -53,6 +58,39 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(const float* __restri
   pixels[i] = rgba;
 }
 
+// The same over the sums and the sums of squares: deinterleave_kernel's three outputs with its operations,
+// and variance[i] = DenoiseVarianceOfSem(NoiseOfPixel(a, q, frame_idx).sem), what denoise_inputs_kernel
+// evaluates on a one-GPU tracer. frame_idx >= 2 (the host checks). 24 bytes read and 32 written per pixel.
+__global__ __launch_bounds__(256) void deinterleave_estimate_kernel(
+    const float* __restrict__ stacks, const float* __restrict__ stacks2, float* __restrict__ image,
+    float* __restrict__ image_nc, uint32_t* __restrict__ pixels, float* __restrict__ variance, uint32_t width,
+    uint32_t npix, uint32_t band_h, uint32_t world, uint32_t max_rows, int frame_idx) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= npix) return;
+  const uint32_t y = i / width, x = i - y * width;
+  const BandRow src = BandSource((int)y, (int)band_h, (int)world);  // rt2_layout.h
+  const unsigned long long at = 3ull * (((unsigned long long)src.rank * max_rows + (uint32_t)src.row) * width + x);
+  const float a[3] = {stacks[at], stacks[at + 1], stacks[at + 2]};
+  const float q[3] = {stacks2[at], stacks2[at + 1], stacks2[at + 2]};
+  image[3ull * i] = a[0];
+  image[3ull * i + 1] = a[1];
+  image[3ull * i + 2] = a[2];
+  const float fi = (float)frame_idx;
+  const float cc[3] = {a[0] / fi, a[1] / fi, a[2] / fi};
+  image_nc[3ull * i] = cc[0];
+  image_nc[3ull * i + 1] = cc[1];
+  image_nc[3ull * i + 2] = cc[2];
+  uint32_t rgba = 0xFF000000u;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float v = gmin1(gmax1(cc[k], 0.0f), 1.0f);
+    rgba |= ((uint32_t)(uint8_t)floor((double)v * 255.999)) << (8 * k);
+  }
+  pixels[i] = rgba;
+  const PixelNoise pn = NoiseOfPixel(a, q, (int64_t)frame_idx);
+  variance[i] = DenoiseVarianceOfSem(pn.sem);
+}
+
 }  // namespace dev
 
 hipError_t LaunchDeinterleave(const float* stacks, float* image, float* image_nc, uint8_t* pixels, int width,
@@ -62,6 +100,17 @@ hipError_t LaunchDeinterleave(const float* stacks, float* image, float* image_nc
   hipLaunchKernelGGL(dev::deinterleave_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, stream, stacks, image,
                      image_nc, reinterpret_cast<uint32_t*>(pixels), (uint32_t)width, npix, (uint32_t)band_h, (uint32_t)world,
                      (uint32_t)max_rows, frame_idx);
+  return hipGetLastError();
+}
+
+hipError_t LaunchDeinterleaveEstimate(const float* stacks, const float* stacks2, float* image, float* image_nc,
+                                      uint8_t* pixels, float* variance, int width, int height, int band_h, int world,
+                                      int max_rows, int frame_idx, hipStream_t stream) {
+  const uint32_t npix = (uint32_t)width * (uint32_t)height;
+  if (npix == 0) return hipSuccess;
+  hipLaunchKernelGGL(dev::deinterleave_estimate_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, stream, stacks, stacks2,
+                     image, image_nc, reinterpret_cast<uint32_t*>(pixels), variance, (uint32_t)width, npix, (uint32_t)band_h,
+                     (uint32_t)world, (uint32_t)max_rows, frame_idx);
   return hipGetLastError();
 }
 

@@ -18,7 +18,8 @@
 // at most N = --max-samples frames (default: num_samples); it prints "frames <f> active <a> samples <s>".
 // --denoise turns moments on and writes the denoised image (RayTracer::Denoise: the variance-guided a-trous
 // filter at its defaults, --denoise-iterations N passes) where it wrote the plain one; it composes with
-// --noise-target and --adaptive and needs at least 2 frames and one GPU.
+// --noise-target and --adaptive and needs at least 2 frames. With --gpus N it writes RayTracer::ImageResolve of
+// the gathered image (temporal off, denoise on: the same filter over the gathered estimate, the same bytes).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -31,7 +32,8 @@ int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene.json> <out.png> [--settings f] [--samples N] [--size WxH] [--gpus N] "
                          "[--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]] "
-                         "[--denoise [--denoise-iterations N]]\n", argv[0]);
+                         "[--denoise [--denoise-iterations N]] (--denoise with --gpus N filters the gathered image)\n",
+                 argv[0]);
     return 2;
   }
   const std::string scene_path = argv[1], out_path = argv[2];
@@ -125,7 +127,12 @@ int main(int argc, char** argv) {
     }
     rt2_denoise_params dp = rt2::RayTracer::DenoiseDefaults();
     if (denoise_iterations > 0) dp.iterations = denoise_iterations;
-    const auto pixels = denoise ? tracer.Denoise(&dp) : tracer.NonConvertedPixels();  // runs the queued frames
+    rt2_present_params pp = rt2::RayTracer::PresentDefaults();
+    pp.temporal = 0;
+    pp.denoise = 1;
+    pp.dp = dp;
+    // (each of the three runs the queued frames)
+    const auto pixels = !denoise ? tracer.NonConvertedPixels() : gpus > 0 ? tracer.ImageResolve(&pp) : tracer.Denoise(&dp);
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     rt2::util::WriteImage(pixels, tracer.Dims().x, tracer.Dims().y, out_path);
 

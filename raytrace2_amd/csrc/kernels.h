@@ -34,6 +34,9 @@ bool RenderTakesFlat(int variant, int mode, bool stats, bool list);
 // gather.hip
 hipError_t LaunchDeinterleave(const float* stacks, float* image, float* image_nc, uint8_t* pixels, int width, int height, int band_h,
                               int world, int max_rows, int frame_idx, hipStream_t stream);
+hipError_t LaunchDeinterleaveEstimate(const float* stacks, const float* stacks2, float* image, float* image_nc,
+                                      uint8_t* pixels, float* variance, int width, int height, int band_h, int world,
+                                      int max_rows, int frame_idx, hipStream_t stream);
 // noise.hip
 uint32_t NoiseBlocks(uint32_t npix);
 hipError_t LaunchNoise(const float* accum, const float* moment2, const uint32_t* counts, float* sem,

@@ -290,6 +290,26 @@ struct rt2_tracer {
   uint64_t gathers = 0;
   double gather_ms = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> gpending;  // per-gather timing events
+  // root: the reconstruction of the gathered image (rt2.h "Reconstructing the gathered image"), each buffer
+  // allocated at the first call that needs it: the gathered stacks of the sums of squares and the variance of
+  // the mean in image order with the frame index they are of (-1: none); the whole-image feature records with
+  // the launch values they were traced under; the chain's scratch, history and length plane with the history's
+  // camera words; the events and time of the last image present (as present_e0 .. present_ms above)
+  rt2::DeviceBuffer d_stacks2;       // [world][max_rows][W] float3
+  rt2::DeviceBuffer d_image_var;     // [H][W] float
+  int64_t estimate_frame = -1;
+  rt2::DeviceBuffer d_img_features;  // [H][W] 16 floats
+  bool img_features_valid = false;
+  rt2::CameraParams img_features_cam;
+  uint64_t img_features_seed = 0;
+  rt2::DeviceBuffer d_img_scratch;
+  rt2::DeviceBuffer d_img_hist;
+  rt2::DeviceBuffer d_img_len;
+  bool img_tp_valid = false;
+  float img_tp_cam[rt2::kTemporalCameraWords] = {};
+  hipEvent_t img_present_e0 = nullptr, img_present_e1 = nullptr;
+  bool img_present_pending = false;
+  double img_present_ms = -1.0;
   // image readbacks to the host (rt2_tracer_image_*): count and device-to-host copy time
   uint64_t readbacks = 0;
   double readback_ms = 0;
@@ -332,6 +352,12 @@ int Sync(rt2_tracer* t);
 void BaseParams(const rt2_tracer* t, const CameraParams& cam, RenderParams* p);
 // capi_multi.cpp
 int GatherMulti(rt2_tracer* t);
+int GatherEstimate(rt2_tracer* t);  // rt2_tracer_gather_estimate: the gather with the sums of squares
+// The tracer holding the gathered image (rank 0) with the estimate of the current FrameIdx() (queued frames
+// included) enqueued on it. A create_multi or plain tracer whose estimate is missing or stale gathers here; a
+// joined one is refused, unless `collective`: then every rank is calling, a rank that is behind takes part in the
+// gather, and a rank other than 0 gets itself back (it holds no image).
+int CurrentEstimate(rt2_tracer* t, bool collective, rt2_tracer** root);
 
 inline int BandH(const rt2_tracer* t) { return t->band_h > 0 ? t->band_h : (t->height > 0 ? t->height : 1); }
 

@@ -36,6 +36,22 @@ def deinterleave(stacks: np.ndarray, height: int, band_h: int) -> np.ndarray:
     return out
 
 
+def deinterleave_estimate(stacks: np.ndarray, stacks2: np.ndarray, height: int, band_h: int, frames: int):
+    """Rank-major padded band stacks (world, max_rows, W, 3) of the sums and of the sums of squares over `frames`
+    frames -> (sums, means, variance of the mean) in image order, (H, W, 3), (H, W, 3) and (H, W): the host
+    statement of gather_estimate()'s kernel (rt2_deinterleave_estimate_host), for stacks gathered by other means."""
+    stacks = np.ascontiguousarray(stacks, np.float32)
+    stacks2 = np.ascontiguousarray(stacks2, np.float32)
+    world, max_rows, w, c = stacks.shape
+    if c != 3 or stacks2.shape != stacks.shape or max_rows != band_rows_max(height, band_h, world):
+        raise ValueError("deinterleave_estimate: need two (world, band_rows_max, W, 3) stacks")
+    image, mean = np.empty((height, w, 3), np.float32), np.empty((height, w, 3), np.float32)
+    var = np.empty((height, w), np.float32)
+    check(lib.rt2_deinterleave_estimate_host(_fp(stacks), _fp(stacks2), _fp(image), _fp(mean), _fp(var), w, height,
+                                             int(band_h), world, int(frames)))
+    return image, mean, var
+
+
 def source_rows(height: int, band_h: int, world: int) -> np.ndarray:
     """Image row y -> row of the rank-major padded stacks viewed as (world * max_rows) rows: the C
     ABI's host de-interleave applied to the stacks' own row numbers (one channel)."""

@@ -684,6 +684,78 @@ class RayTracer:
         check(lib.rt2_tracer_present_time(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- reconstructing the gathered image (rt2.h "Reconstructing the gathered image") -----------
+    # For create_multi, joined and plain tracers; arrays have the shape of the whole image, on rank 0.
+    def gather_estimate(self) -> None:
+        """gather() with the sums of squares: the root then also holds the variance of the mean (collective on
+        joined tracers; enqueued, no wait). Needs enable_moments and FrameIdx() >= 2."""
+        self._push_camera()
+        check(lib.rt2_tracer_gather_estimate(self._h))
+
+    def image_variance(self) -> np.ndarray:
+        """The gathered estimate's variance of the mean, (H, W) float32: denoise()'s input v."""
+        w, h = self.Dims()
+        out = np.zeros((h, w), np.float32)
+        check(lib.rt2_tracer_image_variance(self._h, _fp(out)))
+        return out
+
+    def image_features(self) -> np.ndarray:
+        """features() of the whole image, (H, W, 16) float32, traced on the root (needs no gather, no moments)."""
+        self._push_camera()
+        w, h = self.Dims()
+        out = np.zeros((h, w, 16), np.float32)
+        check(lib.rt2_tracer_image_features(self._h, _fp(out)))
+        return out
+
+    def image_resolve(self, variance: bool = False, length: bool = False, **present_params):
+        """temporal_resolve() and denoise() in one over the gathered estimate: (H, W, 3) float32; with variance /
+        length also the variance of the mean and the blend's length in frames, (H, W) each (length stays zero with
+        temporal off). present_params: present()'s (temporal, denoise, tp, dp). Changes nothing."""
+        self._push_camera()
+        w, h = self.Dims()
+        out = np.zeros((h, w, 3), np.float32)
+        var = np.zeros((h, w), np.float32) if variance else None
+        ln = np.zeros((h, w), np.float32) if length else None
+        check(lib.rt2_tracer_image_resolve(self._h, _present_params(present_params), _fp(out),
+                                           _fp(var) if variance else None, _fp(ln) if length else None))
+        res = (out,) + ((var,) if variance else ()) + ((ln,) if length else ())
+        return res if len(res) > 1 else out
+
+    def image_present(self, **params) -> np.ndarray:
+        """present() of the gathered image, (H, W, 4) uint8."""
+        self._push_camera()
+        w, h = self.Dims()
+        out = np.zeros((h, w, 4), np.uint8)
+        check(lib.rt2_tracer_image_present(self._h, _present_params(params),
+                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return out
+
+    def image_present_async(self, pinned_array: np.ndarray, **params) -> None:
+        """image_present() enqueued into `pinned_array` ((H, W, 4) uint8 of a progressive.PinnedBuffer), returning
+        at once: the bytes are complete after synchronize() or once query() returns 1."""
+        w, h = self.Dims()
+        a = pinned_array
+        if a.dtype != np.uint8 or not a.flags["C_CONTIGUOUS"] or a.nbytes != h * w * 4:
+            raise ValueError("image_present_async: need a C-contiguous uint8 array of H * W * 4 bytes")
+        self._push_camera()
+        check(lib.rt2_tracer_image_present_async(self._h, _present_params(params),
+                                                 a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+
+    def image_move_camera(self, cam: Camera, **temporal_params) -> None:
+        """move_camera() for the gathered image: the blend of the current gathered estimate becomes the root's
+        history, then set_camera(cam) and Reset() on every GPU, without a wait (collective on joined tracers).
+        `self.camera`, when set, becomes `cam`."""
+        d = cam._desc()
+        check(lib.rt2_tracer_image_move_camera(self._h, ctypes.byref(d), _temporal_params(temporal_params)))
+        if self.camera is not None:
+            self.camera = cam
+
+    def image_present_time(self) -> float:
+        """GPU ms of the last image present's kernels (-1: not finished yet, or none). Never waits."""
+        ms = ctypes.c_double(-1.0)
+        check(lib.rt2_tracer_image_present_time(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def enable_stats(self, on: bool = True) -> None:
         check(lib.rt2_tracer_enable_stats(self._h, 1 if on else 0))
 
