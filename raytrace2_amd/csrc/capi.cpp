@@ -47,75 +47,54 @@ int LocalRows(int h, int band_h, int rank, int world) {
   return n;
 }
 
+// The tracer's device buffers in three groups, each listed once, in the order it is freed: the free functions
+// below and DeviceBytes both go through these lists, so a buffer added to one is freed and counted. f takes a
+// DeviceBuffer or a Recon (Release, BytesOf); T: rt2_tracer or const rt2_tracer. First the scene program and tables and the small per-tracer buffers, in the order rt2_tracer_create uploads them.
+template <typename T, typename Fn>
+static void ForSceneBuffers(T* t, Fn&& f) {
+  for (auto* d : {&t->d_nodes, &t->d_materials, &t->d_textures, &t->d_perlin_vec, &t->d_perlin_perm, &t->d_lin,
+                  &t->d_lin_wide, &t->d_lind, &t->d_hit, &t->d_flat_wide, &t->d_flat_cert, &t->d_work, &t->d_stats})
+    f(*d);
+}
+// The frame buffers of the local rows, with their reconstruction.
+template <typename T, typename Fn>
+static void ForFrameBuffers(T* t, Fn&& f) {
+  for (auto* d : {&t->d_accum, &t->d_pixels, &t->d_ray_counts, &t->d_moment2, &t->d_noise, &t->d_counts, &t->d_active,
+                  &t->d_over, &t->d_list, &t->d_slot_of, &t->d_ad_scratch})
+    f(*d);
+  f(t->recon);
+}
+// A root's gathered image, its estimate (capi_multi.cpp) and its reconstruction: the history goes with the image.
+template <typename T, typename Fn>
+static void ForImageBuffers(T* t, Fn&& f) {
+  for (auto* d : {&t->d_stacks, &t->d_image, &t->d_image_nc, &t->d_image_px, &t->d_stacks2, &t->d_image_var}) f(*d);
+  f(t->image_recon);
+}
+static void Release(DeviceBuffer& d) { d.reset(); }
+static void Release(Recon& r) { r.Free(); }
+static size_t BytesOf(const DeviceBuffer& d) { return d.bytes(); }
+static size_t BytesOf(const Recon& r) { return r.Bytes(); }
+
 void FreeImage(rt2_tracer* t) {
-  t->d_stacks.reset();
-  t->d_image.reset();
-  t->d_image_nc.reset();
-  t->d_image_px.reset();
+  ForImageBuffers(t, [](auto& d) { Release(d); });
   t->image_frame = -1;
-  // the gathered image's reconstruction (capi_multi.cpp, capi_filter.cpp): the history goes with the image
-  t->d_stacks2.reset();
-  t->d_image_var.reset();
   t->estimate_frame = -1;
-  t->d_img_features.reset();
-  t->img_features_valid = false;
-  t->d_img_scratch.reset();
-  t->d_img_hist.reset();
-  t->d_img_len.reset();
-  t->img_tp_valid = false;
 }
 
 static void FreeFrame(rt2_tracer* t) {
   for (auto& sl : t->slots) (void)sl.samples.reset();  // stream-ordered (LaunchFrames)
-  t->d_accum.reset();
-  t->d_pixels.reset();
-  t->d_ray_counts.reset();
-  t->d_moment2.reset();
-  t->d_noise.reset();
-  t->d_counts.reset();
-  t->d_active.reset();
-  t->d_over.reset();
-  t->d_list.reset();
-  t->d_slot_of.reset();
-  t->d_ad_scratch.reset();
-  t->d_features.reset();
-  t->d_dn_scratch.reset();
-  t->d_tp_hist.reset();
-  t->d_tp_len.reset();
-  t->tp_valid = false;
-  t->features_valid = false;
+  ForFrameBuffers(t, [](auto& d) { Release(d); });
   FreeImage(t);
 }
 
-// The scene program and tables and the small per-tracer buffers, in the order rt2_tracer_create uploads them.
-static void ResetScene(rt2_tracer* t) {
-  t->d_nodes.reset();
-  t->d_materials.reset();
-  t->d_textures.reset();
-  t->d_perlin_vec.reset();
-  t->d_perlin_perm.reset();
-  t->d_lin.reset();
-  t->d_lin_wide.reset();
-  t->d_lind.reset();
-  t->d_hit.reset();
-  t->d_flat_wide.reset();
-  t->d_flat_cert.reset();
-  t->d_work.reset();
-  t->d_stats.reset();
-}
-
-// Device bytes this tracer holds now: the scene program and small buffers, the frame buffers, both
-// launch slots' sample buffers and chunk tables, and a root's gathered image.
+// Device bytes this tracer holds now: the scene program and small buffers with the clock ring, the frame
+// buffers, both launch slots' sample buffers and chunk tables, and a root's gathered image.
 static size_t DeviceBytes(const rt2_tracer* t) {
-  size_t b = 0;
-  for (const DeviceBuffer* d :
-       {&t->d_nodes, &t->d_materials, &t->d_textures, &t->d_perlin_vec, &t->d_perlin_perm, &t->d_lin, &t->d_lin_wide,
-        &t->d_lind, &t->d_hit, &t->d_flat_wide, &t->d_flat_cert, &t->d_work, &t->d_clock, &t->d_stats, &t->d_accum,
-        &t->d_pixels, &t->d_ray_counts, &t->d_moment2, &t->d_noise, &t->d_counts, &t->d_active, &t->d_over, &t->d_list,
-        &t->d_slot_of, &t->d_ad_scratch, &t->d_features, &t->d_dn_scratch, &t->d_tp_hist, &t->d_tp_len, &t->d_stacks,
-        &t->d_image, &t->d_image_nc, &t->d_image_px, &t->d_stacks2, &t->d_image_var, &t->d_img_features,
-        &t->d_img_scratch, &t->d_img_hist, &t->d_img_len})
-    b += d->bytes();
+  size_t b = t->d_clock.bytes();
+  const auto add = [&b](const auto& d) { b += BytesOf(d); };
+  ForSceneBuffers(t, add);
+  ForFrameBuffers(t, add);
+  ForImageBuffers(t, add);
   for (const auto& sl : t->slots) b += sl.samples.bytes() + sl.chunks.bytes();
   return b;
 }
@@ -547,14 +526,12 @@ rt2_tracer::~rt2_tracer() {
   }
   if (stream) (void)hipStreamSynchronize(stream);
   for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
-  if (present_e0) (void)hipEventDestroy(present_e0);
-  if (present_e1) (void)hipEventDestroy(present_e1);
-  if (img_present_e0) (void)hipEventDestroy(img_present_e0);
-  if (img_present_e1) (void)hipEventDestroy(img_present_e1);
+  recon.DestroyEvents();
+  image_recon.DestroyEvents();
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
   FreeFrame(this);
-  ResetScene(this);
+  ForSceneBuffers(this, [](auto& d) { Release(d); });
   for (auto& sl : slots) {
     (void)sl.chunks.reset();
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);

@@ -11,18 +11,23 @@
 using namespace rt2;
 using namespace rt2::detail;
 
-extern "C" {
+// ---- what the calls below share: refusals, parameters, the chain, the feature pass, the way back to the host ----
+// The local calls run on a tracer that holds the whole image on one GPU.
+static bool OneGpu(const rt2_tracer* t) { return !IsMulti(t) && !t->comm && t->world == 1; }
 
-// ---- feature buffers and denoiser (rt2.h "Feature buffers and denoiser") ----
-void rt2_denoise_defaults(rt2_denoise_params* out) {
-  if (!out) return;
-  const DenoiseParams d = DenoiseDefaults();
-  out->iterations = d.iterations;
-  out->normal_power_log2 = d.normal_power_log2;
-  out->sigma_l = d.sigma_l;
-  out->sigma_p = d.sigma_p;
-  out->sigma_a = d.sigma_a;
-  out->eps_l = d.eps_l;
+// The refusals several calls share, each under the call's own prefix ("denoise", "temporal", "present").
+static int OneGpuRefusal(const char* call) {
+  return Fail(RT2_ERR_INVALID, std::string(call) + ": needs an unpartitioned one-GPU tracer (world 1, not joined)");
+}
+static int MomentsRefusal(const char* call) {
+  return Fail(RT2_ERR_INVALID, std::string(call) + ": moments not enabled (rt2_tracer_enable_moments)");
+}
+static int FramesRefusal(const char* call) { return Fail(RT2_ERR_INVALID, std::string(call) + " needs at least 2 frames"); }
+
+// The feature pass runs the stack traversal: a scene only the threaded program can render is refused.
+static int StackRefusal(const rt2_tracer* t) {
+  return Fail(RT2_ERR_INVALID, "features: the scene needs a traversal stack of " + std::to_string(t->max_stack) +
+                                   " entries (kernel has " + std::to_string(kTraversalStack) + ")");
 }
 
 static int DenoiseParamsOf(const rt2_denoise_params* p, DenoiseParams* k) {
@@ -31,6 +36,32 @@ static int DenoiseParamsOf(const rt2_denoise_params* p, DenoiseParams* k) {
   if (!DenoiseParamsValid(*k))
     return Fail(RT2_ERR_INVALID, "denoise: need 1 <= iterations <= 8, 0 <= normal_power_log2 <= 8, and sigma_l, sigma_p, "
                                  "sigma_a, eps_l finite and > 0");
+  return RT2_OK;
+}
+
+static int TemporalParamsOf(const rt2_temporal_params* p, TemporalParams* k) {
+  *k = TemporalDefaults();
+  if (p) *k = TemporalParams{p->max_history, p->max_history_specular, p->min_normal_dot, p->sigma_p, p->sigma_a};
+  if (!TemporalParamsValid(*k))
+    return Fail(RT2_ERR_INVALID, "temporal: need max_history, sigma_p, sigma_a finite and > 0, max_history_specular finite "
+                                 "and >= 0, min_normal_dot finite");
+  return RT2_OK;
+}
+
+// The stages a rt2_present_params switches on and their parameters, checked only for those stages.
+struct PresentStages {
+  bool temporal = true, denoise = true;
+  TemporalParams tk = TemporalDefaults();
+  DenoiseParams dk = DenoiseDefaults();
+};
+static int PresentStagesOf(const rt2_present_params* params, PresentStages* s) {
+  int rc;
+  if (params) {
+    s->temporal = params->temporal != 0;
+    s->denoise = params->denoise != 0;
+  }
+  if (s->temporal && (rc = TemporalParamsOf(params ? &params->tp : nullptr, &s->tk)) != RT2_OK) return rc;
+  if (s->denoise && (rc = DenoiseParamsOf(params ? &params->dp : nullptr, &s->dk)) != RT2_OK) return rc;
   return RT2_OK;
 }
 
@@ -49,86 +80,99 @@ static double EventMs(const EventPair& ev) {
 
 // What the reconstruction chain (inputs, temporal blend, filter, tone map) runs over: a one-GPU tracer's local
 // image, or the gathered image on its root (rt2.h "Reconstructing the gathered image"). The kernels take
-// pointers and dimensions, so the two differ only in where the estimate comes from and which of the tracer's
-// buffers hold the scratch and the history.
+// pointers and dimensions, so the two differ only in which Recon of the tracer they use, in the rows, and in where
+// the estimate comes from.
 struct Chain {
   rt2_tracer* t;  // device, stream, material table, event pool
+  Recon& recon;   // features (current), scratch, history, present events
   int width, rows;
-  // the estimate: the sums (LaunchDenoiseInputs divides and takes the variance), or with accum null the
-  // resolved colour and variance of the mean (the gather's kernel has done both; they are copied)
-  const float *accum, *moment2;
-  const uint32_t* counts;
-  const float *color, *variance;
   int64_t frames;
-  const float* features;  // current, 16 floats per pixel
-  DeviceBuffer *scratch, *hist, *len;
-  bool* tp_valid;
-  float* tp_cam;
-  // the events around the last present's kernels and its time (rt2_tracer_present_time)
-  hipEvent_t *present_e0, *present_e1;
-  bool* present_pending;
-  double* present_ms;
+  // the estimate: the sums (LaunchDenoiseInputs divides and takes the variance; counts: adaptive sampling's, or
+  // null), or with accum null the resolved colour and variance of the mean (the gather's kernel has done both;
+  // they are copied)
+  const float *accum = nullptr, *moment2 = nullptr;
+  const uint32_t* counts = nullptr;
+  const float *color = nullptr, *variance = nullptr;
+  Chain(rt2_tracer* tracer, Recon& r, int w, int h, int64_t f) : t(tracer), recon(r), width(w), rows(h), frames(f) {}
   size_t n() const { return (size_t)width * (size_t)rows; }
+  float* head() const { return recon.d_scratch.get<float>(); }  // colour float3, then the variance of the mean
+  const float* features() const { return recon.d_features.get<float>(); }
 };
 
 static Chain LocalChain(rt2_tracer* t) {
-  return Chain{t, t->width, t->local_rows, t->d_accum.get<float>(), t->d_moment2.get<float>(),
-               t->adaptive_on ? t->d_counts.get<uint32_t>() : nullptr, nullptr, nullptr, t->frame_idx,
-               t->d_features.get<float>(), &t->d_dn_scratch, &t->d_tp_hist, &t->d_tp_len, &t->tp_valid, t->tp_cam,
-               &t->present_e0, &t->present_e1, &t->present_pending, &t->present_ms};
+  Chain c(t, t->recon, t->width, t->local_rows, t->frame_idx);
+  c.accum = t->d_accum.get<float>();
+  c.moment2 = t->d_moment2.get<float>();
+  if (t->adaptive_on) c.counts = t->d_counts.get<uint32_t>();
+  return c;
 }
 
-// The gathered image on its root r, whose estimate (rt2_tracer_gather_estimate) and whole-image features
-// (EnsureImageFeatures) are current.
+// The gathered image on its root r, whose estimate (rt2_tracer_gather_estimate) is current.
 static Chain ImageChain(rt2_tracer* r) {
-  return Chain{r, r->width, r->height, nullptr, nullptr, nullptr, r->d_image_nc.get<float>(),
-               r->d_image_var.get<float>(), r->estimate_frame, r->d_img_features.get<float>(), &r->d_img_scratch,
-               &r->d_img_hist, &r->d_img_len, &r->img_tp_valid, r->img_tp_cam, &r->img_present_e0, &r->img_present_e1,
-               &r->img_present_pending, &r->img_present_ms};
+  Chain c(r, r->image_recon, r->width, r->height, r->estimate_frame);
+  c.color = r->d_image_nc.get<float>();
+  c.variance = r->d_image_var.get<float>();
+  return c;
 }
 
-// The feature pass runs the stack traversal: a scene only the threaded program can render is refused.
-static int StackRefusal(const rt2_tracer* t) {
-  return Fail(RT2_ERR_INVALID, "features: the scene needs a traversal stack of " + std::to_string(t->max_stack) +
-                                   " entries (kernel has " + std::to_string(kTraversalStack) + ")");
-}
+// The part of the image a feature pass traces (the RenderParams fields of these names).
+struct Partition {
+  int local_rows, band_h, rank, world;
+};
 
-// The tracer's feature records on its device, traced again when the camera, the seed, the size or the
-// partition have changed since (Realloc drops the buffer). ev: events recorded around the pass, or null. Enqueued
-// on the tracer's stream; the host does not wait.
-static int EnsureFeatures(rt2_tracer* t, bool* launched, const EventPair* ev) {
-  *launched = false;
+// The feature records of `part` of the tracer's image in rc, on the tracer's device, traced again when the camera
+// or the seed have changed since (a change of size or partition drops the buffer: Realloc, FreeImage).
+// alloc_pixels: the records the buffer is allocated for. ev: events recorded around the pass, or null; launched
+// (or null): whether a pass ran. Enqueued on the tracer's stream; the host does not wait.
+static int EnsureFeatures(rt2_tracer* t, Recon& rc, const Partition& part, size_t alloc_pixels, const EventPair* ev,
+                          bool* launched) {
+  if (launched) *launched = false;
   if (!t->stack_ok) return StackRefusal(t);
-  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  const size_t n = (size_t)t->width * (size_t)part.local_rows;
   const CameraParams cam = t->camera.Params();
   if (n == 0) return RT2_OK;
-  if (t->d_features && t->features_valid && t->features_seed == t->seed &&
-      memcmp(&t->features_cam, &cam, sizeof(cam)) == 0)
+  if (rc.d_features && rc.features_valid && rc.features_seed == t->seed && memcmp(&rc.features_cam, &cam, sizeof(cam)) == 0)
     return RT2_OK;
   HIP_TRY(hipSetDevice(t->device));
-  if (!t->d_features) {
-    const size_t rows = (size_t)t->width * (size_t)AllocRows(t);
-    HIP_TRY(t->d_features.Alloc(rows * kDenoiseFeatureFloats * sizeof(float)));
+  if (!rc.d_features) {
+    HIP_TRY(rc.d_features.Alloc(alloc_pixels * kDenoiseFeatureFloats * sizeof(float)));
     NoteDeviceBytes(t);
   }
   RenderParams p;
   BaseParams(t, cam, &p);
+  p.local_rows = part.local_rows;
+  p.band_h = part.band_h;
+  p.rank = part.rank;
+  p.world = part.world;
   p.local_pixels = (uint32_t)n;
   if (ev) HIP_TRY(hipEventRecord(ev->e0, t->stream));
-  HIP_TRY(LaunchFeatures(p, t->d_features.get<float>(), t->stream));
+  HIP_TRY(LaunchFeatures(p, rc.d_features.get<float>(), t->stream));
   if (ev) HIP_TRY(hipEventRecord(ev->e1, t->stream));
-  t->features_valid = true;
-  t->features_cam = cam;
-  t->features_seed = t->seed;
-  *launched = true;
+  rc.features_valid = true;
+  rc.features_cam = cam;
+  rc.features_seed = t->seed;
+  if (launched) *launched = true;
   return RT2_OK;
+}
+
+// The tracer's own band, as BaseParams describes it; the buffer is as tall as the accumulation.
+static int LocalFeatures(rt2_tracer* t, const EventPair* ev, bool* launched) {
+  const Partition own{t->local_rows, t->band_h > 0 ? t->band_h : t->height, t->rank, t->world};
+  return EnsureFeatures(t, t->recon, own, (size_t)t->width * (size_t)AllocRows(t), ev, launched);
+}
+
+// The whole image on the root of a gathered image. The root traces every pixel itself: with world 1, rank 0 and
+// one band of the image's height, features_kernel's map from local to image rows is the identity.
+static int ImageFeatures(rt2_tracer* r) {
+  const Partition whole{r->height, r->height, 0, 1};
+  return EnsureFeatures(r, r->image_recon, whole, (size_t)r->width * (size_t)r->height, nullptr, nullptr);
 }
 
 static int FeaturesTimed(rt2_tracer* t) {
   EventPair ev(t);
   if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
   bool launched = false;
-  int rc = EnsureFeatures(t, &launched, &ev);
+  int rc = LocalFeatures(t, &ev, &launched);
   if (rc != RT2_OK || !launched) return rc;
   hipError_t e = hipStreamSynchronize(t->stream);
   t->host_waits++;
@@ -137,40 +181,74 @@ static int FeaturesTimed(rt2_tracer* t) {
   return RT2_OK;
 }
 
-// The whole-image feature records on the root of a gathered image, cached like EnsureFeatures' per (camera, seed;
-// FreeImage drops the buffer with the size). The root traces every pixel itself: with world 1, rank 0 and one
-// band of the image's height, features_kernel's map from local to image rows is the identity.
-static int EnsureImageFeatures(rt2_tracer* r) {
-  if (!r->stack_ok) return StackRefusal(r);
-  const size_t n = (size_t)r->width * (size_t)r->height;
-  const CameraParams cam = r->camera.Params();
+// What rt2_tracer_denoise and the temporal calls need of a one-GPU tracer after their own checks: moments, every
+// frame launched and finished, two frames, current features (timed).
+static int LocalEstimateReady(rt2_tracer* t, const char* call) {
+  if (!t->moments_on) return MomentsRefusal(call);
+  int rc = Sync(t);
+  if (rc != RT2_OK) return rc;
+  if (t->frame_idx < 2) return FramesRefusal(call);
+  return FeaturesTimed(t);
+}
+
+// rc's n feature records, copied to the host.
+static int ReadFeatures(rt2_tracer* t, const Recon& rc, size_t n, float* out) {
   if (n == 0) return RT2_OK;
-  if (r->d_img_features && r->img_features_valid && r->img_features_seed == r->seed &&
-      memcmp(&r->img_features_cam, &cam, sizeof(cam)) == 0)
-    return RT2_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  if (!r->d_img_features) {
-    HIP_TRY(r->d_img_features.Alloc(n * kDenoiseFeatureFloats * sizeof(float)));
-    NoteDeviceBytes(r);
-  }
-  RenderParams p;
-  BaseParams(r, cam, &p);
-  p.local_rows = r->height;
-  p.band_h = r->height;
-  p.rank = 0;
-  p.world = 1;
-  p.local_pixels = (uint32_t)n;
-  HIP_TRY(LaunchFeatures(p, r->d_img_features.get<float>(), r->stream));
-  r->img_features_valid = true;
-  r->img_features_cam = cam;
-  r->img_features_seed = r->seed;
+  HIP_TRY(hipSetDevice(t->device));
+  HIP_TRY(hipMemcpyAsync(out, rc.d_features.get<float>(), n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyDeviceToHost,
+                         t->stream));
+  t->host_waits++;
+  HIP_TRY(hipStreamSynchronize(t->stream));
   return RT2_OK;
 }
 
+// The way back to the host of every resolve: after the enqueues so far (e: their result), copies the resolved
+// colour and, where the pointers are not null, the variance behind it (d_color: a scratch's head) and the length
+// plane d_len, then waits for the stream. waits: the tracer's host_waits, or null (no tracer). An error is
+// reported under the call's name.
+static int ReadBack(hipError_t e, const float* d_color, const float* d_len, size_t n, float* out_color, float* out_variance,
+                    float* out_length, hipStream_t stream, uint64_t* waits, const char* call) {
+  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_variance)
+    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && out_length) e = hipMemcpyAsync(out_length, d_len, n * sizeof(float), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (waits) ++*waits;
+  if (e != hipSuccess) return HipFail(e, call);
+  return RT2_OK;
+}
+
+// What the *_buffers calls share: the checks of the image's size and of the device under the call's name, the
+// device made current, and a non-blocking stream that lasts as long as this object. Declared after the call's
+// DeviceBuffers: the stream goes before they are freed.
+struct BufferCall {
+  hipStream_t stream = nullptr;
+  BufferCall() = default;
+  BufferCall(const BufferCall&) = delete;
+  BufferCall& operator=(const BufferCall&) = delete;
+  ~BufferCall() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  static int CheckSize(const char* call, int width, int height) {
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
+      return Fail(RT2_ERR_INVALID, std::string(call) + ": need width, height > 0 and width * height below 2^26");
+    return RT2_OK;
+  }
+  int Open(const char* call, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
+    if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    const hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return HipFail(e, call);
+    return RT2_OK;
+  }
+};
+
 // The chain's scratch, grown to `need` bytes.
 static int EnsureScratch(const Chain& c, size_t need) {
-  if (need > c.scratch->bytes()) {
-    HIP_TRY(c.scratch->Grow(need));
+  if (need > c.recon.d_scratch.bytes()) {
+    HIP_TRY(c.recon.d_scratch.Grow(need));
     NoteDeviceBytes(c.t);
   }
   return RT2_OK;
@@ -180,7 +258,7 @@ static int EnsureScratch(const Chain& c, size_t need) {
 // the mean. Enqueued on the tracer's stream.
 static hipError_t EnqueueInputs(const Chain& c) {
   const size_t n = c.n();
-  float* d_color = c.scratch->get<float>();
+  float* d_color = c.head();
   if (c.accum) return LaunchDenoiseInputs(c.accum, c.moment2, c.counts, d_color, (uint32_t)n, c.frames, c.t->stream);
   hipError_t e = hipMemcpyAsync(d_color, c.color, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c.t->stream);
   if (e == hipSuccess)
@@ -188,169 +266,40 @@ static hipError_t EnqueueInputs(const Chain& c) {
   return e;
 }
 
-int rt2_tracer_features(rt2_tracer* t, float* out) {
-  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
-  if (IsMulti(t) || t->comm)
-    return Fail(RT2_ERR_INVALID, "features: not on a multi-GPU or joined tracer (a set_partition tracer works)");
-  int rc = FeaturesTimed(t);
-  if (rc != RT2_OK) return rc;
-  const size_t n = (size_t)t->width * (size_t)t->local_rows;
-  if (n) {
-    HIP_TRY(hipSetDevice(t->device));
-    HIP_TRY(hipMemcpyAsync(out, t->d_features.get<float>(), n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyDeviceToHost,
-                           t->stream));
-    t->host_waits++;
-    HIP_TRY(hipStreamSynchronize(t->stream));
-  }
-  return RT2_OK;
-}
-
-int rt2_tracer_denoise(rt2_tracer* t, const rt2_denoise_params* params, float* out_color, float* out_variance) {
-  if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
-  if (IsMulti(t) || t->comm || t->world != 1)
-    return Fail(RT2_ERR_INVALID, "denoise: needs an unpartitioned one-GPU tracer (world 1, not joined)");
-  DenoiseParams k;
-  int rc = DenoiseParamsOf(params, &k);
-  if (rc != RT2_OK) return rc;
-  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "denoise: moments not enabled (rt2_tracer_enable_moments)");
-  if ((rc = Sync(t)) != RT2_OK) return rc;
-  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "denoise needs at least 2 frames");
-  if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
-  const size_t n = (size_t)t->width * (size_t)t->local_rows;
-  if (n == 0) return RT2_OK;
-  HIP_TRY(hipSetDevice(t->device));
-  const Chain c = LocalChain(t);
-  if ((rc = EnsureScratch(c, DenoiseScratchBytes(n))) != RT2_OK) return rc;
-  EventPair ev(t);
-  if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
-  float* d_color = t->d_dn_scratch.get<float>();
-  hipError_t e = hipEventRecord(ev.e0, t->stream);
-  if (e == hipSuccess) e = EnqueueInputs(c);
-  if (e == hipSuccess) e = LaunchDenoise(d_color, t->d_features.get<float>(), t->width, t->local_rows, k, DenoiseLds(), t->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev.e1, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess && out_variance)
-    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  t->host_waits++;
-  if (e != hipSuccess) return HipFail(e, "denoise");
-  t->denoise_ms = EventMs(ev);
-  return RT2_OK;
-}
-
-int rt2_tracer_denoise_times(rt2_tracer* t, double* features_ms, double* denoise_ms) {
-  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
-  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "denoise_times: not on a multi-GPU tracer");
-  if (features_ms) *features_ms = t->features_ms;
-  if (denoise_ms) *denoise_ms = t->denoise_ms;
-  return RT2_OK;
-}
-
-int rt2_denoise_buffers(int device, int width, int height, const float* color, const float* variance,
-                        const float* features, const rt2_denoise_params* params, float* out_color, float* out_variance) {
-  if (!color || !variance || !features || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
-  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
-    return Fail(RT2_ERR_INVALID, "denoise_buffers: need width, height > 0 and width * height below 2^26");
-  DenoiseParams k;
-  int rc = DenoiseParamsOf(params, &k);
-  if (rc != RT2_OK) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
-  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
-  const size_t n = (size_t)width * (size_t)height;
-  DeviceBuffer scratch, feat;  // (freed in the reverse order)
-  hipStream_t stream = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = scratch.Alloc(DenoiseScratchBytes(n));
-  if (e == hipSuccess) e = feat.Alloc(n * kDenoiseFeatureFloats * sizeof(float));
-  float* d_color = scratch.get<float>();
-  float* d_feat = feat.get<float>();
-  if (e == hipSuccess) e = hipMemcpyAsync(d_color, color, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_color + 3 * n, variance, n * sizeof(float), hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_feat, features, n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = LaunchDenoise(d_color, d_feat, width, height, k, DenoiseLds(), stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && out_variance)
-    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (stream) (void)hipStreamDestroy(stream);
-  if (e != hipSuccess) return HipFail(e, "denoise_buffers");
-  return RT2_OK;
-}
-
-// ---- temporal reuse (rt2.h "Temporal reuse") ----
-void rt2_temporal_defaults(rt2_temporal_params* out) {
-  if (!out) return;
-  const TemporalParams d = TemporalDefaults();
-  out->max_history = d.max_history;
-  out->max_history_specular = d.max_history_specular;
-  out->min_normal_dot = d.min_normal_dot;
-  out->sigma_p = d.sigma_p;
-  out->sigma_a = d.sigma_a;
-}
-
-static int TemporalParamsOf(const rt2_temporal_params* p, TemporalParams* k) {
-  *k = TemporalDefaults();
-  if (p) *k = TemporalParams{p->max_history, p->max_history_specular, p->min_normal_dot, p->sigma_p, p->sigma_a};
-  if (!TemporalParamsValid(*k))
-    return Fail(RT2_ERR_INVALID, "temporal: need max_history, sigma_p, sigma_a finite and > 0, max_history_specular finite "
-                                 "and >= 0, min_normal_dot finite");
-  return RT2_OK;
-}
-
-static int EnqueueBlend(const Chain& c, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev);
-
-// The blend of the tracer's current estimate with its history, left on the device: colour and variance at
-// the head of the denoise scratch (where LaunchDenoise takes them), the length in d_tp_len. The checks of
-// rt2_tracer_denoise; push: the result then replaces the history. ev (or null): takes its two events from the
-// pool and records them around the kernels.
-static int TemporalBlend(rt2_tracer* t, const rt2_temporal_params* params, bool with_denoise, bool push, EventPair* ev) {
-  if (IsMulti(t) || t->comm || t->world != 1)
-    return Fail(RT2_ERR_INVALID, "temporal: needs an unpartitioned one-GPU tracer (world 1, not joined)");
-  TemporalParams k;
-  int rc = TemporalParamsOf(params, &k);
-  if (rc != RT2_OK) return rc;
-  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "temporal: moments not enabled (rt2_tracer_enable_moments)");
-  if ((rc = Sync(t)) != RT2_OK) return rc;
-  if (t->frame_idx < 2) return Fail(RT2_ERR_INVALID, "temporal needs at least 2 frames");
-  if ((rc = FeaturesTimed(t)) != RT2_OK) return rc;
-  const size_t n = (size_t)t->width * (size_t)t->local_rows;
-  if (n == 0) return RT2_OK;
-  return EnqueueBlend(LocalChain(t), k, with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float), push, ev);
-}
-
 // The blend's kernels, enqueued on the chain's stream over a tracer that has passed its checks, with its frames
-// launched (or its estimate gathered) and its features current; n > 0. The host does not wait. scratch_bytes:
-// what the scratch must hold at least.
+// launched (or its estimate gathered) and its features current; n > 0. The host does not wait. The blend of the
+// current estimate with the history is left on the device: colour and variance at the head of the scratch (where
+// LaunchDenoise takes them), the length in the chain's length plane; push: the result then replaces the history.
+// scratch_bytes: what the scratch must hold at least. ev (or null): takes its two events from the pool and records
+// them around the blend.
 static int EnqueueBlend(const Chain& c, const TemporalParams& k, size_t scratch_bytes, bool push, EventPair* ev) {
   rt2_tracer* t = c.t;
+  Recon& r = c.recon;
   const size_t n = c.n();
   int rc;
   HIP_TRY(hipSetDevice(t->device));
   if ((rc = EnsureScratch(c, scratch_bytes)) != RT2_OK) return rc;
-  if (!*c.hist) {
-    *c.tp_valid = false;
-    HIP_TRY(c.hist->Alloc(TemporalHistoryBytes(n)));
-    if (c.len->Alloc(n * sizeof(float)) != hipSuccess) {
-      c.hist->reset();
+  if (!r.d_hist) {
+    r.tp_valid = false;
+    HIP_TRY(r.d_hist.Alloc(TemporalHistoryBytes(n)));
+    if (r.d_len.Alloc(n * sizeof(float)) != hipSuccess) {
+      r.d_hist.reset();
       return Fail(RT2_ERR_HIP, "temporal: out of device memory");
     }
     NoteDeviceBytes(t);
   }
-  float* d_color = c.scratch->get<float>();
+  float* d_color = c.head();
   if (ev && !ev->Take()) return Fail(RT2_ERR_HIP, "event create failed");
   hipError_t e = ev ? hipEventRecord(ev->e0, t->stream) : hipSuccess;
   if (e == hipSuccess) e = EnqueueInputs(c);
   if (e == hipSuccess)
-    e = LaunchTemporalBlend(d_color, d_color + 3 * n, nullptr, c.counts, (float)c.frames, c.features,
-                            *c.tp_valid ? c.hist->get<void>() : nullptr, c.tp_cam, t->d_materials.get<float>(),
-                            t->n_materials, true, k, c.len->get<float>(), c.width, c.rows, t->stream);
+    e = LaunchTemporalBlend(d_color, d_color + 3 * n, nullptr, c.counts, (float)c.frames, c.features(),
+                            r.tp_valid ? r.d_hist.get<void>() : nullptr, r.tp_cam, t->d_materials.get<float>(),
+                            t->n_materials, true, k, r.d_len.get<float>(), c.width, c.rows, t->stream);
   if (e == hipSuccess && ev) e = hipEventRecord(ev->e1, t->stream);
   if (e == hipSuccess && push) {
-    *c.tp_valid = false;  // until the pack has run
-    e = LaunchTemporalPack(d_color, d_color + 3 * n, c.len->get<float>(), c.features, c.hist->get<void>(), (uint32_t)n,
+    r.tp_valid = false;  // until the pack has run
+    e = LaunchTemporalPack(d_color, d_color + 3 * n, r.d_len.get<float>(), c.features(), r.d_hist.get<void>(), (uint32_t)n,
                            t->stream);
   }
   if (e != hipSuccess) return HipFail(e, "temporal");
@@ -369,6 +318,175 @@ static void CameraWords(const CameraParams& p, float* out) {  // rt2_camera_para
   out[20] = (float)p.sqrt_spp;
 }
 
+// After a pushing blend (EnqueueBlend, push): the history is held, under the camera it was rendered with.
+static void HistoryPushed(const Chain& c) {
+  CameraWords(c.t->camera.Params(), c.recon.tp_cam);
+  c.recon.tp_valid = true;
+}
+
+// The chain's estimate blended into its history and kept as the history, before the camera moves on: blend and
+// pack are enqueued on the tracer's stream, the host does not wait (n > 0, as EnqueueBlend).
+static int PushHistory(const Chain& c, const TemporalParams& k) {
+  int rc = EnqueueBlend(c, k, c.n() * 4 * sizeof(float), true, nullptr);
+  if (rc == RT2_OK) HistoryPushed(c);
+  return rc;
+}
+
+// The chain of rt2.h from the inputs to the copy into out_rgba, enqueued on the chain's stream over a tracer that
+// has passed its checks, with its frames launched (or its estimate gathered) and its features current; n > 0.
+// Nothing here blocks the host.
+static int EnqueuePresent(const Chain& c, const PresentStages& st, uint8_t* out_rgba) {
+  rt2_tracer* t = c.t;
+  Recon& r = c.recon;
+  const size_t n = c.n();
+  int rc;
+  HIP_TRY(hipSetDevice(t->device));
+  // colour float3 and variance at the scratch's head, as the filter takes them; the RGBA8 words behind them, in
+  // the filter's first plane, which is free again once the filter's last kernel (unpack) has run
+  const size_t need = st.denoise ? DenoiseScratchBytes(n) : n * 5 * sizeof(float);
+  if ((rc = EnsureScratch(c, need)) != RT2_OK) return rc;
+  if (!r.present_e0 && hipEventCreate(&r.present_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  if (!r.present_e1 && hipEventCreate(&r.present_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  r.present_pending = false;
+  r.present_ms = -1.0;
+  HIP_TRY(hipEventRecord(r.present_e0, t->stream));
+  if (st.temporal) {
+    if ((rc = EnqueueBlend(c, st.tk, need, false, nullptr)) != RT2_OK) return rc;
+  } else {
+    HIP_TRY(EnqueueInputs(c));
+  }
+  float* d_color = c.head();
+  uint8_t* d_rgba = reinterpret_cast<uint8_t*>(d_color + 4 * n);
+  if (st.denoise) HIP_TRY(LaunchDenoise(d_color, c.features(), c.width, c.rows, st.dk, DenoiseLds(), t->stream));
+  HIP_TRY(LaunchPresent(d_color, d_rgba, (uint32_t)n, t->stream));
+  HIP_TRY(hipEventRecord(r.present_e1, t->stream));
+  r.present_pending = true;
+  HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, n * 4, hipMemcpyDeviceToHost, t->stream));
+  return RT2_OK;
+}
+
+// rt2_tracer_present_time over the chain's events: polls, never waits.
+static int PresentTime(const Chain& c, double* ms) {
+  Recon& r = c.recon;
+  if (r.present_pending) {
+    HIP_TRY(hipSetDevice(c.t->device));
+    const hipError_t q = hipEventQuery(r.present_e1);
+    if (q == hipSuccess) {
+      float f = -1.0f;
+      if (hipEventElapsedTime(&f, r.present_e0, r.present_e1) != hipSuccess) f = -1.0f;
+      r.present_ms = (double)f;
+      r.present_pending = false;
+    } else if (q != hipErrorNotReady) {
+      return HipFail(q, "present_time");
+    }
+  }
+  if (ms) *ms = r.present_pending ? -1.0 : r.present_ms;
+  return RT2_OK;
+}
+
+extern "C" {
+
+// ---- feature buffers and denoiser (rt2.h "Feature buffers and denoiser") ----
+void rt2_denoise_defaults(rt2_denoise_params* out) {
+  if (!out) return;
+  const DenoiseParams d = DenoiseDefaults();
+  out->iterations = d.iterations;
+  out->normal_power_log2 = d.normal_power_log2;
+  out->sigma_l = d.sigma_l;
+  out->sigma_p = d.sigma_p;
+  out->sigma_a = d.sigma_a;
+  out->eps_l = d.eps_l;
+}
+
+int rt2_tracer_features(rt2_tracer* t, float* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  if (IsMulti(t) || t->comm)
+    return Fail(RT2_ERR_INVALID, "features: not on a multi-GPU or joined tracer (a set_partition tracer works)");
+  int rc = FeaturesTimed(t);
+  if (rc != RT2_OK) return rc;
+  return ReadFeatures(t, t->recon, (size_t)t->width * (size_t)t->local_rows, out);
+}
+
+int rt2_tracer_denoise(rt2_tracer* t, const rt2_denoise_params* params, float* out_color, float* out_variance) {
+  if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  if (!OneGpu(t)) return OneGpuRefusal("denoise");
+  DenoiseParams k;
+  int rc = DenoiseParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  if ((rc = LocalEstimateReady(t, "denoise")) != RT2_OK) return rc;
+  const Chain c = LocalChain(t);
+  const size_t n = c.n();
+  if (n == 0) return RT2_OK;
+  HIP_TRY(hipSetDevice(t->device));
+  if ((rc = EnsureScratch(c, DenoiseScratchBytes(n))) != RT2_OK) return rc;
+  EventPair ev(t);
+  if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
+  hipError_t e = hipEventRecord(ev.e0, t->stream);
+  if (e == hipSuccess) e = EnqueueInputs(c);
+  if (e == hipSuccess) e = LaunchDenoise(c.head(), c.features(), c.width, c.rows, k, DenoiseLds(), t->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev.e1, t->stream);
+  rc = ReadBack(e, c.head(), nullptr, n, out_color, out_variance, nullptr, t->stream, &t->host_waits, "denoise");
+  if (rc != RT2_OK) return rc;
+  t->denoise_ms = EventMs(ev);
+  return RT2_OK;
+}
+
+int rt2_tracer_denoise_times(rt2_tracer* t, double* features_ms, double* denoise_ms) {
+  if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "denoise_times: not on a multi-GPU tracer");
+  if (features_ms) *features_ms = t->features_ms;
+  if (denoise_ms) *denoise_ms = t->denoise_ms;
+  return RT2_OK;
+}
+
+int rt2_denoise_buffers(int device, int width, int height, const float* color, const float* variance,
+                        const float* features, const rt2_denoise_params* params, float* out_color, float* out_variance) {
+  if (!color || !variance || !features || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
+  int rc = BufferCall::CheckSize("denoise_buffers", width, height);
+  if (rc != RT2_OK) return rc;
+  DenoiseParams k;
+  if ((rc = DenoiseParamsOf(params, &k)) != RT2_OK) return rc;
+  DeviceBuffer scratch, feat;  // (freed in the reverse order)
+  BufferCall call;
+  if ((rc = call.Open("denoise_buffers", device)) != RT2_OK) return rc;
+  hipStream_t stream = call.stream;
+  const size_t n = (size_t)width * (size_t)height;
+  hipError_t e = scratch.Alloc(DenoiseScratchBytes(n));
+  if (e == hipSuccess) e = feat.Alloc(n * kDenoiseFeatureFloats * sizeof(float));
+  float* d_color = scratch.get<float>();
+  float* d_feat = feat.get<float>();
+  if (e == hipSuccess) e = hipMemcpyAsync(d_color, color, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_color + 3 * n, variance, n * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_feat, features, n * kDenoiseFeatureFloats * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = LaunchDenoise(d_color, d_feat, width, height, k, DenoiseLds(), stream);
+  return ReadBack(e, d_color, nullptr, n, out_color, out_variance, nullptr, stream, nullptr, "denoise_buffers");
+}
+
+// ---- temporal reuse (rt2.h "Temporal reuse") ----
+void rt2_temporal_defaults(rt2_temporal_params* out) {
+  if (!out) return;
+  const TemporalParams d = TemporalDefaults();
+  out->max_history = d.max_history;
+  out->max_history_specular = d.max_history_specular;
+  out->min_normal_dot = d.min_normal_dot;
+  out->sigma_p = d.sigma_p;
+  out->sigma_a = d.sigma_a;
+}
+
+// The blend of the tracer's current estimate with its history, left on the device (EnqueueBlend), after the checks
+// of rt2_tracer_denoise.
+static int TemporalBlend(rt2_tracer* t, const rt2_temporal_params* params, bool with_denoise, bool push, EventPair* ev) {
+  if (!OneGpu(t)) return OneGpuRefusal("temporal");
+  TemporalParams k;
+  int rc = TemporalParamsOf(params, &k);
+  if (rc != RT2_OK) return rc;
+  if ((rc = LocalEstimateReady(t, "temporal")) != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  return EnqueueBlend(LocalChain(t), k, with_denoise ? DenoiseScratchBytes(n) : n * 4 * sizeof(float), push, ev);
+}
+
 int rt2_tracer_temporal_resolve(rt2_tracer* t, const rt2_temporal_params* params, int denoise, const rt2_denoise_params* dparams,
                                 float* out_color, float* out_variance, float* out_length) {
   if (!t || !out_color) return Fail(RT2_ERR_INVALID, "null argument");
@@ -377,19 +495,14 @@ int rt2_tracer_temporal_resolve(rt2_tracer* t, const rt2_temporal_params* params
   if (rc != RT2_OK) return rc;
   EventPair ev(t);
   if ((rc = TemporalBlend(t, params, denoise != 0, false, &ev)) != RT2_OK) return rc;
-  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  const Chain c = LocalChain(t);
+  const size_t n = c.n();
   if (n == 0) return RT2_OK;
-  float* d_color = t->d_dn_scratch.get<float>();
   hipError_t e = hipSuccess;
-  if (denoise) e = LaunchDenoise(d_color, t->d_features.get<float>(), t->width, t->local_rows, dk, DenoiseLds(), t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess && out_variance)
-    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess && out_length)
-    e = hipMemcpyAsync(out_length, t->d_tp_len.get<float>(), n * sizeof(float), hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  t->host_waits++;
-  if (e != hipSuccess) return HipFail(e, "temporal_resolve");
+  if (denoise) e = LaunchDenoise(c.head(), c.features(), c.width, c.rows, dk, DenoiseLds(), t->stream);
+  rc = ReadBack(e, c.head(), c.recon.d_len.get<float>(), n, out_color, out_variance, out_length, t->stream, &t->host_waits,
+                "temporal_resolve");
+  if (rc != RT2_OK) return rc;
   t->temporal_ms = EventMs(ev);
   return RT2_OK;
 }
@@ -402,16 +515,14 @@ int rt2_tracer_temporal_push(rt2_tracer* t, const rt2_temporal_params* params) {
   hipError_t e = hipStreamSynchronize(t->stream);
   t->host_waits++;
   if (e != hipSuccess) return HipFail(e, "temporal_push");
-  CameraWords(t->camera.Params(), t->tp_cam);
-  t->tp_valid = true;
+  HistoryPushed(LocalChain(t));
   return RT2_OK;
 }
 
 int rt2_tracer_temporal_clear(rt2_tracer* t) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
-  if (IsMulti(t) || t->comm || t->world != 1)
-    return Fail(RT2_ERR_INVALID, "temporal: needs an unpartitioned one-GPU tracer (world 1, not joined)");
-  t->tp_valid = false;
+  if (!OneGpu(t)) return OneGpuRefusal("temporal");
+  t->recon.tp_valid = false;
   return RT2_OK;
 }
 
@@ -430,25 +541,21 @@ int rt2_temporal_buffers(int device, int width, int height, const float* color, 
   if (!color || !variance || !length || !features || !hist_color || !hist_variance || !hist_length || !hist_features ||
       !hist_camera || !out_color)
     return Fail(RT2_ERR_INVALID, "null argument");
-  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
-    return Fail(RT2_ERR_INVALID, "temporal_buffers: need width, height > 0 and width * height below 2^26");
+  int rc = BufferCall::CheckSize("temporal_buffers", width, height);
+  if (rc != RT2_OK) return rc;
   if (n_materials < 0 || n_materials >= 1 << 24)
     return Fail(RT2_ERR_INVALID, "temporal_buffers: need 0 <= n_materials < 2^24");
   TemporalParams k;
-  int rc = TemporalParamsOf(params, &k);
-  if (rc != RT2_OK) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
-  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
+  if ((rc = TemporalParamsOf(params, &k)) != RT2_OK) return rc;
+  // cur / old: colour float3, variance, length; then the two feature images, the history planes, the table
+  DeviceBuffer cur, old, feat, hfeat, out_len, hist, mat;  // (freed in the reverse order)
+  BufferCall call;
+  if ((rc = call.Open("temporal_buffers", device)) != RT2_OK) return rc;
+  hipStream_t stream = call.stream;
   const size_t n = (size_t)width * (size_t)height;
   const size_t nf = n * kDenoiseFeatureFloats * sizeof(float);
   const bool mats = materials && n_materials > 0;
-  // cur / old: colour float3, variance, length; then the two feature images, the history planes, the table
-  DeviceBuffer cur, old, feat, hfeat, out_len, hist, mat;  // (freed in the reverse order)
-  hipStream_t stream = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = cur.Alloc(n * 5 * sizeof(float));
+  hipError_t e = cur.Alloc(n * 5 * sizeof(float));
   if (e == hipSuccess) e = old.Alloc(n * 5 * sizeof(float));
   if (e == hipSuccess) e = feat.Alloc(nf);
   if (e == hipSuccess) e = hfeat.Alloc(nf);
@@ -474,14 +581,7 @@ int rt2_temporal_buffers(int device, int width, int height, const float* color, 
   if (e == hipSuccess)
     e = LaunchTemporalBlend(d_cur, d_cur + 3 * n, d_cur + 4 * n, nullptr, 0.0f, d_feat, d_hist, hist_camera, d_mat,
                             mats ? n_materials : 0, false, k, d_out_len, width, height, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_cur, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && out_variance)
-    e = hipMemcpyAsync(out_variance, d_cur + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && out_length) e = hipMemcpyAsync(out_length, d_out_len, n * sizeof(float), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (stream) (void)hipStreamDestroy(stream);
-  if (e != hipSuccess) return HipFail(e, "temporal_buffers");
-  return RT2_OK;
+  return ReadBack(e, d_cur, d_out_len, n, out_color, out_variance, out_length, stream, nullptr, "temporal_buffers");
 }
 
 // ---- presenting reconstructed frames (rt2.h "Presenting reconstructed frames") ----
@@ -493,79 +593,22 @@ void rt2_present_defaults(rt2_present_params* out) {
   rt2_denoise_defaults(&out->dp);
 }
 
-// The chain of rt2.h from the inputs to the copy into out_rgba, enqueued on the chain's stream over a tracer that
-// has passed its checks, with its frames launched (or its estimate gathered) and its features current; n > 0.
-// Nothing here blocks the host.
-static int EnqueuePresent(const Chain& c, bool temporal, const TemporalParams& tk, bool denoise, const DenoiseParams& dk,
-                          uint8_t* out_rgba) {
-  rt2_tracer* t = c.t;
-  const size_t n = c.n();
-  int rc;
-  HIP_TRY(hipSetDevice(t->device));
-  // colour float3 and variance at the scratch's head, as the filter takes them; the RGBA8 words behind them, in
-  // the filter's first plane, which is free again once the filter's last kernel (unpack) has run
-  const size_t need = denoise ? DenoiseScratchBytes(n) : n * 5 * sizeof(float);
-  if ((rc = EnsureScratch(c, need)) != RT2_OK) return rc;
-  if (!*c.present_e0 && hipEventCreate(c.present_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  if (!*c.present_e1 && hipEventCreate(c.present_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  *c.present_pending = false;
-  *c.present_ms = -1.0;
-  HIP_TRY(hipEventRecord(*c.present_e0, t->stream));
-  if (temporal) {
-    if ((rc = EnqueueBlend(c, tk, need, false, nullptr)) != RT2_OK) return rc;
-  } else {
-    HIP_TRY(EnqueueInputs(c));
-  }
-  float* d_color = c.scratch->get<float>();
-  uint8_t* d_rgba = reinterpret_cast<uint8_t*>(d_color + 4 * n);
-  if (denoise) HIP_TRY(LaunchDenoise(d_color, c.features, c.width, c.rows, dk, DenoiseLds(), t->stream));
-  HIP_TRY(LaunchPresent(d_color, d_rgba, (uint32_t)n, t->stream));
-  HIP_TRY(hipEventRecord(*c.present_e1, t->stream));
-  *c.present_pending = true;
-  HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, n * 4, hipMemcpyDeviceToHost, t->stream));
-  return RT2_OK;
-}
-
-// rt2_tracer_present_time over the chain's events: polls, never waits.
-static int PresentTime(const Chain& c, double* ms) {
-  if (*c.present_pending) {
-    HIP_TRY(hipSetDevice(c.t->device));
-    const hipError_t q = hipEventQuery(*c.present_e1);
-    if (q == hipSuccess) {
-      float f = -1.0f;
-      if (hipEventElapsedTime(&f, *c.present_e0, *c.present_e1) != hipSuccess) f = -1.0f;
-      *c.present_ms = (double)f;
-      *c.present_pending = false;
-    } else if (q != hipErrorNotReady) {
-      return HipFail(q, "present_time");
-    }
-  }
-  if (ms) *ms = *c.present_pending ? -1.0 : *c.present_ms;
-  return RT2_OK;
-}
-
-static const char kPresentTracerMsg[] = "present: needs an unpartitioned one-GPU tracer (world 1, not joined)";
-
 // The chain of rt2.h, enqueued on the tracer's stream; every refusal comes before the first enqueue. Nothing
 // here blocks the host: no stream or event synchronisation, no synchronous copy (growing a buffer at the first
 // call is the exception every first call has).
 int rt2_tracer_present_async(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
   if (!t || !out_rgba) return Fail(RT2_ERR_INVALID, "null argument");
-  if (IsMulti(t) || t->comm || t->world != 1) return Fail(RT2_ERR_INVALID, kPresentTracerMsg);
-  const bool temporal = params ? params->temporal != 0 : true;
-  const bool denoise = params ? params->denoise != 0 : true;
-  TemporalParams tk = TemporalDefaults();
-  DenoiseParams dk = DenoiseDefaults();
-  int rc;
-  if (temporal && (rc = TemporalParamsOf(params ? &params->tp : nullptr, &tk)) != RT2_OK) return rc;
-  if (denoise && (rc = DenoiseParamsOf(params ? &params->dp : nullptr, &dk)) != RT2_OK) return rc;
-  if (!t->moments_on) return Fail(RT2_ERR_INVALID, "present: moments not enabled (rt2_tracer_enable_moments)");
-  if (t->frame_idx + t->queued < 2) return Fail(RT2_ERR_INVALID, "present needs at least 2 frames");
+  if (!OneGpu(t)) return OneGpuRefusal("present");
+  PresentStages st;
+  int rc = PresentStagesOf(params, &st);
+  if (rc != RT2_OK) return rc;
+  if (!t->moments_on) return MomentsRefusal("present");
+  if (t->frame_idx + t->queued < 2) return FramesRefusal("present");
   if ((rc = Flush(t)) != RT2_OK) return rc;
-  bool launched = false;
-  if ((rc = EnsureFeatures(t, &launched, nullptr)) != RT2_OK) return rc;
-  if ((size_t)t->width * (size_t)t->local_rows == 0) return RT2_OK;
-  return EnqueuePresent(LocalChain(t), temporal, tk, denoise, dk, out_rgba);
+  if ((rc = LocalFeatures(t, nullptr, nullptr)) != RT2_OK) return rc;
+  const Chain c = LocalChain(t);
+  if (c.n() == 0) return RT2_OK;
+  return EnqueuePresent(c, st, out_rgba);
 }
 
 int rt2_tracer_present(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
@@ -584,11 +627,8 @@ int rt2_tracer_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, const rt2_
     // the push of rt2_tracer_temporal_push without its wait: blend and pack are on the tracer's stream, and so
     // is every memset of ResetFrame below, so the sums are zeroed after the pack's inputs kernel has read them
     if ((rc = Flush(t)) != RT2_OK) return rc;
-    bool launched = false;
-    if ((rc = EnsureFeatures(t, &launched, nullptr)) != RT2_OK) return rc;
-    if ((rc = EnqueueBlend(LocalChain(t), k, n * 4 * sizeof(float), true, nullptr)) != RT2_OK) return rc;
-    CameraWords(t->camera.Params(), t->tp_cam);
-    t->tp_valid = true;
+    if ((rc = LocalFeatures(t, nullptr, nullptr)) != RT2_OK) return rc;
+    if ((rc = PushHistory(LocalChain(t), k)) != RT2_OK) return rc;
   }
   if ((rc = rt2_tracer_set_camera(t, cam)) != RT2_OK) return rc;
   return rt2_tracer_reset(t);
@@ -596,77 +636,50 @@ int rt2_tracer_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, const rt2_
 
 int rt2_tracer_present_time(rt2_tracer* t, double* ms) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
-  if (IsMulti(t) || t->comm || t->world != 1) return Fail(RT2_ERR_INVALID, kPresentTracerMsg);
+  if (!OneGpu(t)) return OneGpuRefusal("present");
   return PresentTime(LocalChain(t), ms);
 }
 
 int rt2_present_buffers(int device, int width, int height, const float* color, uint8_t* out_rgba) {
   if (!color || !out_rgba) return Fail(RT2_ERR_INVALID, "null argument");
-  if (width <= 0 || height <= 0 || (int64_t)width * height >= (int64_t)1 << 26)
-    return Fail(RT2_ERR_INVALID, "present_buffers: need width, height > 0 and width * height below 2^26");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return Fail(RT2_ERR_HIP, "no HIP device available");
-  if (device < 0 || device >= ndev) return Fail(RT2_ERR_INVALID, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
-  const size_t n = (size_t)width * (size_t)height;
+  int rc = BufferCall::CheckSize("present_buffers", width, height);
+  if (rc != RT2_OK) return rc;
   DeviceBuffer col, px;  // (freed in the reverse order)
-  hipStream_t stream = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = col.Alloc(n * 3 * sizeof(float));
+  BufferCall call;
+  if ((rc = call.Open("present_buffers", device)) != RT2_OK) return rc;
+  hipStream_t stream = call.stream;
+  const size_t n = (size_t)width * (size_t)height;
+  hipError_t e = col.Alloc(n * 3 * sizeof(float));
   if (e == hipSuccess) e = px.Alloc(n * 4);
   if (e == hipSuccess) e = hipMemcpyAsync(col.get<float>(), color, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) e = LaunchPresent(col.get<float>(), px.get<void>(), (uint32_t)n, stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, px.get<uint8_t>(), n * 4, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (stream) (void)hipStreamDestroy(stream);
   if (e != hipSuccess) return HipFail(e, "present_buffers");
   return RT2_OK;
 }
 
 // ---- reconstructing the gathered image (rt2.h "Reconstructing the gathered image") ----
-// The stages a rt2_present_params switches on and their parameters, checked only for those stages.
-struct PresentStages {
-  bool temporal = true, denoise = true;
-  TemporalParams tk = TemporalDefaults();
-  DenoiseParams dk = DenoiseDefaults();
-};
-static int PresentStagesOf(const rt2_present_params* params, PresentStages* s) {
-  int rc;
-  if (params) {
-    s->temporal = params->temporal != 0;
-    s->denoise = params->denoise != 0;
-  }
-  if (s->temporal && (rc = TemporalParamsOf(params ? &params->tp : nullptr, &s->tk)) != RT2_OK) return rc;
-  if (s->denoise && (rc = DenoiseParamsOf(params ? &params->dp : nullptr, &s->dk)) != RT2_OK) return rc;
-  return RT2_OK;
-}
+static const char kImageRankMsg[] = "the gathered image lives on rank 0";
 
 // The root of the gathered image, with the estimate of the current FrameIdx() and the whole-image features
 // enqueued on its stream. Every refusal comes before the first enqueue.
 static int ImageReady(rt2_tracer* t, rt2_tracer** root) {
   const rt2_tracer* first = IsMulti(t) ? t->parts[0] : t;
-  if (first->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  if (first->rank != 0) return Fail(RT2_ERR_INVALID, kImageRankMsg);
   if (!first->stack_ok) return StackRefusal(first);
   int rc = CurrentEstimate(t, false, root);
   if (rc != RT2_OK) return rc;
-  return EnsureImageFeatures(*root);
+  return ImageFeatures(*root);
 }
 
 int rt2_tracer_image_features(rt2_tracer* t, float* out) {
   if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
   rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
-  if (r->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
-  int rc = EnsureImageFeatures(r);
+  if (r->rank != 0) return Fail(RT2_ERR_INVALID, kImageRankMsg);
+  int rc = ImageFeatures(r);
   if (rc != RT2_OK) return rc;
-  const size_t n = (size_t)r->width * (size_t)r->height;
-  if (n) {
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipMemcpyAsync(out, r->d_img_features.get<float>(), n * kDenoiseFeatureFloats * sizeof(float),
-                           hipMemcpyDeviceToHost, r->stream));
-    r->host_waits++;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-  }
-  return RT2_OK;
+  return ReadFeatures(r, r->image_recon, (size_t)r->width * (size_t)r->height, out);
 }
 
 int rt2_tracer_image_resolve(rt2_tracer* t, const rt2_present_params* params, float* out_color, float* out_variance,
@@ -688,18 +701,11 @@ int rt2_tracer_image_resolve(rt2_tracer* t, const rt2_present_params* params, fl
     if ((rc = EnsureScratch(c, need)) != RT2_OK) return rc;
     HIP_TRY(EnqueueInputs(c));
   }
-  float* d_color = c.scratch->get<float>();
   hipError_t e = hipSuccess;
-  if (st.denoise) e = LaunchDenoise(d_color, c.features, c.width, c.rows, st.dk, DenoiseLds(), r->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_color, d_color, n * 3 * sizeof(float), hipMemcpyDeviceToHost, r->stream);
-  if (e == hipSuccess && out_variance)
-    e = hipMemcpyAsync(out_variance, d_color + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, r->stream);
-  if (e == hipSuccess && out_length && st.temporal)
-    e = hipMemcpyAsync(out_length, c.len->get<float>(), n * sizeof(float), hipMemcpyDeviceToHost, r->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-  r->host_waits++;
-  if (e != hipSuccess) return HipFail(e, "image_resolve");
-  return RT2_OK;
+  if (st.denoise) e = LaunchDenoise(c.head(), c.features(), c.width, c.rows, st.dk, DenoiseLds(), r->stream);
+  // the length plane is the blend's: with the temporal stage off it is not copied (out_length is left untouched)
+  return ReadBack(e, c.head(), c.recon.d_len.get<float>(), n, out_color, out_variance, st.temporal ? out_length : nullptr,
+                  r->stream, &r->host_waits, "image_resolve");
 }
 
 int rt2_tracer_image_present_async(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
@@ -711,7 +717,7 @@ int rt2_tracer_image_present_async(rt2_tracer* t, const rt2_present_params* para
   if ((rc = ImageReady(t, &r)) != RT2_OK) return rc;
   const Chain c = ImageChain(r);
   if (c.n() == 0) return RT2_OK;
-  return EnqueuePresent(c, st.temporal, st.tk, st.denoise, st.dk, out_rgba);
+  return EnqueuePresent(c, st, out_rgba);
 }
 
 int rt2_tracer_image_present(rt2_tracer* t, const rt2_present_params* params, uint8_t* out_rgba) {
@@ -738,10 +744,8 @@ int rt2_tracer_image_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, cons
     rt2_tracer* r = nullptr;
     if ((rc = CurrentEstimate(t, true, &r)) != RT2_OK) return rc;
     if (r->rank == 0) {
-      if ((rc = EnsureImageFeatures(r)) != RT2_OK) return rc;
-      if ((rc = EnqueueBlend(ImageChain(r), k, n * 4 * sizeof(float), true, nullptr)) != RT2_OK) return rc;
-      CameraWords(r->camera.Params(), r->img_tp_cam);
-      r->img_tp_valid = true;
+      if ((rc = ImageFeatures(r)) != RT2_OK) return rc;
+      if ((rc = PushHistory(ImageChain(r), k)) != RT2_OK) return rc;
     }
   }
   if ((rc = rt2_tracer_set_camera(t, cam)) != RT2_OK) return rc;
@@ -751,7 +755,7 @@ int rt2_tracer_image_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, cons
 int rt2_tracer_image_present_time(rt2_tracer* t, double* ms) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
   rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
-  if (r->rank != 0) return Fail(RT2_ERR_INVALID, "the gathered image lives on rank 0");
+  if (r->rank != 0) return Fail(RT2_ERR_INVALID, kImageRankMsg);
   return PresentTime(ImageChain(r), ms);
 }
 }  // extern "C"

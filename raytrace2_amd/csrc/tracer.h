@@ -119,6 +119,55 @@ struct rt2_scene {
   rt2::CompiledScene compiled;
 };
 
+namespace rt2::detail {
+
+// The reconstruction state of one image: a one-GPU tracer's local rows, or the gathered image on its root (the
+// tracer holds one of each; capi_filter.cpp runs the same chain over either). Every buffer is allocated at the
+// first call that needs it. The cached feature records (rt2.h "Feature buffers and denoiser") with the launch
+// values they were traced under; the filter's scratch planes, whose head holds the chain's colour and variance;
+// temporal reuse (rt2.h "Temporal reuse"): the packed history (temporal.hip's four planes) and the blend's length
+// plane, whether a history is held and the camera words it was pushed under; presenting (rt2.h "Presenting
+// reconstructed frames"): the events around the last present's kernels (created at the first present, re-recorded
+// by every later one), whether that present's time is still to be read from them (rt2_tracer_present_time polls,
+// never waits), and the last time read (-1: none).
+struct Recon {
+  DeviceBuffer d_features;  // 16 floats per pixel
+  bool features_valid = false;
+  CameraParams features_cam;
+  uint64_t features_seed = 0;
+  DeviceBuffer d_scratch;
+  DeviceBuffer d_hist;
+  DeviceBuffer d_len;
+  bool tp_valid = false;
+  float tp_cam[kTemporalCameraWords] = {};
+  hipEvent_t present_e0 = nullptr, present_e1 = nullptr;
+  bool present_pending = false;
+  double present_ms = -1.0;
+
+  // Its device buffers, listed once, in the order they are freed. R: Recon or const Recon.
+  template <typename R, typename Fn>
+  static void ForBuffers(R& r, Fn&& f) {
+    for (auto* d : {&r.d_features, &r.d_scratch, &r.d_hist, &r.d_len}) f(*d);
+  }
+  // Drops the buffers, and the records and the history with them (a resize); the present events stay.
+  void Free() {
+    ForBuffers(*this, [](DeviceBuffer& d) { d.reset(); });
+    features_valid = false;
+    tp_valid = false;
+  }
+  size_t Bytes() const {
+    size_t b = 0;
+    ForBuffers(*this, [&b](const DeviceBuffer& d) { b += d.bytes(); });
+    return b;
+  }
+  void DestroyEvents() {  // ~rt2_tracer, at the events' place in its order
+    if (present_e0) (void)hipEventDestroy(present_e0);
+    if (present_e1) (void)hipEventDestroy(present_e1);
+  }
+};
+
+}  // namespace rt2::detail
+
 struct rt2_tracer {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -185,30 +234,11 @@ struct rt2_tracer {
   rt2::DeviceBuffer d_slot_of;
   rt2::DeviceBuffer d_ad_scratch;  // wg counts (uint2), wg offsets, classify partials, totals
   uint32_t n_active = 0;
-  // feature buffers and denoiser (rt2.h "Feature buffers and denoiser"), allocated at the first call: the
-  // cached feature records (16 floats per local pixel) with the launch values they were traced under, the
-  // filter's scratch planes, and the GPU times of the last feature pass and the last denoise (-1: none)
-  rt2::DeviceBuffer d_features;
-  bool features_valid = false;
-  rt2::CameraParams features_cam;
-  uint64_t features_seed = 0;
-  rt2::DeviceBuffer d_dn_scratch;
-  double features_ms = -1.0, denoise_ms = -1.0;
-  // temporal reuse (rt2.h "Temporal reuse"), allocated at the first call: the packed history (temporal.hip's
-  // four planes) and the blend's length plane; whether a history is held and the camera words it was pushed
-  // under; the GPU time of the last resolve's temporal kernels (-1: none)
-  rt2::DeviceBuffer d_tp_hist;
-  rt2::DeviceBuffer d_tp_len;
-  bool tp_valid = false;
-  float tp_cam[rt2::kTemporalCameraWords] = {};
+  // the reconstruction of the local rows (Recon above) and the GPU times of the last feature pass, the last
+  // denoise and the last resolve's temporal kernels (-1: none), which only the local calls report
+  rt2::detail::Recon recon;
+  double features_ms = -1.0, denoise_ms = -1.0, temporal_ms = -1.0;
   int n_materials = 0;  // materials in d_materials
-  double temporal_ms = -1.0;
-  // presenting (rt2.h "Presenting reconstructed frames"): the events around the last present's kernels (created
-  // at the first present, re-recorded by every later one), whether that present's time is still to be read from
-  // them (rt2_tracer_present_time polls, never waits), and the last time read (-1: none)
-  hipEvent_t present_e0 = nullptr, present_e1 = nullptr;
-  bool present_pending = false;
-  double present_ms = -1.0;
   rt2::DeviceBuffer d_work;  // one work counter per launch slot (words 0 and 16)
   rt2::DeviceBuffer d_stats;
   bool stats_on = false;
@@ -290,26 +320,13 @@ struct rt2_tracer {
   uint64_t gathers = 0;
   double gather_ms = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> gpending;  // per-gather timing events
-  // root: the reconstruction of the gathered image (rt2.h "Reconstructing the gathered image"), each buffer
-  // allocated at the first call that needs it: the gathered stacks of the sums of squares and the variance of
-  // the mean in image order with the frame index they are of (-1: none); the whole-image feature records with
-  // the launch values they were traced under; the chain's scratch, history and length plane with the history's
-  // camera words; the events and time of the last image present (as present_e0 .. present_ms above)
+  // root: the gathered stacks of the sums of squares and the variance of the mean in image order
+  // (rt2_tracer_gather_estimate), allocated at the first call, with the frame index they are of (-1: none); and
+  // the reconstruction of the gathered image (rt2.h "Reconstructing the gathered image")
   rt2::DeviceBuffer d_stacks2;       // [world][max_rows][W] float3
   rt2::DeviceBuffer d_image_var;     // [H][W] float
   int64_t estimate_frame = -1;
-  rt2::DeviceBuffer d_img_features;  // [H][W] 16 floats
-  bool img_features_valid = false;
-  rt2::CameraParams img_features_cam;
-  uint64_t img_features_seed = 0;
-  rt2::DeviceBuffer d_img_scratch;
-  rt2::DeviceBuffer d_img_hist;
-  rt2::DeviceBuffer d_img_len;
-  bool img_tp_valid = false;
-  float img_tp_cam[rt2::kTemporalCameraWords] = {};
-  hipEvent_t img_present_e0 = nullptr, img_present_e1 = nullptr;
-  bool img_present_pending = false;
-  double img_present_ms = -1.0;
+  rt2::detail::Recon image_recon;
   // image readbacks to the host (rt2_tracer_image_*): count and device-to-host copy time
   uint64_t readbacks = 0;
   double readback_ms = 0;

@@ -260,3 +260,69 @@ def test_device_bytes_peak_is_the_sum_of_the_buffers(have_gpu, w, h):
     tr.OnResize((w, h))
     check(tr, BOOK1_SCENE_BYTES + n * 16, "book 1, fresh")
     tr.close()
+
+
+@pytest.mark.parametrize("size,resized", [((64, 48), (96, 80)), ((290, 201), (500, 365))])
+def test_device_bytes_peak_counts_the_gathered_image_and_its_reconstruction(have_gpu, size, resized):
+    """The root of two parts on one GPU (stats() of a multi tracer is the largest part's, the root's): state by
+    state, device_bytes_peak is the running maximum of the documented list, the gathered image's six
+    reconstruction buffers included; and a resize drops every one of them. As above, the parts are created at the
+    scene's 600 x 600, which is the mark until a larger state: at 64 x 48 nothing rises above it (the mark itself
+    is what is checked), at 290 x 201 every state does, and its resize to 500 x 365 is large enough that the new
+    size's list without any reconstruction buffer is above everything the old size held, so a buffer that
+    survived the resize at its old size would show as an excess."""
+    from raytrace2_amd import local_rows
+    from raytrace2_amd.dist import band_rows_max
+    sc = R.Scene(scene_path("cornell_box_original"), R.DEFAULT_SEED)
+    scene = CORNELL_SCENE_BYTES + CORNELL_FLAT_BYTES
+    peak = scene + 600 * 600 * 16
+
+    def rendered(w, h):
+        """What the root holds after 2 frames with moments on: its band's sums, pixels and sums of squares (as
+        tall as the largest rank's band), and one launch slot: an octet of frames of float3 samples of its own
+        rows, and the table of two one-frame chunks and the sentinel."""
+        rows, own = band_rows_max(h, 2, 2), len(local_rows(h, 2, 0, 2))
+        return scene + w * rows * 28 + 8 * w * own * 12 + 24
+
+    def gathered(w, h):
+        """+ the two gathered stacks (sums, sums of squares: capi_multi.cpp EnsureImage, EnsureEstimate), the image
+        (float3 sum, float3 mean, RGBA8) and the variance plane."""
+        return rendered(w, h) + 2 * (2 * band_rows_max(h, 2, 2) * w * 12) + w * h * 28 + w * h * 4
+
+    def check(now, what):
+        nonlocal peak
+        peak = max(peak, now)
+        got = tr.stats()["device_bytes_peak"]
+        print(f"{w}x{h} {what}: held {now}, peak {got}")
+        assert got == peak, (what, got, peak)
+
+    tr = R.RayTracer(sc, devices=[0, 0])
+    tr.SetSamplesPerPixel(16)
+    (w, h), n = size, size[0] * size[1]
+    tr.OnResize((w, h))
+    tr.enable_moments()
+    tr.Render(2)
+    tr.gather_estimate()
+    assert tr.last_launch()["chunk_frames"] == 1
+    check(gathered(w, h), "gather_estimate")
+    # + the whole-image feature records (16 floats), the filter's scratch (denoise.hip DenoiseScratchBytes: 100 bytes
+    # per pixel), the packed history (temporal.hip TemporalHistoryBytes: 64) and the length plane
+    full = gathered(w, h) + n * 64 + n * 100 + n * 68
+    tr.image_resolve(temporal=1, denoise=1)
+    check(full, "image_resolve")
+    tr.image_present()  # the RGBA8 words live in the scratch
+    check(full, "image_present")
+    # the resize frees the frame buffers, the sample buffer and the gathered image; the next launch takes the other
+    # launch slot (launches alternate), and the first slot keeps its 24-byte chunk table until the tracer goes
+    (w, h), n = resized, resized[0] * resized[1]
+    again = gathered(w, h) + 24
+    if size != (64, 48):
+        assert again > full, "the resized list alone is above the old peak"
+    tr.OnResize((w, h))
+    tr.Render(2)
+    tr.gather_estimate()
+    assert tr.last_launch()["chunk_frames"] == 1
+    check(again, "resized, gather_estimate")
+    tr.image_resolve(temporal=1, denoise=1)
+    check(again + n * 232, "resized, image_resolve")
+    tr.close()
