@@ -20,6 +20,18 @@ namespace rt2 {
 
 namespace {
 
+// A word of a record as a float and back, bit for bit (refs, codes and counts ride in float records).
+float Bits(uint32_t u) {
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+uint32_t Word(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return u;
+}
+
 // Quad::Hit's interior decision on one coordinate of a rectangle, 0 <= c1 ((p - q) c2) <= 1 with the
 // float operations in that order (the rectangle forms below), as a function of the hit point's
 // coordinate p alone.
@@ -29,15 +41,11 @@ bool CoordIn(float p, float q, float c1, float c2) {
 }
 // Floats in the order of the reals as integers (-0 and +0 both 0) and back (0 -> +0).
 int64_t OrderKey(float f) {
-  uint32_t b;
-  memcpy(&b, &f, 4);
+  const uint32_t b = Word(f);
   return (b & 0x80000000u) ? -(int64_t)(b & 0x7FFFFFFFu) : (int64_t)b;
 }
 float FromOrderKey(int64_t k) {
-  const uint32_t b = k >= 0 ? (uint32_t)k : ((uint32_t)(-k) | 0x80000000u);
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
+  return Bits(k >= 0 ? (uint32_t)k : ((uint32_t)(-k) | 0x80000000u));
 }
 // The floats p with CoordIn(p, q, c1, c2) are one interval [lo, hi] of the reals' order, which holds
 // q: p -> p - q, y -> y c2 and y -> c1 y are each monotone under round-to-nearest (non-decreasing,
@@ -117,8 +125,7 @@ bool BoxAAWordsOf(const float* const face[6], float out[6], float& mB) {
   static const int kAxis[6] = {2, 0, 2, 0, 1, 1};
   float tw[6][8];
   for (int j = 0; j < 6; j++) {
-    uint32_t code;
-    memcpy(&code, &face[j][11], 4);
+    const uint32_t code = Word(face[j][11]);
     if (code != 4u + (uint32_t)kAxis[j] || !RectAAWords(face[j], kAxis[j], tw[j])) return false;
   }
   // planes: lo / hi face index per axis (boxaa.h kBoxAAFaceMap: x- 3, x+ 1, y- 5, y+ 4, z- 2, z+ 0)
@@ -170,34 +177,44 @@ void WorldNormal(const std::vector<float>& lind, uint32_t xf, const float n_mode
                         c2[0] * n[0] + c2[1] * n[1] + c2[2] * n[2]};
     const float l2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
     const float s = 1.0f / std::sqrt(l2);
-    n[0] = v[0] * s;
-    n[1] = v[1] * s;
-    n[2] = v[2] * s;
-    uint32_t parent;
-    memcpy(&parent, &c1[3], 4);
+    for (int k = 0; k < 3; k++) n[k] = v[k] * s;
+    const uint32_t parent = Word(c1[3]);
     x = parent;
   }
-  out[0] = n[0];
-  out[1] = n[1];
-  out[2] = n[2];
+  std::copy(n, n + 3, out);
 }
 
+// The four words of a program step (rt2_layout.h "Threaded program"): step i of program p.
+template <class P> auto& Kind(P& p, size_t i) { return p[4 * i]; }
+template <class P> auto& Skip(P& p, size_t i) { return p[4 * i + 1]; }
+template <class P> auto& RecOf(P& p, size_t i) { return p[4 * i + 2]; }  // its record's offset in `lind`
+template <class P> auto& Aux(P& p, size_t i) { return p[4 * i + 3]; }
+size_t Steps(const std::vector<uint32_t>& p) { return p.size() / 4; }
+
+// Everything Linearize and its helpers write while they build the threaded program. A program that
+// cannot be built (the step limit, transforms nested too deep, a medium over an accelerated list) is
+// given up by assigning a fresh one: nothing of it stays behind.
+struct ThreadedProgram {
+  std::vector<uint32_t> lin;  // CompiledScene::lin, lind
+  std::vector<float> lind;
+  std::vector<float> lind_bvh;     // BVH node records, kept apart while Flattener::bvh_apart
+  std::vector<uint32_t> box_runs;  // first quad step of each MakeBox run with a box record
+  std::unordered_map<uint32_t, uint32_t> lind_axis;  // program quad record -> axis code
+  bool origins_bounded = false;  // CompiledScene::origins_bounded: set by QUADAA words and y-axis transforms
+  int boundary_boxes = 0;  // medium boundaries given a box record
+  int xform_depth = 0;     // CompiledScene::lin_xform_depth
+};
+
 struct Flattener {
-  // the threaded program holds a test whose exactness needs ray origins within +-2^64 in world space
-  // (QUADAA rectangles, box boundaries as QUADAA words, transforms about y: CompiledScene::origins_bounded)
-  bool origins_bounded = false;
   const Scene& s;
   CompiledScene& out;
+  const CompileOptions& opt;
+  ThreadedProgram prog;
   std::unordered_map<int, uint32_t> ref_of;  // obj index -> node ref (DAG sharing)
   std::unordered_map<int, int> acc_depth;    // accelerated list obj -> tree depth
-  std::unordered_map<uint32_t, uint32_t> lind_axis;  // program quad record -> axis code
-  bool accelerate_lists = true;
-  // depth of an accelerated list's tree beyond the balanced ceil(log2 n) that SAH splits may use
-  // (CompileScene retries with 0 when the scene's traversal stack would not fit)
-  int acc_depth_slack = kAccDepthSlack;
   std::unordered_map<int, bool> medium_memo;
 
-  Flattener(const Scene& sc, CompiledScene& o) : s(sc), out(o) {}
+  Flattener(const Scene& sc, CompiledScene& o, const CompileOptions& op) : s(sc), out(o), opt(op) {}
 
   // BVH node records go to the prefix [0, out.hot_records), in breadth-first order, when it is
   // reserved (bvh_rank: BVH object -> breadth-first rank)
@@ -209,17 +226,9 @@ struct Flattener {
     return off;
   }
   float* Rec(uint32_t off) { return out.nodes.data() + 4 * (size_t)off; }
-  static float Bits(uint32_t u) {
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-  }
   void Put(uint32_t off, float a, float b, float c, float d) {
-    float* r = Rec(off);
-    r[0] = a;
-    r[1] = b;
-    r[2] = c;
-    r[3] = d;
+    const float v[4] = {a, b, c, d};
+    std::copy(v, v + 4, Rec(off));
   }
 
   bool HasMedium(int i) {
@@ -286,9 +295,8 @@ struct Flattener {
     };
     size_t mid = lo + (hi - lo) / 2;
     // surface-area heuristic over centroid-sorted sweeps on each axis (book 2 +0.6 % over the
-    // median split on the longest axis, which RT2_ACC_SAH=0 keeps)
-    const char* se = getenv("RT2_ACC_SAH");
-    if (!(se && atoi(se) == 0) && hi - lo > 2) {
+    // median split on the longest axis, which acc_sah = false keeps)
+    if (opt.acc_sah && hi - lo > 2) {
       auto area = [](const AABB& b) {
         const float dx = b.x.max - b.x.min, dy = b.y.max - b.y.min, dz = b.z.max - b.z.min;
         return dx * dy + dy * dz + dz * dx;
@@ -336,7 +344,7 @@ struct Flattener {
     }
     int depth = 0, balanced = 0;
     while (((size_t)1 << balanced) < items.size()) balanced++;  // ceil(log2 n): the median tree's depth
-    uint32_t root = BuildAcc(items, 0, items.size(), balanced + acc_depth_slack, depth);
+    uint32_t root = BuildAcc(items, 0, items.size(), balanced + opt.acc_depth_slack, depth);
     acc_depth[i] = depth;
     vec3 c((box.x.min + box.x.max) * 0.5f, (box.y.min + box.y.max) * 0.5f, (box.z.min + box.z.max) * 0.5f);
     float hx = box.x.max - c.x, hy = box.y.max - c.y, hz = box.z.max - c.z;
@@ -405,7 +413,7 @@ struct Flattener {
           refs.push_back(r);
           leaf_only = leaf_only && IsLeafPrim(c);
         }
-        if (accelerate_lists && AccelEligible(o, refs)) {
+        if (opt.accelerate_lists && AccelEligible(o, refs)) {
           ref = EmitListAcc(i, o, refs);
           out.lists++;
           break;
@@ -433,14 +441,11 @@ struct Flattener {
         if (child == kRefNone) return kRefNone;
         const mat4& iv = o.inv_model;
         const mat4& m = o.model;
-        Put(off + 0, iv[0][0], iv[0][1], iv[0][2], Bits(child));
-        Put(off + 1, iv[1][0], iv[1][1], iv[1][2], Bits(parent_xf));
-        Put(off + 2, iv[2][0], iv[2][1], iv[2][2], 0);
-        Put(off + 3, iv[3][0], iv[3][1], iv[3][2], 0);
-        Put(off + 4, m[0][0], m[0][1], m[0][2], 0);
-        Put(off + 5, m[1][0], m[1][1], m[1][2], 0);
-        Put(off + 6, m[2][0], m[2][1], m[2][2], 0);
-        Put(off + 7, m[3][0], m[3][1], m[3][2], 0);
+        const float link[4] = {Bits(child), Bits(parent_xf), 0, 0};
+        for (uint32_t c = 0; c < 4; c++) {
+          Put(off + c, iv[c][0], iv[c][1], iv[c][2], link[c]);
+          Put(off + 4 + c, m[c][0], m[c][1], m[c][2], 0);
+        }
         ref = self;
         out.xforms++;
         break;
@@ -502,15 +507,8 @@ struct Flattener {
   // Threaded program (rt2_layout.h): pre-order of the tree the reference traverses, plus a copy of
   // every visited record in program order (`lind`), so consecutive steps read consecutive bytes.
   // References inside copied records (XFORM parent, medium boundary) point into `lind`.
-  // Returns false when the program would exceed kLinearMaxSteps.
-  // kLinearMaxSteps, or RT2_LINEAR_MAX_STEPS from the environment (ablation of the mode switch)
-  static size_t LinearMaxSteps() {
-    static const size_t v = [] {
-      const char* e = getenv("RT2_LINEAR_MAX_STEPS");
-      return e ? (size_t)strtoul(e, nullptr, 10) : (size_t)kLinearMaxSteps;
-    }();
-    return v;
-  }
+  // Returns false when the program would exceed linear_max_steps (kLinearMaxSteps; another value is an
+  // ablation of the mode switch).
   uint32_t CopyRecords(uint32_t src_off, int n, std::vector<float>& lind) {
     uint32_t off = (uint32_t)(lind.size() / 4);
     const float* r = out.nodes.data() + 4 * (size_t)src_off;
@@ -528,6 +526,11 @@ struct Flattener {
     uint32_t off = CopyRecords(src, 1 + (int)((kids.size() + 3) / 4), lind);
     for (size_t k = 0; k < kids.size(); k++) lind[4 * (off + 1 + k / 4) + k % 4] = Bits(kids[k]);
     return make_ref(kList, off);
+  }
+  // a box record (boxaa.h BoxAAPair: the six planes, then mB, padded to kBoxAARecords records)
+  static void AppendBoxRecord(const float bw[6], float mB, std::vector<float>& lind) {
+    const float rec[4 * kBoxAARecords] = {bw[0], bw[1], bw[2], bw[3], bw[4], bw[5], mB};
+    lind.insert(lind.end(), rec, rec + 4 * kBoxAARecords);
   }
   // A medium boundary that is a list of at most kBoundaryAAMax unit-normal axis-aligned quads (a box
   // in its own space, MakeBox) also gets its children as consecutive QUADAA test words (8 words
@@ -548,8 +551,7 @@ struct Flattener {
       const int c = o.children[k];
       if (s.objs[(size_t)c].kind != kQuad) return 0;
       const float* r = out.nodes.data() + 4 * (size_t)(ref_of.at(c) & kOffsetMask);
-      uint32_t axis;
-      memcpy(&axis, &r[11], 4);
+      uint32_t axis = Word(r[11]);
       if (axis < 4 || axis > 6) return 0;
       float rec[8];
       if (!RectAAWords(r, (int)axis - 4, rec)) return 0;
@@ -557,19 +559,16 @@ struct Flattener {
       codes |= (axis - 4) << (3 * k);
     }
     lind.insert(lind.end(), words.begin(), words.end());
-    origins_bounded = true;
+    prog.origins_bounded = true;
     uint32_t box = 0;
-    if (box_aa && o.children.size() == 6) {  // a MakeBox: its box record (boxaa.h BoxAAPair) follows
+    if (opt.box_aa && o.children.size() == 6) {  // a MakeBox: its box record (boxaa.h BoxAAPair) follows
       const float* faces[6];
       for (int j = 0; j < 6; j++) faces[j] = out.nodes.data() + 4 * (size_t)(ref_of.at(o.children[(size_t)j]) & kOffsetMask);
       float bw[6], mB;
       if (BoxAAWordsOf(faces, bw, mB)) {
-        float rec[4 * kBoxAARecords] = {};
-        std::copy(bw, bw + 6, rec);
-        rec[6] = mB;
-        lind.insert(lind.end(), rec, rec + 4 * kBoxAARecords);
+        AppendBoxRecord(bw, mB, lind);
         box = kBoundaryBoxFlag;
-        out.box_steps++;
+        prog.boundary_boxes++;
       }
     }
     return kBoundaryAAFlag | box | ((uint32_t)o.children.size() << 24) | codes;
@@ -579,21 +578,21 @@ struct Flattener {
   // the node array, which is the list's child order (the kernel breaks equal roots by it).
   // `octant` (bit k: the ray direction is negative along axis k) orders each node's children for
   // such rays: the child with the larger centroids first along a split axis the ray runs down.
-  bool LinearizeAcc(uint32_t ref, std::vector<uint32_t>& lin, std::vector<float>& lind, uint32_t octant = 0) {
-    if (lin.size() / 4 >= LinearMaxSteps()) return false;
+  bool LinearizeAcc(uint32_t ref, uint32_t octant = 0) {
+    std::vector<uint32_t>& lin = prog.lin;
+    std::vector<float>& lind = prog.lind;
+    if (Steps(lin) >= opt.linear_max_steps) return false;
     const uint32_t kind = ref >> 28, off = ref & kOffsetMask;
     if (kind == kAccSphere) {
       lin.insert(lin.end(), {kAccSphere, 0u, CopyRecords(off, kSphereRecords, lind), off});
       return true;
     }
-    const size_t me = lin.size() / 4;
+    const size_t me = Steps(lin);
     lin.insert(lin.end(), {kAccBvh, 0u, CopyRecords(off, kBvhRecords, lind), 0u});
-    uint32_t near_ref, far_ref;
-    memcpy(&near_ref, &out.nodes[4 * (size_t)off + 3], 4);
-    memcpy(&far_ref, &out.nodes[4 * (size_t)off + 7], 4);
+    uint32_t near_ref = Word(out.nodes[4 * (size_t)off + 3]), far_ref = Word(out.nodes[4 * (size_t)off + 7]);
     if ((octant >> (kind - kAccBvh)) & 1u) std::swap(near_ref, far_ref);
-    if (!LinearizeAcc(near_ref, lin, lind, octant) || !LinearizeAcc(far_ref, lin, lind, octant)) return false;
-    lin[4 * me + 1] = (uint32_t)(lin.size() / 4);
+    if (!LinearizeAcc(near_ref, octant) || !LinearizeAcc(far_ref, octant)) return false;
+    Skip(lin, me) = (uint32_t)Steps(lin);
     return true;
   }
   // Whether rays in the space of transform chain xf (innermost first) start within +-2^100, the bound
@@ -608,8 +607,7 @@ struct Flattener {
     std::vector<uint32_t> chain;
     for (uint32_t x = xf; x != kRefNone;) {
       chain.push_back(x & kOffsetMask);
-      uint32_t parent;
-      memcpy(&parent, &lind[4 * (size_t)(x & kOffsetMask) + 7], 4);
+      const uint32_t parent = Word(lind[4 * (size_t)(x & kOffsetMask) + 7]);
       x = parent;
     }
     double b = lim;
@@ -651,13 +649,7 @@ struct Flattener {
     return inside(o.aabb) && inside(s.objs[(size_t)o.child].aabb) && inside(s.objs[(size_t)s.root].aabb);
   }
   // Box-level steps (boxaa.h) for every MakeBox run whose faces take the QUADAA test (DESIGN.md §4
-  // "Box-level test"). RT2_BOX_AA=0 keeps every MakeBox a plain six-face run (the A/B baseline).
-  bool box_aa = true;
-  std::vector<uint32_t> box_runs;  // first quad step of each MakeBox run with a box record
-  void SetBoxAA() {
-    const char* e = getenv("RT2_BOX_AA");
-    box_aa = !(e && atoi(e) == 0);
-  }
+  // "Box-level test"). box_aa = false keeps every MakeBox a plain six-face run (the A/B baseline).
   // A list that is a MakeBox whose faces all take the QUADAA rectangle test in this space: its box words
   bool BoxList(const Obj& o, uint32_t parent_xf, const std::vector<float>& lind, float bw[6], float& mB) const {
     if (o.kind != kList || o.children.size() != 6 || !QuadAASpace(parent_xf, lind)) return false;
@@ -675,8 +667,7 @@ struct Flattener {
   // bounds bit for bit (AABB(a, b) unions with fmin / fmax and PadToMinimums only enlarges, so this holds
   // for the loader's trees; it is what the certificate's monotonicity argument stands on, so it is checked
   // here and the scene keeps its BVH walk where it fails).
-  bool bvh_apart = false;        // BVH node records go after the leaves' records in `lind`
-  std::vector<float> lind_bvh;   // (collected here while bvh_apart)
+  bool bvh_apart = false;  // BVH node records go after the leaves' records in `lind` (prog.lind_bvh until then)
   static constexpr uint32_t kApartBase = 0x40000000u;
   bool QuadsOnly(int i) const {
     const Obj& o = s.objs[(size_t)i];
@@ -722,24 +713,26 @@ struct Flattener {
         if (ContainsAccList(c)) return true;
     return false;
   }
-  bool Linearize(int i, uint32_t parent_xf, std::vector<uint32_t>& lin, std::vector<float>& lind, int xf_depth = 0) {
-    if (lin.size() / 4 >= LinearMaxSteps()) return false;
+  bool Linearize(int i, uint32_t parent_xf, int xf_depth = 0) {
+    std::vector<uint32_t>& lin = prog.lin;
+    std::vector<float>& lind = prog.lind;
+    if (Steps(lin) >= opt.linear_max_steps) return false;
     const Obj& o = s.objs[(size_t)i];
     uint32_t src = ref_of.at(i) & kOffsetMask;
     auto emit = [&](uint32_t kind, uint32_t rec, uint32_t aux) {
       lin.insert(lin.end(), {kind, 0u, rec, aux});
-      return lin.size() / 4 - 1;
+      return Steps(lin) - 1;
     };
     switch (o.kind) {
       case kBvh: {
-        // (bvh_apart: the node's record goes after the leaves' records; CompileSceneWith fixes the offset)
-        size_t me = emit(kBvh, bvh_apart ? kApartBase + CopyRecords(src, kBvhRecords, lind_bvh)
+        // (bvh_apart: the node's record goes after the leaves' records; BuildThreadedProgram fixes the offset)
+        size_t me = emit(kBvh, bvh_apart ? kApartBase + CopyRecords(src, kBvhRecords, prog.lind_bvh)
                                          : CopyRecords(src, kBvhRecords, lind), 0);
-        if (!Linearize(o.left, parent_xf, lin, lind, xf_depth)) return false;
+        if (!Linearize(o.left, parent_xf, xf_depth)) return false;
         if (!(o.left == o.right && !HasMedium(o.left))) {
-          if (!Linearize(o.right, parent_xf, lin, lind, xf_depth)) return false;
+          if (!Linearize(o.right, parent_xf, xf_depth)) return false;
         }
-        lin[4 * me + 1] = (uint32_t)(lin.size() / 4);
+        Skip(lin, me) = (uint32_t)Steps(lin);
         return true;
       }
       case kList:
@@ -747,19 +740,17 @@ struct Flattener {
           // LISTACC step (aux = steps per copy of the tree, skip = the index after the copies), then
           // the tree in pre-order, and, when they fit, seven more copies, one per ray-direction
           // octant, each visiting a node's children nearer-first for rays of that octant (the list's
-          // answer does not depend on the order: rt2_layout.h LISTACC). RT2_ACC_OCTANTS=0: one copy.
+          // answer does not depend on the order: rt2_layout.h LISTACC). acc_octants = false: one copy.
           const size_t me = emit(kListAcc, CopyRecords(src, 2, lind), 0);
-          uint32_t root;
-          memcpy(&root, &out.nodes[4 * (size_t)src + 7], 4);
-          const size_t first = lin.size() / 4;
-          if (!LinearizeAcc(root, lin, lind)) return false;
-          const uint32_t copy = (uint32_t)(lin.size() / 4 - first);
-          lin[4 * me + 3] = copy;
-          const char* oe = getenv("RT2_ACC_OCTANTS");
-          if (!(oe && atoi(oe) == 0) && lin.size() / 4 + 7 * (size_t)copy <= LinearMaxSteps())
+          const uint32_t root = Word(out.nodes[4 * (size_t)src + 7]);
+          const size_t first = Steps(lin);
+          if (!LinearizeAcc(root)) return false;
+          const uint32_t copy = (uint32_t)(Steps(lin) - first);
+          Aux(lin, me) = copy;
+          if (opt.acc_octants && Steps(lin) + 7 * (size_t)copy <= opt.linear_max_steps)
             for (uint32_t oct = 1; oct < 8; oct++)
-              if (!LinearizeAcc(root, lin, lind, oct)) return false;
-          lin[4 * me + 1] = (uint32_t)(lin.size() / 4);
+              if (!LinearizeAcc(root, oct)) return false;
+          Skip(lin, me) = (uint32_t)Steps(lin);
           return true;
         }
         {
@@ -767,36 +758,34 @@ struct Flattener {
           // the six planes, then mB, padded to 2 records) right before the faces' records, and its first quad
           // step noted; after the run pass its run (exactly these six quads) gets the box flag (aux bit
           // 31), and the kernel runs the box-level test before the six-face run
-          if (box_aa) {
+          static_assert(kLinearMaxRun >= 6, "a box's run is its six faces");
+          if (opt.box_aa) {
             float bw[6], mB;
             if (BoxList(o, parent_xf, lind, bw, mB)) {
-              float rec[4 * kBoxAARecords] = {};
-              std::copy(bw, bw + 6, rec);
-              rec[6] = mB;
-              lind.insert(lind.end(), rec, rec + 4 * kBoxAARecords);
-              box_runs.push_back((uint32_t)(lin.size() / 4));
+              AppendBoxRecord(bw, mB, lind);
+              prog.box_runs.push_back((uint32_t)Steps(lin));
             }
           }
           for (int c : o.children)
-            if (!Linearize(c, parent_xf, lin, lind, xf_depth)) return false;
+            if (!Linearize(c, parent_xf, xf_depth)) return false;
           return true;
         }
       case kXform: {
         uint32_t off = CopyRecords(src, kXformRecords, lind);
         lind[4 * (off + 1) + 3] = Bits(parent_xf);
         const bool yaxis = YAxisPattern(i, lind, off);
-        origins_bounded = origins_bounded || yaxis;
+        prog.origins_bounded = prog.origins_bounded || yaxis;
         lind[4 * (off + 2) + 3] = Bits(yaxis ? kXformYAxis : 0u);
         uint32_t self = make_ref(kXform, off);
         if (xf_depth >= kLinearMaxXformDepth) return false;  // the kernel nests one loop per level
         size_t me = emit(kXform, off, 0);
-        out.lin_xform_depth = std::max(out.lin_xform_depth, xf_depth + 1);
-        if (!Linearize(o.child, self, lin, lind, xf_depth + 1)) return false;
-        lin[4 * me + 1] = (uint32_t)(lin.size() / 4);  // index of the matching exit step
+        prog.xform_depth = std::max(prog.xform_depth, xf_depth + 1);
+        if (!Linearize(o.child, self, xf_depth + 1)) return false;
+        Skip(lin, me) = (uint32_t)Steps(lin);  // index of the matching exit step
         // exit step: skip = the end of the transform's record range [off + kXformRecords, end) (the
         // records of every primitive under it follow its own record)
         const size_t ex = emit(kXformExit, off, parent_xf);
-        lin[4 * ex + 1] = (uint32_t)(lind.size() / 4);
+        Skip(lin, ex) = (uint32_t)(lind.size() / 4);
         return true;
       }
       case kMedium: {
@@ -806,20 +795,19 @@ struct Flattener {
         uint32_t b = CopyBoundary(o.child, lind);
         lind[4 * off + 2] = Bits(b);
         emit(kMedium, off, 0);
-        return lin.size() / 4 <= LinearMaxSteps();
+        return Steps(lin) <= opt.linear_max_steps;
       }
       case kQuad: {
         uint32_t off = CopyRecords(src, kQuadRecords, lind);
-        uint32_t axis;
-        memcpy(&axis, &lind[4 * (off + 2) + 3], 4);
+        uint32_t axis = Word(lind[4 * (off + 2) + 3]);
         const float* r = out.nodes.data() + 4 * (size_t)src;
         float test[8];
         // a unit-normal quad that is not a rectangle in its plane takes the axis-aligned test
         // with division (code K + 1: the same decision and t)
         if (axis >= 4 && axis <= 6 && !(QuadAASpace(parent_xf, lind) && RectAAWords(r, (int)axis - 4, test))) axis -= 3;
-        lind_axis[off] = axis;
+        prog.lind_axis[off] = axis;
         if (axis >= 4 && axis <= 6) {  // QUADAA layout (rt2_layout.h)
-          origins_bounded = true;
+          prog.origins_bounded = true;
           const float n[3] = {r[0], r[1], r[2]}, d = r[3], q[3] = {r[4], r[5], r[6]}, mat = r[7];
           float w[3] = {q[0], q[1], q[2]};
           if (parent_xf != kRefNone) WorldNormal(lind, parent_xf, n, w);  // replaces q (unused here)
@@ -830,11 +818,11 @@ struct Flattener {
           lind[4 * (off + 3) + 3] = Bits(parent_xf);  // enclosing transform of this occurrence
         }
         emit(kQuad, off, 0);
-        return lin.size() / 4 <= LinearMaxSteps();
+        return Steps(lin) <= opt.linear_max_steps;
       }
       default:  // sphere
         emit(kSphere, CopyRecords(src, kSphereRecords, lind), 0);
-        return lin.size() / 4 <= LinearMaxSteps();
+        return Steps(lin) <= opt.linear_max_steps;
     }
   }
 
@@ -875,17 +863,9 @@ struct Flattener {
 
 void PackMaterials(const Scene& s, CompiledScene& out) {
   for (const MaterialDesc& m : s.materials) {
-    uint32_t type = m.type, tex = m.tex_idx;
-    float ri_inv = (float)(1.0 / (double)m.refraction_index);
-    float rec[8];
-    memcpy(&rec[0], &type, 4);
-    rec[1] = m.albedo.x;
-    rec[2] = m.albedo.y;
-    rec[3] = m.albedo.z;
-    rec[4] = m.fuzz;
-    rec[5] = m.refraction_index;
-    memcpy(&rec[6], &tex, 4);
-    rec[7] = ri_inv;
+    const float ri_inv = (float)(1.0 / (double)m.refraction_index);
+    const float rec[8] = {Bits(m.type), m.albedo.x, m.albedo.y, m.albedo.z, m.fuzz, m.refraction_index,
+                          Bits(m.tex_idx), ri_inv};
     out.materials.insert(out.materials.end(), rec, rec + 8);
   }
 }
@@ -894,57 +874,52 @@ void PackMaterials(const Scene& s, CompiledScene& out) {
 // the material fetch and a solid texture's tex_value read for each quad step's primitive, at the
 // primitive's own record offset, and every XFORM record as it stands. Leaves out.hit empty when the
 // scene gets none: no program, nested transforms, no quad, a table above kHitTableBytesMax, or
-// RT2_HIT_TABLE=0 in the environment.
-void BuildHitTable(CompiledScene& out) {
+// hit_table = false. Reads lin, lind, lin_xform_depth, materials and textures; writes hit.
+void BuildHitTable(CompiledScene& out, const CompileOptions& opt) {
   out.hit.clear();
-  const char* e = getenv("RT2_HIT_TABLE");
-  if ((e && atoi(e) == 0) || out.lin.empty() || out.lin_xform_depth > 1) return;
+  if (!opt.hit_table || out.lin.empty() || out.lin_xform_depth > 1) return;
   if (out.lind.size() * sizeof(float) > kHitTableBytesMax) return;
   std::vector<float> hit(out.lind.size(), 0.0f);
-  const size_t n = out.lin.size() / 4, n_mat = out.materials.size() / 8, n_tex = out.textures.size() / 12;
+  const size_t n = Steps(out.lin), n_mat = out.materials.size() / 8, n_tex = out.textures.size() / 12;
   bool any = false;
   for (size_t i = 0; i < n; i++) {
-    const uint32_t kind = out.lin[4 * i];
-    const size_t off = 4 * (size_t)out.lin[4 * i + 2];
+    const uint32_t kind = Kind(out.lin, i);
+    const size_t off = 4 * (size_t)RecOf(out.lin, i);
     if (kind == kXform)
       std::copy(out.lind.begin() + (long)off, out.lind.begin() + (long)off + 4 * kXformRecords, hit.begin() + (long)off);
     if (kind == kQuad) {
       // (a quad step's skip word starts with its own axis code: the codes of the run that begins there)
-      const uint32_t code = out.lin[4 * i + 1] & 7u;
+      const uint32_t code = Skip(out.lin, i) & 7u;
       const float* r = &out.lind[off];
       float* h = &hit[off];
       uint32_t mat, flags = 0;
       if (code >= 4 && code <= 6) {  // QUADAA
         std::copy(r + 8, r + 11, h);
         h[3] = r[17];
-        uint32_t xf;
-        memcpy(&xf, &r[17], 4);
+        const uint32_t xf = Word(r[17]);
         if (xf != kRefNone) {
           std::copy(r + 12, r + 15, h + 4);
           flags |= kHitWorldNormal;
         }
-        memcpy(&mat, &r[15], 4);
+        mat = Word(r[15]);
       } else {  // QUAD
         std::copy(r, r + 3, h);
         h[3] = r[15];
-        memcpy(&mat, &r[7], 4);
+        mat = Word(r[7]);
       }
       if (mat >= n_mat) return;
       const float* m = &out.materials[8 * (size_t)mat];
       std::copy(m, m + 8, h + 8);
-      uint32_t type, tex;
-      memcpy(&type, &m[0], 4);
-      memcpy(&tex, &m[6], 4);
+      const uint32_t type = Word(m[0]), tex = Word(m[6]);
       if ((type == kMatTexture || type == kMatDiffuseLight || type == kMatIsotropic) && tex < n_tex) {
         const float* t = &out.textures[12 * (size_t)tex];
-        uint32_t ttype;
-        memcpy(&ttype, &t[0], 4);
+        const uint32_t ttype = Word(t[0]);
         if (ttype == kTexSolid) {
           std::copy(t, t + 4, h + 16);
           flags |= kHitSolid;
         }
       }
-      memcpy(&h[7], &flags, 4);
+      h[7] = Bits(flags);
       any = true;
     }
   }
@@ -967,12 +942,7 @@ void PackTextures(const Scene& s, CompiledScene& out) {
       u[8] = (uint32_t)(out.perlin_vec.size() / 4);
       u[9] = (uint32_t)out.perlin_perm.size();
       u[10] = (uint32_t)t.point_count;
-      for (const vec3& g : t.perlin_vec) {
-        out.perlin_vec.push_back(g.x);
-        out.perlin_vec.push_back(g.y);
-        out.perlin_vec.push_back(g.z);
-        out.perlin_vec.push_back(0.0f);
-      }
+      for (const vec3& g : t.perlin_vec) out.perlin_vec.insert(out.perlin_vec.end(), {g.x, g.y, g.z, 0.0f});
       out.perlin_perm.insert(out.perlin_perm.end(), t.perm_x.begin(), t.perm_x.end());
       out.perlin_perm.insert(out.perlin_perm.end(), t.perm_y.begin(), t.perm_y.end());
       out.perlin_perm.insert(out.perlin_perm.end(), t.perm_z.begin(), t.perm_z.end());
@@ -981,270 +951,259 @@ void PackTextures(const Scene& s, CompiledScene& out) {
   }
 }
 
-}  // namespace
 
-bool QuadAATestWords(const float* r, int k, float out[8]) { return RectAAWords(r, k, out); }
-bool BoxAAWords(const float* const faces[6], float out[6], float& mB) { return BoxAAWordsOf(faces, out, mB); }
-
-bool CompileScene(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists) {
-  return CompileSceneWith(s, out, err, accelerate_lists, kAccDepthSlack);
-}
-
-bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists,
-                      int acc_depth_slack) {
-  out = CompiledScene();
-  if (s.root < 0) {
-    err = "scene has no BVH root";
-    return false;
-  }
-  // BVH node records come first, in breadth-first order from the root, so any prefix of the record
-  // array holds the top levels of the tree (the stack traversal stages such a prefix in LDS when
-  // the whole scene does not fit, kModeStackHybrid); everything else follows. Record contents are
-  // the same in any order.
+// The passes of a compile, in the order CompileSceneWith calls them. BVH ranking: BVH node records come first, in breadth-first order from the root, so any prefix of the
+// record array holds the top levels of the tree (the stack traversal stages such a prefix in LDS when
+// the whole scene does not fit, kModeStackHybrid); everything else follows. Record contents are
+// the same in any order. Reads the object graph; returns BVH object -> breadth-first rank.
+std::unordered_map<int, uint32_t> RankBvhNodes(const Scene& s) {
   std::unordered_map<int, uint32_t> rank;
-  {
-    std::vector<int> q{s.root};
-    std::unordered_set<int> seen{s.root};
-    auto push = [&](int c) {
-      if (c >= 0 && seen.insert(c).second) q.push_back(c);
-    };
-    for (size_t h = 0; h < q.size(); h++) {
-      const Obj& o = s.objs[(size_t)q[h]];
-      if (o.kind == kBvh) {
-        rank.emplace(q[h], (uint32_t)rank.size());
-        push(o.left);
-        push(o.right);
-      } else if (o.kind == kList) {
-        for (int c : o.children) push(c);
-      } else if (o.kind == kXform || o.kind == kMedium) {
-        push(o.child);
-      }
+  std::vector<int> q{s.root};
+  std::unordered_set<int> seen{s.root};
+  auto push = [&](int c) {
+    if (c >= 0 && seen.insert(c).second) q.push_back(c);
+  };
+  for (size_t h = 0; h < q.size(); h++) {
+    const Obj& o = s.objs[(size_t)q[h]];
+    if (o.kind == kBvh) {
+      rank.emplace(q[h], (uint32_t)rank.size());
+      push(o.left);
+      push(o.right);
+    } else if (o.kind == kList) {
+      for (int c : o.children) push(c);
+    } else if (o.kind == kXform || o.kind == kMedium) {
+      push(o.child);
     }
   }
+  return rank;
+}
+
+// Flatten. Reads the object graph and the ranks; writes nodes (the ranked prefix, then every other
+// object's records: Emit), hot_records, root, the object counts, and max_stack and bvh_depth (StackNeed).
+bool Flatten(Flattener& fl, const std::unordered_map<int, uint32_t>& rank, std::string& err) {
+  CompiledScene& out = fl.out;
   const uint32_t hot = (uint32_t)rank.size() * (uint32_t)kBvhRecords;
   out.hot_records = hot;
   out.nodes.assign(4 * (size_t)hot, 0.0f);
-  Flattener fl(s, out);
-  fl.accelerate_lists = accelerate_lists;
-  fl.acc_depth_slack = acc_depth_slack;
   fl.bvh_rank = &rank;
-  out.root = fl.Emit(s.root, kRefNone, err);
+  out.root = fl.Emit(fl.s.root, kRefNone, err);
   if (out.root == kRefNone) return false;
   if (fl.hot_next != hot) {
     err = "internal: BVH record count changed between passes";
     return false;
   }
   int depth = 0;
-  out.max_stack = std::max(1, fl.StackNeed(s.root, depth));
+  out.max_stack = std::max(1, fl.StackNeed(fl.s.root, depth));
   out.bvh_depth = depth;
-  if (out.max_stack > kTraversalStack && out.acc_lists > 0 && acc_depth_slack > 0) {
-    // the SAH's extra tree depth pushed the stack past the kernel's: balanced trees instead (a
-    // performance heuristic never makes a scene fail to load)
-    return CompileSceneWith(s, out, err, accelerate_lists, 0);
-  }
-  if (out.nodes.size() / 4 > kOffsetMask) {
-    err = "scene too large for 28-bit node offsets";
-    return false;
-  }
-  fl.SetBoxAA();
-  // RT2_FLAT_BVH=0: no flat program (the A/B baseline); 2: built, and the kernel certifies no hit
-  const char* fe = getenv("RT2_FLAT_BVH");
-  const int flat_env = fe ? atoi(fe) : 1;
-  const bool flat = flat_env != 0 && fl.FlatQualifies();
+  return true;
+}
+
+// Threaded program. Reads nodes and the object graph (Linearize); writes lin, lind, lin_xform_depth,
+// origins_bounded and the medium boundaries' share of box_steps, and leaves box_runs and lind_axis in
+// fl.prog for the run passes. `flat`: the BVH node records go after the leaves' records. A program that
+// cannot be built leaves every one of these as a scene without a program has them.
+void BuildThreadedProgram(Flattener& fl, bool flat) {
+  ThreadedProgram& p = fl.prog;
   fl.bvh_apart = flat;
-  if (!fl.Linearize(s.root, kRefNone, out.lin, out.lind)) {
-    out.lin.clear();
-    out.lind.clear();
+  if (!fl.Linearize(fl.s.root, kRefNone)) {
+    p = ThreadedProgram();
   } else if (flat) {
-    const uint32_t base = (uint32_t)(out.lind.size() / 4);
-    for (size_t i = 0; i < out.lin.size() / 4; i++)
-      if (out.lin[4 * i] == kBvh) out.lin[4 * i + 2] = out.lin[4 * i + 2] - Flattener::kApartBase + base;
-    out.lind.insert(out.lind.end(), fl.lind_bvh.begin(), fl.lind_bvh.end());
+    const uint32_t base = (uint32_t)(p.lind.size() / 4);
+    for (size_t i = 0; i < Steps(p.lin); i++)
+      if (Kind(p.lin, i) == kBvh) RecOf(p.lin, i) = RecOf(p.lin, i) - Flattener::kApartBase + base;
+    p.lind.insert(p.lind.end(), p.lind_bvh.begin(), p.lind_bvh.end());
   }
-  out.origins_bounded = fl.origins_bounded && !out.lin.empty();
-  // The stack traversal needs max_stack entries per lane; the threaded program needs none, so a
-  // deeper scene still loads when it has one (and then always runs threaded).
-  out.stack_ok = out.max_stack <= kTraversalStack;
-  if (!out.stack_ok && out.lin.empty()) {
-    err = "scene needs a traversal stack of " + std::to_string(out.max_stack) + " entries (kernel has " +
-          std::to_string(kTraversalStack) + ") and has no threaded program";
-    return false;
+  fl.out.lin.swap(p.lin);
+  fl.out.lind.swap(p.lind);
+  fl.out.origins_bounded = p.origins_bounded;
+  fl.out.box_steps = p.boundary_boxes;
+  fl.out.lin_xform_depth = p.xform_depth;
+}
+
+// Quad runs: for a quad step, aux = number of consecutive quad steps starting there with no
+// skip target inside the run (so every lane that reaches the run's first step walks all of it), and
+// skip = the axis codes of the run's quads, 3 bits each, then a 1 bit (the kernel's loop ends when the
+// codes shifted past the last quad equal 1). A box's run is its six quads exactly, and its aux carries
+// kRunBoxFlag. Reads the steps' kinds and records, `entry` (entry[i]: a skip lands on step i; the caller
+// marks its program's targets, the boxes' ends are marked here), `box_starts` (the first step of each
+// MakeBox run with a box record) and `axis_of` (quad record -> axis code); writes the quad steps' skip
+// and aux. `adjacent_records`: a run also ends where the next quad's record does not follow directly (the
+// flat program). `where` ends the error text of a box whose quads did not form its run.
+bool FormQuadRuns(std::vector<uint32_t>& p, std::vector<char>& entry, const std::vector<uint32_t>& box_starts,
+                  const std::unordered_map<uint32_t, uint32_t>& axis_of, bool adjacent_records, const char* where,
+                  std::string& err) {
+  const size_t n = Steps(p);
+  for (uint32_t b : box_starts) entry[b] = entry[b + 6] = 1;
+  for (size_t i = n; i-- > 0;) {
+    if (Kind(p, i) != kQuad) continue;
+    const bool joins = i + 1 < n && Kind(p, i + 1) == kQuad && !entry[i + 1] &&
+                       (!adjacent_records || RecOf(p, i + 1) == RecOf(p, i) + (uint32_t)kQuadRecords);
+    Aux(p, i) = joins ? std::min(Aux(p, i + 1) + 1, kLinearMaxRun) : 1u;  // (step i + 1's own run: set above)
   }
-  // Quad runs: for a quad step, aux = number of consecutive quad steps starting there with no
-  // skip target inside the run (so every lane that reaches the run's first step walks all of it).
-  {
-    size_t n = out.lin.size() / 4;
-    std::vector<char> entry(n + 1, 0);
-    for (size_t i = 0; i < n; i++)
-      if (out.lin[4 * i] == kBvh || out.lin[4 * i] == kAccBvh) entry[out.lin[4 * i + 1]] = 1;
-    for (uint32_t b : fl.box_runs) entry[b] = entry[b + 6] = 1;  // a box's run is its six quads exactly
-    for (size_t i = n; i-- > 0;) {
-      if (out.lin[4 * i] != kQuad) continue;
-      uint32_t run = 1;
-      if (i + 1 < n && out.lin[4 * (i + 1)] == kQuad && !entry[i + 1])
-        run = std::min(out.lin[4 * (i + 1) + 3] + 1, kLinearMaxRun);
-      out.lin[4 * i + 3] = run;
-    }
-    // axis codes of each run's quads, 3 bits each, then a 1 bit (the kernel's loop ends when the
-    // codes shifted past the last quad equal 1), in the skip word
-    for (size_t i = 0; i < n; i++) {
-      if (out.lin[4 * i] != kQuad) continue;
-      uint32_t codes = 0;
-      const uint32_t run = out.lin[4 * i + 3];
-      for (uint32_t k = 0; k < run; k++) codes |= fl.lind_axis.at(out.lin[4 * (i + k) + 2]) << (3 * k);
-      out.lin[4 * i + 1] = codes | (1u << (3 * run));
-    }
-    for (uint32_t b : fl.box_runs) {
-      if (out.lin[4 * b] != kQuad || out.lin[4 * b + 3] != 6u || out.lin[4 * b + 1] != kBoxAARunCodes) {
-        err = "internal: a box's quads did not form its run";
-        return false;
-      }
-      out.lin[4 * b + 3] |= kRunBoxFlag;
-      out.box_steps++;
-    }
+  for (size_t i = 0; i < n; i++) {
+    if (Kind(p, i) != kQuad) continue;
+    uint32_t codes = 0;
+    const uint32_t run = Aux(p, i);
+    for (uint32_t k = 0; k < run; k++) codes |= axis_of.at(RecOf(p, i + k)) << (3 * k);
+    Skip(p, i) = codes | (1u << (3 * run));
   }
-  // Wide program: each 16-byte step entry followed by the first 48 bytes of its record (a whole BVH
-  // node or QUADAA quad), so one 64-byte scalar load fetches both
-  // plus one entry past the last step, kind kProgramEnd: the wave's next step index reaches n when
-  // every lane is done, and the kernel reads that entry's kind instead of comparing the index with n
-  {
-    size_t n = out.lin.size() / 4;
-    out.lin_wide.assign(16 * (n + 1), 0u);
-    out.lin_wide[16 * n] = kProgramEnd;
-    for (size_t i = 0; i < n; i++) {
-      for (int k = 0; k < 4; k++) out.lin_wide[16 * i + k] = out.lin[4 * i + k];
-      const size_t rec = 4 * (size_t)out.lin[4 * i + 2];
-      for (size_t k = 0; k < 12 && rec + k < out.lind.size(); k++) memcpy(&out.lin_wide[16 * i + 4 + k], &out.lind[rec + k], 4);
+  for (uint32_t b : box_starts) {
+    if (Kind(p, b) != kQuad || Aux(p, b) != 6u || Skip(p, b) != kBoxAARunCodes) {
+      err = std::string("internal: a box's quads did not form its run") + where;
+      return false;
     }
-    // BVH steps in the wide program: word 2 = the step after a hit, word 3 = the step after a hit
-    // whose paired box misses. A BVH step followed by a BVH step (its near child: pre-order puts
-    // it next, and no skip index lands on it) also carries that child's box in the words the
-    // node's record leaves unused (7, 11-15): one step tests both boxes with the same tmax the
-    // child's own step would see, a lane that hits both goes on to the child's first child, and
-    // the child's step is never executed. Down a chain of near children every other step drops
-    // out. Paired only in scenes with spheres (their kernels carry the second test: book 1 +2.9 %,
-    // book 2 +2.5 % against single-box steps; the Cornell kernel without it is 0.7 % faster).
-    // RT2_BVH_PAIRS=0 keeps single-box steps.
-    const char* pe = getenv("RT2_BVH_PAIRS");
-    const bool pairs = out.spheres > 0 && !(pe && atoi(pe) == 0);
-    std::vector<char> target(n + 1, 0), second(n + 1, 0);
-    for (size_t i = 0; i < n; i++)
-      if (out.lin[4 * i] == kBvh || out.lin[4 * i] == kAccBvh || out.lin[4 * i] == kXform) target[out.lin[4 * i + 1]] = 1;
-    for (size_t i = 0; i < n; i++) {
-      const uint32_t kind = out.lin[4 * i];
-      if (kind != kBvh && kind != kAccBvh) continue;  // accelerated-list tree nodes pair alike (padded boxes)
-      uint32_t* w = &out.lin_wide[16 * i];
-      w[2] = (uint32_t)(i + 1);
-      w[3] = out.lin[4 * i + 1];
-      if (!pairs || second[i] || i + 1 >= n || out.lin[4 * (i + 1)] != kind || target[i + 1]) continue;
-      const size_t c = i + 1;
-      second[c] = 1;
-      w[2] = (uint32_t)(c + 1);
-      w[3] = out.lin[4 * c + 1];
-      const float* b = &out.lind[4 * (size_t)out.lin[4 * c + 2]];  // child's box: lo.xyz, _, hi.xyz, _
-      memcpy(&w[7], &b[0], 4);
-      memcpy(&w[11], &b[1], 4);
-      memcpy(&w[12], &b[2], 4);
-      memcpy(&w[13], &b[4], 4);
-      memcpy(&w[14], &b[5], 4);
-      memcpy(&w[15], &b[6], 4);
-    }
+    Aux(p, b) |= kRunBoxFlag;
   }
-  // Flat program (rt2_layout.h): the BVH program's leaf steps in their order, without its kBvh steps; quad
-  // runs formed again over the new adjacency (a MakeBox run still exactly its six faces, flagged); the
-  // certificate box of each leaf = its parent BVH node's record, bit for bit, in the kXform step's wide
-  // entry and in the certificate table at each quad's record offset (a quad under a transform: its
-  // transform's box, flagged).
-  if (flat && !out.lin.empty()) {
-    const size_t n = out.lin.size() / 4;
-    std::vector<uint32_t> fmap(n + 1, 0), flin;
-    std::vector<size_t> parent;                 // per flat step: its parent BVH step in the BVH program
-    std::vector<char> under;                    // per flat step: inside a transform
-    std::vector<std::pair<size_t, size_t>> open;  // BVH steps whose range holds the current step: (step, end)
-    bool in_xf = false, ok = true;
-    for (size_t i = 0; i < n; i++) {
-      while (!open.empty() && i >= open.back().second) open.pop_back();
-      fmap[i] = (uint32_t)(flin.size() / 4);
-      const uint32_t kind = out.lin[4 * i];
-      if (kind == kBvh) {
-        open.emplace_back(i, out.lin[4 * i + 1]);
-        continue;
-      }
-      if (open.empty() || !(kind == kQuad || kind == kXform || kind == kXformExit)) ok = false;
-      if (!ok) break;
-      flin.insert(flin.end(), {kind, out.lin[4 * i + 1], out.lin[4 * i + 2], out.lin[4 * i + 3]});
-      parent.push_back(open.back().first);
-      under.push_back(in_xf && kind == kQuad);
-      if (kind == kXform) in_xf = true;
-      if (kind == kXformExit) in_xf = false;
+  return true;
+}
+// The threaded program's runs: its entries are the skip targets of its BVH and list-tree steps. Reads lin
+// and fl.prog's box_runs and lind_axis; writes lin's quad steps and the runs' share of box_steps.
+bool FormThreadedRuns(Flattener& fl, std::string& err) {
+  std::vector<uint32_t>& lin = fl.out.lin;
+  std::vector<char> entry(Steps(lin) + 1, 0);
+  for (size_t i = 0; i < Steps(lin); i++)
+    if (Kind(lin, i) == kBvh || Kind(lin, i) == kAccBvh) entry[Skip(lin, i)] = 1;
+  if (!FormQuadRuns(lin, entry, fl.prog.box_runs, fl.prog.lind_axis, false, "", err)) return false;
+  fl.out.box_steps += (int)fl.prog.box_runs.size();
+  return true;
+}
+
+// One entry of a wide program: the step's four words, then the first 12 words of its record.
+void WideEntry(uint32_t* w, const uint32_t* step, const std::vector<float>& lind) {
+  std::copy(step, step + 4, w);
+  const size_t rec = 4 * (size_t)RecOf(step, 0);
+  for (size_t k = 0; k < 12 && rec + k < lind.size(); k++) memcpy(&w[4 + k], &lind[rec + k], 4);
+}
+// Wide program: each 16-byte step entry followed by the first 48 bytes of its record (a whole BVH
+// node or QUADAA quad), so one 64-byte scalar load fetches both
+// plus one entry past the last step, kind kProgramEnd: the wave's next step index reaches n when
+// every lane is done, and the kernel reads that entry's kind instead of comparing the index with n.
+// Reads lin and lind; writes lin_wide.
+void BuildWideProgram(CompiledScene& out) {
+  const size_t n = Steps(out.lin);
+  out.lin_wide.assign(16 * (n + 1), 0u);
+  out.lin_wide[16 * n] = kProgramEnd;
+  for (size_t i = 0; i < n; i++) WideEntry(&out.lin_wide[16 * i], &out.lin[4 * i], out.lind);
+}
+
+// BVH steps in the wide program: word 2 = the step after a hit, word 3 = the step after a hit
+// whose paired box misses. A BVH step followed by a BVH step (its near child: pre-order puts
+// it next, and no skip index lands on it) also carries that child's box in the words the
+// node's record leaves unused (7, 11-15): one step tests both boxes with the same tmax the
+// child's own step would see, a lane that hits both goes on to the child's first child, and
+// the child's step is never executed. Down a chain of near children every other step drops
+// out. Paired only in scenes with spheres (their kernels carry the second test: book 1 +2.9 %,
+// book 2 +2.5 % against single-box steps; the Cornell kernel without it is 0.7 % faster);
+// `pairs` false keeps single-box steps. Reads lin and lind; writes the BVH steps' entries of lin_wide.
+void PairBvhSteps(CompiledScene& out, bool pairs) {
+  const std::vector<uint32_t>& lin = out.lin;
+  const size_t n = Steps(lin);
+  std::vector<char> target(n + 1, 0), second(n + 1, 0);
+  for (size_t i = 0; i < n; i++)
+    if (Kind(lin, i) == kBvh || Kind(lin, i) == kAccBvh || Kind(lin, i) == kXform) target[Skip(lin, i)] = 1;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t kind = Kind(lin, i);
+    if (kind != kBvh && kind != kAccBvh) continue;  // accelerated-list tree nodes pair alike (padded boxes)
+    uint32_t* w = &out.lin_wide[16 * i];
+    w[2] = (uint32_t)(i + 1);
+    w[3] = Skip(lin, i);
+    if (!pairs || second[i] || i + 1 >= n || Kind(lin, i + 1) != kind || target[i + 1]) continue;
+    const size_t c = i + 1;
+    second[c] = 1;
+    w[2] = (uint32_t)(c + 1);
+    w[3] = Skip(lin, c);
+    const float* b = &out.lind[4 * (size_t)RecOf(lin, c)];  // child's box: lo.xyz, _, hi.xyz, _
+    memcpy(&w[7], &b[0], 4);
+    memcpy(&w[11], &b[1], 8);
+    memcpy(&w[13], &b[4], 12);
+  }
+}
+
+// Flat program (rt2_layout.h): the BVH program's leaf steps in their order, without its kBvh steps; quad
+// runs formed again over the new adjacency (a MakeBox run still exactly its six faces, flagged); the
+// certificate box of each leaf = its parent BVH node's record, bit for bit, in the kXform step's wide
+// entry and in the certificate table at each quad's record offset (a quad under a transform: its
+// transform's box, flagged).
+struct LeafSteps {
+  std::vector<uint32_t> flin;  // the flat program's steps
+  std::vector<uint32_t> fmap;  // BVH-program step (or its end) -> the flat step at or after it
+  std::vector<size_t> parent;  // per flat step: its parent BVH step in the BVH program
+  std::vector<char> under;     // per flat step: a quad inside a transform
+};
+// Leaf-step projection. Reads lin; writes f. False when the program has no flat form (a step outside
+// every BVH node, or of a kind the flat walk has no case for).
+bool ProjectLeafSteps(const std::vector<uint32_t>& lin, LeafSteps& f) {
+  const size_t n = Steps(lin);
+  f.fmap.assign(n + 1, 0);
+  std::vector<std::pair<size_t, size_t>> open;  // BVH steps whose range holds the current step: (step, end)
+  bool in_xf = false;
+  for (size_t i = 0; i < n; i++) {
+    while (!open.empty() && i >= open.back().second) open.pop_back();
+    f.fmap[i] = (uint32_t)Steps(f.flin);
+    const uint32_t kind = Kind(lin, i);
+    if (kind == kBvh) {
+      open.emplace_back(i, Skip(lin, i));
+      continue;
     }
-    fmap[n] = (uint32_t)(flin.size() / 4);
-    const size_t m = flin.size() / 4;
-    if (ok && m > 0) {
-      std::vector<char> entry(m + 1, 0);
-      for (uint32_t b : fl.box_runs) entry[fmap[b]] = entry[fmap[b] + 6] = 1;
-      for (size_t j = 0; j < m; j++)
-        if (flin[4 * j] == kXform) flin[4 * j + 1] = fmap[flin[4 * j + 1]];  // its exit step
-      for (size_t j = m; j-- > 0;) {
-        if (flin[4 * j] != kQuad) continue;
-        uint32_t run = 1;
-        if (j + 1 < m && flin[4 * (j + 1)] == kQuad && !entry[j + 1] &&
-            flin[4 * (j + 1) + 2] == flin[4 * j + 2] + (uint32_t)kQuadRecords)
-          run = std::min((flin[4 * (j + 1) + 3] & kRunLenMask) + 1, kLinearMaxRun);
-        flin[4 * j + 3] = run;
-      }
-      for (size_t j = 0; j < m; j++) {
-        if (flin[4 * j] != kQuad) continue;
-        uint32_t codes = 0;
-        const uint32_t run = flin[4 * j + 3];
-        for (uint32_t k = 0; k < run; k++) codes |= fl.lind_axis.at(flin[4 * (j + k) + 2]) << (3 * k);
-        flin[4 * j + 1] = codes | (1u << (3 * run));
-      }
-      for (uint32_t b : fl.box_runs) {
-        const size_t j = fmap[b];
-        if (flin[4 * j] != kQuad || flin[4 * j + 3] != 6u || flin[4 * j + 1] != kBoxAARunCodes) {
-          err = "internal: a box's quads did not form its run in the flat program";
-          return false;
-        }
-        flin[4 * j + 3] |= kRunBoxFlag;
-      }
-      out.flat_wide.assign(16 * (m + 1), 0u);
-      out.flat_wide[16 * m] = kProgramEnd;
-      out.flat_cert.assign(out.lind.size(), 0.0f);
-      const uint32_t* xbox = nullptr;  // wide entry of the transform step last entered (under[j]: the one j lies in)
-      for (size_t j = 0; j < m; j++) {
-        uint32_t* w = &out.flat_wide[16 * j];
-        for (int k = 0; k < 4; k++) w[k] = flin[4 * j + k];
-        const size_t rec = 4 * (size_t)flin[4 * j + 2];
-        const float* box = &out.lind[4 * (size_t)out.lin[4 * parent[j] + 2]];  // (lo.xyz, _) (hi.xyz, _)
-        if (flin[4 * j] == kXform) {
-          memcpy(&w[4], &box[0], 12);
-          memcpy(&w[7], &box[4], 12);
-          xbox = w;
-        } else {
-          for (size_t k = 0; k < 12 && rec + k < out.lind.size(); k++) memcpy(&w[4 + k], &out.lind[rec + k], 4);
-        }
-        if (flin[4 * j] == kQuad) {
-          float* c = &out.flat_cert[rec];
-          if (under[j]) {
-            // its transform's certificate box, bit for bit words 4-9 of that step's wide entry, and the flag
-            const uint32_t f = kFlatCertXform;
-            memcpy(&c[0], &xbox[4], 12);
-            memcpy(&c[4], &xbox[7], 12);
-            memcpy(&c[3], &f, 4);
-          } else {
-            memcpy(&c[0], &box[0], 12);
-            memcpy(&c[4], &box[4], 12);
-          }
-        }
-      }
-      out.flat_mode = flat_env == 2 ? kFlatCertifyNothing : kFlatOn;
-      out.flat_steps = (int)m;
+    if (open.empty() || !(kind == kQuad || kind == kXform || kind == kXformExit)) return false;
+    f.flin.insert(f.flin.end(), {kind, Skip(lin, i), RecOf(lin, i), Aux(lin, i)});
+    f.parent.push_back(open.back().first);
+    f.under.push_back(in_xf && kind == kQuad);
+    if (kind == kXform) in_xf = true;
+    if (kind == kXformExit) in_xf = false;
+  }
+  f.fmap[n] = (uint32_t)Steps(f.flin);
+  for (size_t j = 0; j < Steps(f.flin); j++)
+    if (Kind(f.flin, j) == kXform) Skip(f.flin, j) = f.fmap[Skip(f.flin, j)];  // its exit step
+  return !f.flin.empty();
+}
+// The flat program's wide steps and certificate table. Reads f (its runs formed), lin and lind; writes
+// flat_wide and flat_cert.
+void WriteFlatProgram(const LeafSteps& f, CompiledScene& out) {
+  const size_t m = Steps(f.flin);
+  out.flat_wide.assign(16 * (m + 1), 0u);
+  out.flat_wide[16 * m] = kProgramEnd;
+  out.flat_cert.assign(out.lind.size(), 0.0f);
+  const uint32_t* xbox = nullptr;  // wide entry of the transform step last entered (under[j]: the one j lies in)
+  for (size_t j = 0; j < m; j++) {
+    uint32_t* w = &out.flat_wide[16 * j];
+    const float* box = &out.lind[4 * (size_t)RecOf(out.lin, f.parent[j])];  // (lo.xyz, _) (hi.xyz, _)
+    if (Kind(f.flin, j) == kXform) {
+      std::copy(&f.flin[4 * j], &f.flin[4 * j] + 4, w);
+      memcpy(&w[4], &box[0], 12);
+      memcpy(&w[7], &box[4], 12);
+      xbox = w;
+    } else {
+      WideEntry(w, &f.flin[4 * j], out.lind);
+    }
+    if (Kind(f.flin, j) == kQuad) {
+      // (under a transform: its transform's certificate box, bit for bit words 4-9 of that step's wide
+      // entry, and the flag)
+      float* c = &out.flat_cert[4 * (size_t)RecOf(f.flin, j)];
+      memcpy(&c[0], f.under[j] ? (const void*)&xbox[4] : &box[0], 12);
+      memcpy(&c[4], f.under[j] ? (const void*)&xbox[7] : &box[4], 12);
+      if (f.under[j]) c[3] = Bits(kFlatCertXform);
     }
   }
-  PackMaterials(s, out);
-  PackTextures(s, out);
-  BuildHitTable(out);
+}
+// Reads lin, lind and fl.prog's box_runs and lind_axis; writes flat_wide, flat_cert, flat_steps and
+// flat_mode (flat_bvh = 2: the kernel certifies no hit), or none of them when the program has no flat form.
+bool BuildFlatProgram(Flattener& fl, std::string& err) {
+  LeafSteps f;
+  if (!ProjectLeafSteps(fl.out.lin, f)) return true;
+  std::vector<char> entry(Steps(f.flin) + 1, 0);
+  std::vector<uint32_t> box_starts;
+  for (uint32_t b : fl.prog.box_runs) box_starts.push_back(f.fmap[b]);
+  if (!FormQuadRuns(f.flin, entry, box_starts, fl.prog.lind_axis, true, " in the flat program", err)) return false;
+  WriteFlatProgram(f, fl.out);
+  fl.out.flat_mode = fl.opt.flat_bvh == 2 ? kFlatCertifyNothing : kFlatOn;
+  fl.out.flat_steps = (int)Steps(f.flin);
+  return true;
+}
+
+// Feature bits (rt2_layout.h Feature; kFeatGenList is Emit's) from the object counts, materials and
+// textures, and one record in perlin_vec, perlin_perm and textures where they are empty.
+void SetFeatures(const Scene& s, CompiledScene& out) {
   if (out.spheres) out.features |= kFeatSphere;
   for (const Obj& o : s.objs)
     if (o.kind == kSphere && !(o.disp.x == 0.0f && o.disp.y == 0.0f && o.disp.z == 0.0f)) out.features |= kFeatMotion;
@@ -1260,6 +1219,75 @@ bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool
   if (out.perlin_vec.empty()) out.perlin_vec.assign(4, 0.0f);
   if (out.perlin_perm.empty()) out.perlin_perm.assign(1, 0);
   if (out.textures.empty()) out.textures.assign(12, 0.0f);
+}
+
+}  // namespace
+
+bool QuadAATestWords(const float* r, int k, float out[8]) { return RectAAWords(r, k, out); }
+bool BoxAAWords(const float* const faces[6], float out[6], float& mB) { return BoxAAWordsOf(faces, out, mB); }
+
+CompileOptions CompileOptions::FromEnv() {
+  CompileOptions o;
+  auto on = [](const char* name) {
+    const char* e = getenv(name);
+    return !(e && atoi(e) == 0);
+  };
+  o.acc_sah = on("RT2_ACC_SAH");
+  o.acc_octants = on("RT2_ACC_OCTANTS");
+  o.box_aa = on("RT2_BOX_AA");
+  o.bvh_pairs = on("RT2_BVH_PAIRS");
+  o.hit_table = on("RT2_HIT_TABLE");
+  if (const char* e = getenv("RT2_FLAT_BVH")) o.flat_bvh = atoi(e);
+  if (const char* e = getenv("RT2_LINEAR_MAX_STEPS")) o.linear_max_steps = (size_t)strtoul(e, nullptr, 10);
+  return o;
+}
+
+bool CompileScene(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists) {
+  CompileOptions opt = CompileOptions::FromEnv();
+  opt.accelerate_lists = accelerate_lists;
+  return CompileSceneWith(s, out, err, opt);
+}
+
+bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, const CompileOptions& opt) {
+  out = CompiledScene();
+  if (s.root < 0) {
+    err = "scene has no BVH root";
+    return false;
+  }
+  const std::unordered_map<int, uint32_t> rank = RankBvhNodes(s);
+  Flattener fl(s, out, opt);
+  if (!Flatten(fl, rank, err)) return false;
+  if (out.max_stack > kTraversalStack && out.acc_lists > 0 && opt.acc_depth_slack > 0) {
+    // the SAH's extra tree depth pushed the stack past the kernel's: balanced trees instead (a
+    // performance heuristic never makes a scene fail to load)
+    CompileOptions balanced = opt;
+    balanced.acc_depth_slack = 0;
+    return CompileSceneWith(s, out, err, balanced);
+  }
+  if (out.nodes.size() / 4 > kOffsetMask) {
+    err = "scene too large for 28-bit node offsets";
+    return false;
+  }
+  const bool flat = opt.flat_bvh != 0 && fl.FlatQualifies();
+  BuildThreadedProgram(fl, flat);
+  // The stack traversal needs max_stack entries per lane; the threaded program needs none, so a
+  // deeper scene still loads when it has one (and then always runs threaded).
+  out.stack_ok = out.max_stack <= kTraversalStack;
+  if (!out.stack_ok && out.lin.empty()) {
+    err = "scene needs a traversal stack of " + std::to_string(out.max_stack) + " entries (kernel has " +
+          std::to_string(kTraversalStack) + ") and has no threaded program";
+    return false;
+  }
+  if (!out.lin.empty()) {
+    if (!FormThreadedRuns(fl, err)) return false;
+    BuildWideProgram(out);
+    PairBvhSteps(out, out.spheres > 0 && opt.bvh_pairs);
+    if (flat && !BuildFlatProgram(fl, err)) return false;
+  }
+  PackMaterials(s, out);
+  PackTextures(s, out);
+  BuildHitTable(out, opt);
+  SetFeatures(s, out);
   return true;
 }
 

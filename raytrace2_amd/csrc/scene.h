@@ -165,13 +165,29 @@ struct CompiledScene {
   uint32_t flat_mode = 0;
   int flat_steps = 0;
 };
-// accelerate_lists = false keeps every list a linear child loop (the reference's own order).
-bool CompileScene(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists = true);
 // Accelerated-list trees built by SAH splits are at most this many levels deeper than balanced ones
-// (compile.cpp BuildAcc); CompileSceneWith(..., 0) builds them balanced (depth ceil(log2 n)).
+// (compile.cpp BuildAcc); acc_depth_slack = 0 builds them balanced (depth ceil(log2 n)).
 constexpr int kAccDepthSlack = 2;
-bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists,
-                      int acc_depth_slack);
+// Everything a compile may be told (DESIGN.md "Compile-time knobs"). The defaults are the product; every
+// other value is an A/B baseline or a test, and the images are bit-identical under all of them.
+struct CompileOptions {
+  bool accelerate_lists = true;  // false keeps every list a linear child loop (the reference's own order)
+  int acc_depth_slack = kAccDepthSlack;  // (the compile runs again with 0 when the stack would not fit)
+  bool acc_sah = true;      // list trees split by the surface-area heuristic (false: the median)
+  bool acc_octants = true;  // a list tree's steps once per ray-direction octant, when they fit
+  bool box_aa = true;       // box-level steps for MakeBox runs and medium boundaries (boxaa.h)
+  bool bvh_pairs = true;    // paired BVH steps in the wide program (sphere scenes)
+  bool hit_table = true;    // the threaded program's hit table (rt2_layout.h HIT)
+  int flat_bvh = 1;         // the flat program: 0 off, 1 on, 2 built and certifies nothing
+  size_t linear_max_steps = kLinearMaxSteps;  // a longer threaded program is not built (stack traversal)
+  // The options the RT2_* environment variables ask for: RT2_ACC_SAH, RT2_ACC_OCTANTS, RT2_BOX_AA,
+  // RT2_BVH_PAIRS, RT2_HIT_TABLE (a value with atoi 0 switches the feature off), RT2_FLAT_BVH (its atoi)
+  // and RT2_LINEAR_MAX_STEPS (strtoul). The only place the compiler reads the environment.
+  static CompileOptions FromEnv();
+};
+// CompileSceneWith under CompileOptions::FromEnv() and the given accelerate_lists.
+bool CompileScene(const Scene& s, CompiledScene& out, std::string& err, bool accelerate_lists = true);
+bool CompileSceneWith(const Scene& s, CompiledScene& out, std::string& err, const CompileOptions& opt);
 // The 8 QUADAA test words of QUAD record r (20 floats, rt2_layout.h) with axis code k + 4, or false when
 // the quad takes the general path (compile.cpp RectAAWords; for tests/cpp/quadaa_bounds.cpp).
 bool QuadAATestWords(const float* r, int k, float out[8]);

@@ -157,7 +157,7 @@ int main(int argc, char** argv) {
   Scene s;
   std::string err;
   CompiledScene c;
-  unsetenv("RT2_BOX_AA");  // the default: box steps (compile.cpp SetBoxAA)
+  unsetenv("RT2_BOX_AA");  // the default: box steps (scene.h CompileOptions::box_aa)
   if (!LoadScene(path, 1, s, err) || !CompileScene(s, c, err)) {
     fprintf(stderr, "scene: %s\n", err.c_str());
     return 2;

@@ -119,12 +119,16 @@ static int check(const char* path) {
       if (!used[w] && U(c.hit[w]) != 0u) return fail(path, "a word outside every entry is not 0", w);
   }
   std::printf("%s hit_bytes=%zu quads=%zu xforms=%zu depth=%d\n", path, c.hit.size() * 4, quads, xforms, c.lin_xform_depth);
-  // the switch
+  // the switch, through the environment and as an option
   setenv("RT2_HIT_TABLE", "0", 1);
-  CompiledScene off;
+  CompiledScene off, off2;
   if (!CompileScene(s, off, err)) return 2;
   unsetenv("RT2_HIT_TABLE");
   if (!off.hit.empty()) return fail(path, "RT2_HIT_TABLE=0 built a table", 0);
+  CompileOptions no_table;
+  no_table.hit_table = false;
+  if (!CompileSceneWith(s, off2, err, no_table)) return 2;
+  if (!off2.hit.empty() || off2.lin != off.lin) return fail(path, "hit_table = false differs from RT2_HIT_TABLE=0", 0);
   // (bytes, not floats: refs such as kRefNone are NaN patterns)
   if (off.lind.size() != c.lind.size() || std::memcmp(off.lind.data(), c.lind.data(), 4 * c.lind.size()) != 0 ||
       off.lin != c.lin)

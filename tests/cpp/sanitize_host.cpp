@@ -4,7 +4,8 @@
 // json.cpp, scene.cpp, compile.cpp, image.cpp (the product's loader, compiler and image writer) and
 // oracle/rt_oracle.cpp (the CPU restatement), then run on:
 //   --good <scene.json>...   every committed scene: LoadScene (Serialize.cpp:199-360 + the legacy
-//                            adapter), CompileScene with and without list trees, Camera::Params at the
+//                            adapter), CompileScene with and without list trees, then under step limits below the
+//                            program's length and with every CompileOptions field changed, Camera::Params at the
 //                            BASELINE sizes, the oracle's loader and an 8x8, 2-frame oracle render in both
 //                            product orders; every byte prefix of the small ones and single-byte
 //                            corruptions of each (all must fail cleanly or load);
@@ -70,6 +71,29 @@ static bool Exercise(const std::string& path, bool render) {
       CompiledScene c;
       std::string e2;
       if (!CompileScene(s, c, e2, accel != 0)) Fail(path + ": compile: " + e2);
+      if (!render) continue;
+      // a committed scene: the step limit at 1, at 10 and just below the program's length (a program given
+      // up part-way leaves a stack-traversal scene), then every option at its non-default value together
+      const size_t steps = c.lin.size() / 4;
+      for (size_t limit : {(size_t)1, (size_t)10, steps - 1}) {
+        if (limit >= steps) continue;
+        CompileOptions o;
+        o.accelerate_lists = accel != 0;
+        o.linear_max_steps = limit;
+        CompiledScene l;
+        if (!CompileSceneWith(s, l, e2, o)) Fail(path + ": compile under a step limit: " + e2);
+        if (!(l.lin.empty() && l.lind.empty() && l.lin_wide.empty() && l.hit.empty() && l.flat_wide.empty() &&
+              l.flat_cert.empty() && l.box_steps == 0 && l.flat_steps == 0 && l.flat_mode == 0 &&
+              l.lin_xform_depth == 0 && !l.origins_bounded))
+          Fail(path + ": a program past the step limit left something behind");
+      }
+      CompileOptions all;
+      all.accelerate_lists = accel != 0;
+      all.acc_depth_slack = 0;
+      all.acc_sah = all.acc_octants = all.box_aa = all.bvh_pairs = all.hit_table = false;
+      all.flat_bvh = 2;
+      all.linear_max_steps = 1000;
+      if (!CompileSceneWith(s, c, e2, all)) Fail(path + ": compile with every option changed: " + e2);
     }
     const int dims[4][3] = {{400, 400, 64}, {1024, 1024, 1000}, {1920, 1080, 500}, {800, 800, 10000}};
     for (const auto& d : dims) {

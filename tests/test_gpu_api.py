@@ -165,6 +165,36 @@ def test_box_level_test_certifies_and_changes_no_bit(have_gpu, monkeypatch, name
     assert np.array_equal(acc.view(np.uint32), acc0.view(np.uint32))
 
 
+def test_scene_past_the_step_limit_renders_on_the_stack_like_the_oracle(have_gpu, monkeypatch):
+    """A threaded program given up part-way (RT2_LINEAR_MAX_STEPS=10 at scene load, below the Cornell box's 29
+    steps and after its first MakeBox was recorded) leaves a stack-traversal scene: no threaded steps, no box
+    steps, and an accumulation bit-identical to the scene loaded without the variable and to the oracle."""
+    from oracle.oracle import OracleScene
+    name, w, h, spp, frames = "cornell_box_original", 32, 32, 4, 4
+
+    def render(env):
+        if env is None:
+            monkeypatch.delenv("RT2_LINEAR_MAX_STEPS", raising=False)
+        else:
+            monkeypatch.setenv("RT2_LINEAR_MAX_STEPS", env)
+        sc = R.Scene(scene_path(name), R.DEFAULT_SEED)
+        tr = R.RayTracer(sc, 0)
+        tr.set_seed(R.DEFAULT_SEED)
+        tr.SetSamplesPerPixel(spp)
+        tr.OnResize((w, h))
+        tr.Render(frames)
+        acc = tr.Accumulation().copy()
+        tr.close()
+        return sc.info(), acc
+    info10, acc10 = render("10")
+    info, acc = render(None)
+    assert info.linear_steps > 10 and info.box_steps > 0
+    assert info10.linear_steps == 0 and info10.box_steps == 0
+    o_acc, _, _ = OracleScene(scene_path(name), R.DEFAULT_SEED).render(w, h, spp, frames, forward=True)
+    assert np.array_equal(acc10.view(np.uint32), acc.view(np.uint32))
+    assert np.array_equal(acc10.view(np.uint32), o_acc.view(np.uint32))
+
+
 def test_medium_box_far_away_matches_the_oracle(have_gpu):
     """The medium's box-boundary test (boxaa.h BoxAAPair) at distances where the second boundary query
     starts on the first hit itself: for t1 above 2^11, fl(t1 + 0.0001) = t1 (ConstantMedium.cpp:26-30), so

@@ -3,7 +3,9 @@
 json.cpp, scene.cpp, compile.cpp, image.cpp (the product's loader, scene compiler and image writer) and
 oracle/rt_oracle.cpp (the CPU restatement) are compiled with -fsanitize=address,undefined and
 -fno-sanitize-recover=all, and tests/cpp/sanitize_host.cpp drives them over every committed scene (load,
-compile in both list modes, camera at the BASELINE sizes, a small oracle render in both product orders),
+compile in both list modes, again with the step limit at 1, at 10 and one below the program's length, where the
+threaded program is given up part-way and must leave a stack-traversal scene, and once with every compile
+option at its non-default value, camera at the BASELINE sizes, a small oracle render in both product orders),
 every byte prefix and 400 single-byte corruptions of each scene document, the malformed documents of
 tests/test_loader.py, the camera files' WriteCamera round trip and WriteImage in both formats. Any
 sanitizer report aborts the run. CPU only; the GPU code is not built here (no device sanitizer on this
