@@ -1569,7 +1569,15 @@ constexpr bool BoxOn() {
   return true;
 }
 // kFlat (the kernels with kFeatFlat): the walk of the launch's flat program (rt2_layout.h "Flat program":
-// no kBvh steps, so no slab test, no next-index search between leaves) with the certificate of DESIGN.md §4
+// no kBvh steps, so no slab test, no next-index search between leaves). Its step index is a scalar taken from
+// the step words alone: a flat program holds only kQuad runs, kXform, kXformExit and kProgramEnd, and each of
+// them sends every lane to the same successor (at + 1, or at + run of the quad step's word 3); no step kind
+// that sets a per-lane `next` (kBvh's skip, a sphere, a medium, an accelerated list) occurs. Every lane that
+// enters the trace starts at step 0, so by induction every live lane's `next` is the wave's step at every
+// step: `next == at` always holds and the minimum over the live lanes is that successor. The walk therefore
+// keeps no per-lane `next`, tests none and searches none. Lanes the caller's depth branch masked off stay
+// masked (the walk only narrows exec inside a step), and the index does not depend on which lanes are live.
+// The walk runs with the certificate of DESIGN.md §4
 // "Flat walk of small BVHs": `uncert` returns whether this lane's hit is not proven to be the hit of the
 // BVH program's walk (the caller then traces that program for the lane). One rule per trace, after the walk,
 // on the winner's certificate box from the table with the world ray: for a winner under a transform the box
@@ -1598,12 +1606,13 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   uint32_t cur_xf = kRefNone;
   f3 acc_pinv = mk(0.0f, 0.0f, 0.0f);  // accelerated list: this ray's box padding x inv
   uint32_t acc_best = kRefNone;  // accelerated list: child index of its current closest sphere
-  uint32_t next = 0;  // this lane's next step
+  uint32_t next = 0;  // this lane's next step (kFlat: the wave's, a value of the step words alone)
   RT2_WAVE(0);
 #if RT2_EXP_WAVESTEPS
   cnt.wd[7]++;
 #endif
-  uint32_t i = wave_min_next(next);  // wave-uniform step = min over live lanes of `next`
+  // wave-uniform step = min over live lanes of `next` (kFlat: the step words' successor, from 0)
+  uint32_t i = kFlat ? 0u : wave_min_next(next);
   // (i reaches P.lin_len when every lane is done: the wide program's entry there is kProgramEnd)
   while (true) {
     u32x16 sw = sld16(prog, i * 64u);  // entry + the first 48 bytes of its record
@@ -1660,8 +1669,8 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
     if (kind == kSphere) RT2_WAVE(4);
     if (kind == kMedium) RT2_WAVE(5);
     const uint32_t at = i;
-    i = kRefNone;  // computed after the step
-    if (next == at) {
+    if constexpr (!kFlat) i = kRefNone;  // computed after the step
+    if (kFlat || next == at) {  // (kFlat: every live lane is at the wave's step, see above)
     next = at + 1u;
     if (kind == kQuad) {
       // a run of st.w quads with contiguous records, axis codes in st.y (3 bits each), tested in
@@ -1980,7 +1989,7 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
       }
     }
     }  // next == at
-    i = wave_min_next(next);
+    i = kFlat ? next : wave_min_next(next);
   }
   h.t = tmax;
   h.prim = prim;
@@ -2379,6 +2388,8 @@ __global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~(kFeatList | kFeatFlat)), 
   constexpr bool kList = (FL & kFeatList) != 0u;
   constexpr bool kFlat = (FL & kFeatFlat) != 0u;
   static_assert(!kFlat || (kMode == kModeLinear && !kStats), "the flat walk: threaded product kernels only");
+  static_assert(!kFlat || (F & (kFeatSphere | kFeatMedium | kFeatAccList)) == 0u,
+                "the flat walk's scalar step index: no step kind that sets a per-lane next (sphere, medium, accelerated list)");
   constexpr bool kLds = kMode == kModeStackLds || kMode == kModeStackHybrid;
   constexpr uint32_t kGroup = StageGroup<F, kMode, kStats>();
   constexpr uint32_t kPlanes = kGroup ? 3u * (kGroup - 1u) : 1u;  // [slot][component] planes of 64 lanes
