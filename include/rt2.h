@@ -369,7 +369,8 @@ RT2_API int rt2_tracer_render_until(rt2_tracer* tr, float target_rms, int min_fr
  * Caveat: stopping on a pixel's own variance estimate is biased — an unlucky pixel whose first samples
  *   happen to agree looks converged and freezes. `window` and `min_frames` are the guards.
  * RT2_ERR_INVALID: enable_adaptive with moments off, or on a create_multi or joined tracer (their gathered
- *   image divides by one common frame index; set_partition tracers work); enable_moments(0) and join while
+ *   image divides by one common frame index; set_partition tracers work, and "Adaptive sampling of the gathered
+ *   image" below is the family for those tracers); enable_moments(0) and join while
  *   adaptive is on; sample_counts / adaptive_check / render_adaptive with adaptive off; a check with
  *   fewer than 2 frames; a window outside [0, 64] or a threshold that is negative or NaN; enable_adaptive
  *   on a tracer that renders without the threaded traversal (the list kernels exist for that mode only).
@@ -546,7 +547,8 @@ RT2_API int rt2_present_buffers(int device, int width, int height, const float* 
  *   an event recorded after both copies), and one kernel on the root writes what gather's kernel writes
  *   (image_accumulation, image_non_converted_pixels and image_pixels read the same bytes) and the variance of the
  *   mean. Collective on joined tracers: every rank calls it. It enqueues and does not wait. Needs moments on on
- *   every rank, FrameIdx() >= 2 and adaptive sampling off.
+ *   every rank, FrameIdx() >= 2 and adaptive sampling off (or switched on by rt2_tracer_image_enable_adaptive:
+ *   "Adaptive sampling of the gathered image" below).
  * image_variance: blocking readback of v = ((sem_r^2 + sem_g^2) + sem_b^2) / 3 in float32, float per image pixel:
  *   what rt2_tracer_denoise takes from standard_error.
  * image_features: rt2_tracer_features of the whole image, 16 floats per image pixel, traced on the root alone (the
@@ -577,12 +579,12 @@ RT2_API int rt2_present_buffers(int device, int width, int height, const float* 
  *   sums `image`, the means `image_nc` = sum / (float)frames (float3 each) and `variance` (float). No GPU needed.
  * RT2_ERR_INVALID: a NULL tracer, camera or output (out_variance, out_length excepted); a readback, resolve,
  *   present or present_time on a rank other than 0; gather_estimate (and the calls that run it) with moments off,
- *   fewer than 2 frames, adaptive sampling on, on a set_partition tracer (world > 1) that is not joined, or with
+ *   fewer than 2 frames, adaptive sampling switched on by rt2_tracer_enable_adaptive, on a set_partition tracer (world > 1) that is not joined, or with
  *   ranks that disagree on dims or frame index; image_variance before any gather_estimate; image_resolve /
  *   image_present* on a joined tracer without a gather_estimate of the current FrameIdx(); invalid temporal or
  *   denoise parameters, checked only for the stages switched on (image_move_camera: its temporal parameters);
  *   image_features, resolve, present and a pushing move_camera on a scene only the threaded traversal can render;
- *   image_move_camera with adaptive sampling on or on an unjoined partition; deinterleave_estimate_host with a
+ *   image_move_camera with adaptive sampling switched on by rt2_tracer_enable_adaptive or on an unjoined partition; deinterleave_estimate_host with a
  *   NULL argument, a negative size, world < 1 or frames outside [2, 2^31). A refused call changes nothing. */
 RT2_API int rt2_tracer_gather_estimate(rt2_tracer* tr);
 RT2_API int rt2_tracer_image_variance(rt2_tracer* tr, float* out);  /* float per image pixel */
@@ -596,6 +598,63 @@ RT2_API int rt2_tracer_image_present_time(rt2_tracer* tr, double* ms);
 RT2_API int rt2_deinterleave_estimate_host(const float* stacks, const float* stacks2, float* image, float* image_nc,
                                            float* variance, int width, int height, int band_h, int world,
                                            int64_t frames);
+
+/* ---- Adaptive sampling of the gathered image ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches exactly what it launched before.
+ * "Adaptive sampling" above for a create_multi or joined tracer, whose gathered image divided by one common frame
+ * index: with it on, every rank's stack of sample counts n_p travels with its accumulation (a third transfer of the
+ * gather's RCCL group; on one GPU a third copy on the root's stream), and the root's kernel divides each pixel's sum
+ * by its own n_p. The calls of that section keep their refusals on these tracers, and a plain tracer switched on
+ * by rt2_tracer_enable_adaptive behaves as before, its refusals of gather_estimate, image_resolve, image_present*
+ * and image_move_camera included. The check's window runs along the row and partitions hold whole rows, so every
+ * decision, every sum and every count is, bit for bit, that of a one-GPU tracer under rt2_tracer_enable_adaptive at
+ * the same seed, size, camera and steps.
+ * image_enable_adaptive: on a create_multi tracer, enable_adaptive on every part; on a joined tracer, on this rank
+ *   (call it after rt2_tracer_join, which refuses an adaptive tracer; every rank calls it); on a plain one-GPU
+ *   tracer (world 1) enable_adaptive, and its gathers carry the counts. Needs moments on and the threaded traversal
+ *   on every part (asked before any part changes). It synchronises, reallocates, resets the frame index and the
+ *   sums, and drops the gathered image and a whole-image history held. on = 0 switches adaptive sampling off the
+ *   same way.
+ * image_adaptive_check: adaptive_check on every part. On a create_multi tracer every part's check and the copy of
+ *   its totals are enqueued before any is waited for, so the checks overlap across the GPUs and the host waits
+ *   once per part. `out` is the whole image's: pixels, active, retired, samples and nonfinite summed over the
+ *   parts, frames the common FrameIdx(). Collective on joined tracers: every rank calls it; after the local check
+ *   its four totals and its pixel count are summed over the ranks on the device (ncclAllReduce, uint64, on the
+ *   tracer's stream) before the one copy to the host, so every rank receives the same whole-image scalars, while
+ *   what a rank launches next follows its own active count.
+ * image_render_adaptive: render_adaptive's loop over image_adaptive_check; it stops when the whole image has no
+ *   active pixel. On joined tracers every rank leaves the loop at the same step.
+ * image_part_adaptive: the scalars the last check left of GPU `part` alone, before the sum (part 0 of a plain or
+ *   joined tracer is itself): how evenly the active pixels stay spread over the parts.
+ * image_sample_counts: n_p of the gathered image, uint32 per image pixel, on the root. Blocks. Like the other
+ *   rt2_tracer_image_* readbacks it reads what the last gather (or gather_estimate) left.
+ * With it on: gather and gather_estimate carry the counts; image_accumulation, image_non_converted_pixels (sum /
+ *   (float)n_p), image_pixels and image_variance (from each pixel's own n_p) are those of the one-GPU adaptive
+ *   tracer; a create_multi tracer's non_converted_pixels and pixels likewise, its moments and standard_error as
+ *   before (the parts' rows placed on the host). image_resolve and image_present* run unchanged, the blend's
+ *   length being each pixel's n_p. image_move_camera pushes the blend as the root's history under the camera the
+ *   frames were rendered with, then sets the camera and resets every part, which reactivates every pixel.
+ * deinterleave_adaptive_host: the CPU statement of that gather's kernel, beside rt2_deinterleave_estimate_host: the
+ *   rank-major stacks [world][rt2_band_rows_max][width] of the sums (float3), their squares (float3) and the counts
+ *   (uint32) -> image-order sums `image`, means `image_nc` = sum / (float)n_p, `variance` (float) and `image_counts`.
+ *   stacks2 and variance may both be NULL (the plain gather). No GPU needed.
+ * RT2_ERR_INVALID: image_enable_adaptive(1) with moments off or without the threaded traversal, or on a
+ *   set_partition tracer (world > 1) that is not joined; image_adaptive_check, image_render_adaptive,
+ *   image_part_adaptive and image_sample_counts with it off; a check with fewer than 2 frames; a window outside
+ *   [0, 64] or a threshold that is negative or NaN; a NULL tracer or output; image_part_adaptive with a part out
+ *   of range or before the first check since a reset; image_sample_counts before a gather or on a rank other than
+ *   0; a gather whose ranks disagree on whether it is on; deinterleave_adaptive_host with a NULL argument (stacks2
+ *   and variance excepted, together), a negative size or world < 1. A refused call changes nothing. */
+RT2_API int rt2_tracer_image_enable_adaptive(rt2_tracer* tr, int on);
+RT2_API int rt2_tracer_image_adaptive_check(rt2_tracer* tr, float threshold, int window, rt2_adaptive* out);
+RT2_API int rt2_tracer_image_render_adaptive(rt2_tracer* tr, float threshold, int window, int min_frames, int max_frames,
+                                             int check_every, rt2_adaptive* out);
+RT2_API int rt2_tracer_image_part_adaptive(rt2_tracer* tr, int part, rt2_adaptive* out);
+RT2_API int rt2_tracer_image_sample_counts(rt2_tracer* tr, uint32_t* out); /* n_p per image pixel */
+RT2_API int rt2_deinterleave_adaptive_host(const float* stacks, const float* stacks2 /* may be NULL */,
+                                           const uint32_t* counts, float* image, float* image_nc,
+                                           float* variance /* may be NULL */, uint32_t* image_counts, int width,
+                                           int height, int band_h, int world);
 
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad

@@ -403,6 +403,30 @@ class RayTracer {
     Check(rt2_tracer_image_present_time(t_.get(), &ms));
     return ms;
   }
+  // Adaptive sampling of the gathered image (rt2.h "Adaptive sampling of the gathered image"): EnableAdaptive,
+  // AdaptiveCheck, RenderAdaptive and SampleCounts for a tracer over several GPUs (n_gpus >= 1) or a joined one,
+  // where those members are refused. The checks of the GPUs overlap and their scalars are summed; every gather
+  // carries each pixel's sample count, so the gathered image and its reconstruction rest on it. Needs
+  // EnableMoments; ImageEnableAdaptive resets the frame like OnResize. ImageSampleCounts: the whole image, after a
+  // gather (any readback of a multi-GPU tracer runs one; GatherEstimate is one).
+  void ImageEnableAdaptive(bool on = true) { Check(rt2_tracer_image_enable_adaptive(t_.get(), on ? 1 : 0)); }
+  rt2_adaptive ImageAdaptiveCheck(float threshold, int window = 1) {
+    rt2_adaptive a{};
+    Check(rt2_tracer_image_adaptive_check(t_.get(), threshold, window, &a));
+    return a;
+  }
+  rt2_adaptive ImageRenderAdaptive(const Scene& /*scene*/, float threshold, int max_frames, int window = 1,
+                                   int min_frames = 0, int check_every = 0) {
+    Sync();
+    rt2_adaptive a{};
+    Check(rt2_tracer_image_render_adaptive(t_.get(), threshold, window, min_frames, max_frames, check_every, &a));
+    return a;
+  }
+  [[nodiscard]] std::vector<uint32_t> ImageSampleCounts() const {
+    std::vector<uint32_t> out(ImagePixels());
+    Check(rt2_tracer_image_sample_counts(t_.get(), out.data()));
+    return out;
+  }
   [[nodiscard]] bool Query() {
     const int q = rt2_tracer_query(t_.get());
     Check(q);

@@ -261,6 +261,13 @@ def _load():
         "rt2_tracer_image_move_camera": (i32, [vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(TemporalParams)]),
         "rt2_tracer_image_present_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
         "rt2_deinterleave_estimate_host": (i32, [fp, fp, fp, fp, fp, i32, i32, i32, i32, i64]),
+        "rt2_tracer_image_enable_adaptive": (i32, [vp, i32]),
+        "rt2_tracer_image_adaptive_check": (i32, [vp, f32, i32, ctypes.POINTER(Adaptive)]),
+        "rt2_tracer_image_render_adaptive": (i32, [vp, f32, i32, i32, i32, i32, ctypes.POINTER(Adaptive)]),
+        "rt2_tracer_image_part_adaptive": (i32, [vp, i32, ctypes.POINTER(Adaptive)]),
+        "rt2_tracer_image_sample_counts": (i32, [vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "rt2_deinterleave_adaptive_host": (i32, [fp, fp, ctypes.POINTER(ctypes.c_uint32), fp, fp, fp,
+                                                 ctypes.POINTER(ctypes.c_uint32), i32, i32, i32, i32]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

@@ -60,14 +60,16 @@ static void ForSceneBuffers(T* t, Fn&& f) {
 template <typename T, typename Fn>
 static void ForFrameBuffers(T* t, Fn&& f) {
   for (auto* d : {&t->d_accum, &t->d_pixels, &t->d_ray_counts, &t->d_moment2, &t->d_noise, &t->d_counts, &t->d_active,
-                  &t->d_over, &t->d_list, &t->d_slot_of, &t->d_ad_scratch})
+                  &t->d_over, &t->d_list, &t->d_slot_of, &t->d_ad_scratch, &t->d_check_sum})
     f(*d);
   f(t->recon);
 }
 // A root's gathered image, its estimate (capi_multi.cpp) and its reconstruction: the history goes with the image.
 template <typename T, typename Fn>
 static void ForImageBuffers(T* t, Fn&& f) {
-  for (auto* d : {&t->d_stacks, &t->d_image, &t->d_image_nc, &t->d_image_px, &t->d_stacks2, &t->d_image_var}) f(*d);
+  for (auto* d : {&t->d_stacks, &t->d_image, &t->d_image_nc, &t->d_image_px, &t->d_stacks2, &t->d_image_var,
+                  &t->d_stacks_n, &t->d_image_n})
+    f(*d);
   f(t->image_recon);
 }
 static void Release(DeviceBuffer& d) { d.reset(); }
@@ -79,6 +81,7 @@ void FreeImage(rt2_tracer* t) {
   ForImageBuffers(t, [](auto& d) { Release(d); });
   t->image_frame = -1;
   t->estimate_frame = -1;
+  t->image_counts = false;
 }
 
 static void FreeFrame(rt2_tracer* t) {
@@ -113,6 +116,9 @@ int Realloc(rt2_tracer* t) {
   if (t->adaptive_on) {
     const size_t tiles = AdaptiveTiles(t->width, std::max(t->local_rows, 1));
     const size_t blocks = AdaptiveBlocks((uint32_t)n);
+    // the padded stack, like d_accum (n counts AllocRows): a gather with image_adaptive on sends BandRowsMax rows
+    // of counts from every rank, and a rank with fewer rows must not be read past its end; ResetFrame zeroes the
+    // padding and no kernel writes it
     HIP_TRY(t->d_counts.Alloc(n * sizeof(uint32_t)));
     HIP_TRY(t->d_active.Alloc(n));
     HIP_TRY(t->d_over.Alloc(n));
@@ -131,6 +137,7 @@ int ResetFrame(rt2_tracer* t) {
   t->image_frame = -1;
   t->estimate_frame = -1;
   t->n_active = (uint32_t)((size_t)t->width * (size_t)t->local_rows);  // adaptive: every pixel active again
+  t->last_check = {};
   if (n == 0) return RT2_OK;
   HIP_TRY(hipSetDevice(t->device));
   HIP_TRY(hipMemsetAsync(t->d_accum.get<float>(), 0, n * 3 * sizeof(float), t->stream));
@@ -530,6 +537,7 @@ rt2_tracer::~rt2_tracer() {
   image_recon.DestroyEvents();
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
+  if (h_check) (void)hipHostFree(h_check);
   FreeFrame(this);
   ForSceneBuffers(this, [](auto& d) { Release(d); });
   for (auto& sl : slots) {
@@ -1180,12 +1188,18 @@ int rt2_tracer_accumulation(rt2_tracer* t, float* out) {
 }
 
 int rt2_tracer_non_converted_pixels(rt2_tracer* t, float* out) {
+  if (t && out && IsMulti(t) && t->parts[0]->image_adaptive) {
+    // adaptive sampling of the gathered image: the counts travelled with the gather and the root's kernel divided
+    // each pixel's sum by its own (the same IEEE quotient as the host's below)
+    int rc = GatherMulti(t);
+    return rc != RT2_OK ? rc : rt2_tracer_image_non_converted_pixels(t, out);
+  }
   int rc = rt2_tracer_accumulation(t, out);
   if (rc != RT2_OK) return rc;
   size_t n = (size_t)t->width * (size_t)rt2_tracer_local_rows(t) * 3;
   if (t->adaptive_on) {  // adaptive sampling: each pixel's sum over its own sample count
     std::vector<uint32_t> np(n / 3);
-    if ((rc = rt2_tracer_sample_counts(t, np.data())) != RT2_OK) return rc;
+    if ((rc = SampleCountsLocal(t, np.data())) != RT2_OK) return rc;
     for (size_t i = 0; i < n; i++) out[i] = out[i] / (float)np[i / 3];
     return RT2_OK;
   }

@@ -89,7 +89,7 @@ struct Chain {
   int64_t frames;
   // the estimate: the sums (LaunchDenoiseInputs divides and takes the variance; counts: adaptive sampling's, or
   // null), or with accum null the resolved colour and variance of the mean (the gather's kernel has done both;
-  // they are copied)
+  // they are copied; counts: the gathered n_p when the ranks sent them, the blend's lengths, or null)
   const float *accum = nullptr, *moment2 = nullptr;
   const uint32_t* counts = nullptr;
   const float *color = nullptr, *variance = nullptr;
@@ -112,6 +112,9 @@ static Chain ImageChain(rt2_tracer* r) {
   Chain c(r, r->image_recon, r->width, r->height, r->estimate_frame);
   c.color = r->d_image_nc.get<float>();
   c.variance = r->d_image_var.get<float>();
+  // gathered with the ranks' sample counts (adaptive sampling of the gathered image): the gather's kernel divided
+  // by each pixel's own n_p, and the blend's length is that n_p, as in LocalChain
+  if (r->image_counts) c.counts = r->d_image_n.get<uint32_t>();
   return c;
 }
 
@@ -733,7 +736,7 @@ int rt2_tracer_image_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, cons
   const rt2_tracer* first = IsMulti(t) ? t->parts[0] : t;
   if (!IsMulti(t) && !t->comm && t->world > 1)
     return Fail(RT2_ERR_INVALID, "image_move_camera: a partitioned tracer must be joined to a communicator");
-  if (first->adaptive_on)
+  if (first->adaptive_on && !first->image_adaptive)
     return Fail(RT2_ERR_INVALID, "image_move_camera: adaptive sampling is on (rt2_tracer_move_camera keeps its history)");
   const size_t n = (size_t)first->width * (size_t)first->height;
   if (first->moments_on && first->frame_idx + first->queued >= 2 && n > 0) {

@@ -53,17 +53,38 @@ int EnsureEstimate(rt2_tracer* root) {
   return RT2_OK;
 }
 
+// The root's stacks of the gathered sample counts and n_p in image order (a gather of ranks with image_adaptive
+// on), sized like EnsureImage's buffers, which it runs after (EnsureImage frees these with the image); a root
+// whose ranks never switch image_adaptive on allocates neither.
+int EnsureCounts(rt2_tracer* root) {
+  const size_t npix = (size_t)root->width * (size_t)root->height;
+  const size_t stacks = (size_t)root->world * (size_t)BandRowsMax(root) * (size_t)root->width * sizeof(uint32_t);
+  if (root->d_stacks_n.bytes() == stacks && root->d_image_n.bytes() == npix * sizeof(uint32_t)) return RT2_OK;
+  HIP_TRY(hipSetDevice(root->device));
+  HIP_TRY(root->d_stacks_n.Alloc(stacks));
+  HIP_TRY(root->d_image_n.Alloc(npix * sizeof(uint32_t)));
+  NoteDeviceBytes(root);
+  return RT2_OK;
+}
+
 // Gathers the band stacks of `ranks` (every rank this thread drives: a multi tracer's parts, or
 // one joined tracer) to rank 0 and de-interleaves them there. RCCL unless `loopback` (the ranks
 // share one GPU and their stacks are copied on it). Enqueued on the streams; does not wait.
 // estimate: the stacks of the sums of squares travel with them (the same RCCL group, or copies on the
 // root's stream), and the root's kernel also writes the variance of the mean (rt2_tracer_gather_estimate);
-// its refusals come before anything is enqueued.
+// its refusals come before anything is enqueued. With image_adaptive on (rt2.h "Adaptive sampling of the gathered
+// image") every rank's stack of sample counts travels too, as a third transfer of the same group, and the root's
+// kernel divides each pixel's sum by its own count; the ranks must agree on it (checked here for the ranks this
+// thread drives, before anything is enqueued).
 int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback, bool estimate) {
   rt2_tracer* root = nullptr;
+  const bool counts = ranks[0]->image_adaptive;
+  for (const rt2_tracer* p : ranks)
+    if (p->image_adaptive != counts)
+      return Fail(RT2_ERR_INVALID, "gather: the ranks disagree on adaptive sampling of the gathered image");
   if (estimate) {
     for (const rt2_tracer* p : ranks) {
-      if (p->adaptive_on)
+      if (p->adaptive_on && !p->image_adaptive)
         return Fail(RT2_ERR_INVALID, "gather_estimate: adaptive sampling is on (the gathered estimate divides by one "
                                      "frame index)");
       if (!p->moments_on) return Fail(RT2_ERR_INVALID, "gather_estimate: moments not enabled (rt2_tracer_enable_moments)");
@@ -84,11 +105,13 @@ int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback, bool estim
     if (p->width != r0->width || p->height != r0->height || p->frame_idx != r0->frame_idx)
       return Fail(RT2_ERR_INVALID, "gather: the ranks disagree on dims or frame index");
   const size_t count = (size_t)BandRowsMax(r0) * (size_t)r0->width * 3;  // floats per rank
+  const size_t count_n = count / 3;                                       // sample counts per rank
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (root) {
     int rc = EnsureImage(root);
     if (rc != RT2_OK) return rc;
     if (estimate && (rc = EnsureEstimate(root)) != RT2_OK) return rc;
+    if (counts && (rc = EnsureCounts(root)) != RT2_OK) return rc;
     HIP_TRY(hipSetDevice(root->device));
     e0 = TakeEvent(root);
     e1 = TakeEvent(root);
@@ -110,6 +133,9 @@ int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback, bool estim
         if (estimate)
           HIP_TRY(hipMemcpyAsync(root->d_stacks2.get<float>() + (size_t)p->rank * count, p->d_moment2.get<float>(),
                                  count * sizeof(float), hipMemcpyDeviceToDevice, root->stream));
+        if (counts)  // d_counts is as tall as d_accum (capi.cpp Realloc): the padding rows are there, and zero
+          HIP_TRY(hipMemcpyAsync(root->d_stacks_n.get<uint32_t>() + (size_t)p->rank * count_n, p->d_counts.get<uint32_t>(),
+                                 count_n * sizeof(uint32_t), hipMemcpyDeviceToDevice, root->stream));
       }
       // later work on a part's stream (Render, Reset) must not overwrite its accumulation (or its sums of
       // squares) while the root's copy may still read it: every part stream waits for all the copies
@@ -140,13 +166,27 @@ int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback, bool estim
           (void)ncclGroupEnd();
           return Fail(RT2_ERR_HIP, std::string("ncclGather: ") + ncclGetErrorString(r));
         }
+        if (counts)
+          r = ncclGather(p->d_counts.get<uint32_t>(), p == root ? root->d_stacks_n.get<uint32_t>() : nullptr, count_n,
+                         ncclUint32, 0, p->comm, p->stream);
+        if (r != ncclSuccess) {
+          (void)ncclGroupEnd();
+          return Fail(RT2_ERR_HIP, std::string("ncclGather: ") + ncclGetErrorString(r));
+        }
       }
       NCCL_TRY(ncclGroupEnd());
     }
   }
   if (root) {
     HIP_TRY(hipSetDevice(root->device));
-    if (estimate)
+    if (counts)
+      HIP_TRY(LaunchDeinterleaveAdaptive(root->d_stacks.get<float>(), estimate ? root->d_stacks2.get<float>() : nullptr,
+                                         root->d_stacks_n.get<uint32_t>(), root->d_image.get<float>(),
+                                         root->d_image_nc.get<float>(), root->d_image_px.get<uint8_t>(),
+                                         estimate ? root->d_image_var.get<float>() : nullptr,
+                                         root->d_image_n.get<uint32_t>(), root->width, root->height, BandH(root),
+                                         root->world, BandRowsMax(root), root->stream));
+    else if (estimate)
       HIP_TRY(LaunchDeinterleaveEstimate(root->d_stacks.get<float>(), root->d_stacks2.get<float>(),
                                          root->d_image.get<float>(), root->d_image_nc.get<float>(),
                                          root->d_image_px.get<uint8_t>(), root->d_image_var.get<float>(), root->width,
@@ -159,6 +199,7 @@ int GatherRanks(const std::vector<rt2_tracer*>& ranks, bool loopback, bool estim
     if (e1) HIP_TRY(hipEventRecord(e1, root->stream));
     if (e0 && e1) root->gpending.emplace_back(e0, e1);
     root->image_frame = root->frame_idx;
+    root->image_counts = counts;
     root->gathers++;
   }
   // every rank notes the estimate it took part in (the root's is the one its variance plane holds)
@@ -291,6 +332,7 @@ int rt2_tracer_join(rt2_tracer* t, const uint8_t* unique_id, int world, int rank
   if (!t || !unique_id) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: null argument");
   if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: a multi-GPU tracer has its own communicators");
   if (t->comm) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: already joined");
+  // (also after rt2_tracer_image_enable_adaptive, which is called on the joined tracer: rt2.h)
   if (t->adaptive_on) return Fail(RT2_ERR_INVALID, "rt2_tracer_join: adaptive sampling is on (one-GPU tracers only)");
   int rc = rt2_tracer_set_partition(t, band_h > 0 ? band_h : kDefaultBandH, rank, world);
   if (rc != RT2_OK) return rc;
@@ -359,6 +401,22 @@ int rt2_tracer_image_pixels(rt2_tracer* t, uint8_t* out) {
   return RT2_OK;
 }
 
+// n_p of the gathered image (rt2.h "Adaptive sampling of the gathered image"): what the gather's kernel wrote in
+// image order from the ranks' stacks of counts
+int rt2_tracer_image_sample_counts(rt2_tracer* t, uint32_t* out) {
+  if (!t || !out) return Fail(RT2_ERR_INVALID, "null argument");
+  const rt2_tracer* first = IsMulti(t) ? t->parts[0] : t;
+  if (!first->image_adaptive)
+    return Fail(RT2_ERR_INVALID, "adaptive sampling of the gathered image not enabled (rt2_tracer_image_enable_adaptive)");
+  rt2_tracer* r = nullptr;
+  int rc = ImageRoot(t, &r);
+  if (rc != RT2_OK) return rc;
+  if (!r->image_counts) return Fail(RT2_ERR_INVALID, "no gathered sample counts (call rt2_tracer_gather first)");
+  const size_t n = (size_t)r->width * (size_t)r->height;
+  if (n) HIP_TRY(hipMemcpy(out, r->d_image_n.get<uint32_t>(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT2_OK;
+}
+
 // ---- reconstructing the gathered image (rt2.h): the gather's side; the chain is in capi_filter.cpp ----
 int rt2_tracer_gather_estimate(rt2_tracer* t) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
@@ -397,6 +455,36 @@ int rt2_deinterleave_estimate_host(const float* stacks, const float* stacks2, fl
         image_nc[3 * i + c] = a[c] / fi;
       }
       variance[i] = DenoiseVarianceOfSem(NoiseOfPixel(a, q, frames).sem);
+    }
+  }
+  return RT2_OK;
+}
+
+int rt2_deinterleave_adaptive_host(const float* stacks, const float* stacks2, const uint32_t* counts, float* image,
+                                   float* image_nc, float* variance, uint32_t* image_counts, int width, int height,
+                                   int band_h, int world) {
+  if (!stacks || !counts || !image || !image_nc || !image_counts || width < 0 || height < 0 || band_h < 0 || world < 1)
+    return Fail(RT2_ERR_INVALID, "bad de-interleave arguments");
+  if ((stacks2 == nullptr) != (variance == nullptr))
+    return Fail(RT2_ERR_INVALID, "deinterleave_adaptive: stacks2 and variance come together, or both NULL");
+  const size_t max_rows = (size_t)rt2::BandRowsMax(height, band_h, world);
+  for (int y = 0; y < height; y++) {
+    const BandRow src = BandSource(y, band_h, world);
+    for (int x = 0; x < width; x++) {
+      const size_t from = ((size_t)src.rank * max_rows + (size_t)src.row) * (size_t)width + (size_t)x;
+      const size_t i = (size_t)y * (size_t)width + (size_t)x;
+      const uint32_t n = counts[from];
+      const float fn = (float)n;
+      const float a[3] = {stacks[3 * from], stacks[3 * from + 1], stacks[3 * from + 2]};
+      for (int c = 0; c < 3; c++) {
+        image[3 * i + c] = a[c];
+        image_nc[3 * i + c] = a[c] / fn;
+      }
+      image_counts[i] = n;
+      if (variance) {
+        const float q[3] = {stacks2[3 * from], stacks2[3 * from + 1], stacks2[3 * from + 2]};
+        variance[i] = DenoiseVarianceOfSem(NoiseOfPixel(a, q, (int64_t)n).sem);
+      }
     }
   }
   return RT2_OK;

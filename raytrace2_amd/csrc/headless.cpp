@@ -20,6 +20,9 @@
 // filter at its defaults, --denoise-iterations N passes) where it wrote the plain one; it composes with
 // --noise-target and --adaptive and needs at least 2 frames. With --gpus N it writes RayTracer::ImageResolve of
 // the gathered image (temporal off, denoise on: the same filter over the gathered estimate, the same bytes).
+// --gpus N --adaptive THRESHOLD takes the members for adaptive sampling of the gathered image (ImageEnableAdaptive,
+// ImageRenderAdaptive: every GPU's check, the scalars summed, the sample counts gathered with the image) and prints
+// the same line; the image is the one-GPU command's, byte for byte.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -112,14 +115,16 @@ int main(int argc, char** argv) {
     tracer.camera = &scene.cam;
     tracer.OnResize(dims);
     if (until || adapt || denoise) tracer.EnableMoments();
-    if (adapt) tracer.EnableAdaptive();
+    if (adapt && gpus > 0) tracer.ImageEnableAdaptive();
+    else if (adapt) tracer.EnableAdaptive();
 
     const auto t0 = std::chrono::steady_clock::now();
     if (until) {
       const rt2_noise nz = tracer.RenderUntil(scene, noise_target, (int)settings.num_samples);
       std::fprintf(stderr, "frames %zu rms %.9g\n", (size_t)tracer.FrameIdx(), (double)nz.rms);
     } else if (adapt) {
-      const rt2_adaptive a = tracer.RenderAdaptive(scene, adaptive, (int)settings.num_samples, window);
+      const rt2_adaptive a = gpus > 0 ? tracer.ImageRenderAdaptive(scene, adaptive, (int)settings.num_samples, window)
+                                      : tracer.RenderAdaptive(scene, adaptive, (int)settings.num_samples, window);
       std::fprintf(stderr, "frames %zu active %llu samples %llu\n", (size_t)tracer.FrameIdx(),
                    (unsigned long long)a.active, (unsigned long long)a.samples);
     } else {

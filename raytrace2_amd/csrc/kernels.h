@@ -37,6 +37,9 @@ hipError_t LaunchDeinterleave(const float* stacks, float* image, float* image_nc
 hipError_t LaunchDeinterleaveEstimate(const float* stacks, const float* stacks2, float* image, float* image_nc,
                                       uint8_t* pixels, float* variance, int width, int height, int band_h, int world,
                                       int max_rows, int frame_idx, hipStream_t stream);
+hipError_t LaunchDeinterleaveAdaptive(const float* stacks, const float* stacks2, const uint32_t* counts, float* image,
+                                      float* image_nc, uint8_t* pixels, float* variance, uint32_t* image_counts, int width,
+                                      int height, int band_h, int world, int max_rows, hipStream_t stream);
 // noise.hip
 uint32_t NoiseBlocks(uint32_t npix);
 hipError_t LaunchNoise(const float* accum, const float* moment2, const uint32_t* counts, float* sem,

@@ -227,6 +227,9 @@ struct rt2_tracer {
   // adaptive.hip) and each pixel's slot in it, and the check's per-workgroup scratch. n_active is what
   // the last check left (all local pixels after a reset); launches take the list once a pixel has retired.
   bool adaptive_on = false;
+  // adaptive sampling of the gathered image (rt2_tracer_image_enable_adaptive): adaptive_on, and the counts travel
+  // with the gather. The refusals of the gathered-image calls key on adaptive_on && !image_adaptive.
+  bool image_adaptive = false;
   rt2::DeviceBuffer d_counts;
   rt2::DeviceBuffer d_active;
   rt2::DeviceBuffer d_over;
@@ -234,6 +237,12 @@ struct rt2_tracer {
   rt2::DeviceBuffer d_slot_of;
   rt2::DeviceBuffer d_ad_scratch;  // wg counts (uint2), wg offsets, classify partials, totals
   uint32_t n_active = 0;
+  // what the last check left of this tracer's own pixels (rt2_tracer_image_part_adaptive; frames 0: none since the
+  // last reset), and the image check's pinned host words and, on a joined tracer, the device words its all-reduce
+  // sums in place (capi_estimate.cpp ImageCheck; allocated at the first image check)
+  rt2_adaptive last_check = {};
+  unsigned long long* h_check = nullptr;
+  rt2::DeviceBuffer d_check_sum;
   // the reconstruction of the local rows (Recon above) and the GPU times of the last feature pass, the last
   // denoise and the last resolve's temporal kernels (-1: none), which only the local calls report
   rt2::detail::Recon recon;
@@ -326,6 +335,11 @@ struct rt2_tracer {
   rt2::DeviceBuffer d_stacks2;       // [world][max_rows][W] float3
   rt2::DeviceBuffer d_image_var;     // [H][W] float
   int64_t estimate_frame = -1;
+  // root, with image_adaptive on: the gathered stacks of the sample counts and n_p in image order, allocated at the
+  // first gather that carries them; image_counts: the last gather wrote them (the chain's lengths are then n_p)
+  rt2::DeviceBuffer d_stacks_n;      // [world][max_rows][W] uint32
+  rt2::DeviceBuffer d_image_n;       // [H][W] uint32
+  bool image_counts = false;
   rt2::detail::Recon image_recon;
   // image readbacks to the host (rt2_tracer_image_*): count and device-to-host copy time
   uint64_t readbacks = 0;
@@ -367,6 +381,15 @@ int Sync(rt2_tracer* t);
 // The RenderParams every kernel over the scene takes: the scene tables and root, background, camera, image
 // and partition, seed and Philox keys, stack depth; everything else zero.
 void BaseParams(const rt2_tracer* t, const CameraParams& cam, RenderParams* p);
+// capi_estimate.cpp: the two halves of an adaptive check over the tracer's local pixels, whose frames are launched
+// and number at least 2. Enqueue: the check's kernels on the tracer's stream and, with `host` not null, the copy
+// of their totals into it; d_totals (or null) receives where the totals lie on the device. Nothing is enqueued for
+// a tracer without a pixel (*host zeroed). Finish, after the stream has been waited for: the local totals become
+// the tracer's n_active and last_check, and *out (or null).
+int EnqueueAdaptiveCheck(rt2_tracer* t, float threshold, int window, rt2::AdaptiveTotals* host,
+                         rt2::AdaptiveTotals** d_totals);
+int FinishAdaptiveCheck(rt2_tracer* t, const rt2::AdaptiveTotals& h, rt2_adaptive* out);
+int SampleCountsLocal(rt2_tracer* t, uint32_t* out);  // n_p per local pixel of an adaptive one-GPU tracer (blocks)
 // capi_multi.cpp
 int GatherMulti(rt2_tracer* t);
 int GatherEstimate(rt2_tracer* t);  // rt2_tracer_gather_estimate: the gather with the sums of squares

@@ -10,6 +10,7 @@ a single-GPU render. The only exchange is this gather.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional
 
 import numpy as np
@@ -50,6 +51,30 @@ def deinterleave_estimate(stacks: np.ndarray, stacks2: np.ndarray, height: int, 
     check(lib.rt2_deinterleave_estimate_host(_fp(stacks), _fp(stacks2), _fp(image), _fp(mean), _fp(var), w, height,
                                              int(band_h), world, int(frames)))
     return image, mean, var
+
+
+def deinterleave_adaptive(stacks: np.ndarray, stacks2: Optional[np.ndarray], counts: np.ndarray, height: int, band_h: int):
+    """Rank-major padded band stacks (world, max_rows, W, 3) of the sums and (or None) of their squares, and
+    (world, max_rows, W) uint32 of each pixel's sample count -> (sums, means, variance of the mean or None, counts) in
+    image order: the host statement of the gather's kernel under adaptive sampling of the gathered image
+    (rt2_deinterleave_adaptive_host), each pixel divided by its own count."""
+    stacks = np.ascontiguousarray(stacks, np.float32)
+    counts = np.ascontiguousarray(counts, np.uint32)
+    world, max_rows, w, c = stacks.shape
+    if stacks2 is not None:
+        stacks2 = np.ascontiguousarray(stacks2, np.float32)
+    if (c != 3 or counts.shape != (world, max_rows, w) or (stacks2 is not None and stacks2.shape != stacks.shape)
+            or max_rows != band_rows_max(height, band_h, world)):
+        raise ValueError("deinterleave_adaptive: need (world, band_rows_max, W, 3) stacks and (world, band_rows_max, W) counts")
+    image, mean = np.empty((height, w, 3), np.float32), np.empty((height, w, 3), np.float32)
+    var = np.empty((height, w), np.float32) if stacks2 is not None else None
+    n = np.empty((height, w), np.uint32)
+    u32 = ctypes.POINTER(ctypes.c_uint32)
+    check(lib.rt2_deinterleave_adaptive_host(_fp(stacks), _fp(stacks2) if stacks2 is not None else None,
+                                             counts.ctypes.data_as(u32), _fp(image), _fp(mean),
+                                             _fp(var) if var is not None else None, n.ctypes.data_as(u32), w, height,
+                                             int(band_h), world))
+    return image, mean, var, n
 
 
 def source_rows(height: int, band_h: int, world: int) -> np.ndarray:

@@ -756,6 +756,43 @@ class RayTracer:
         check(lib.rt2_tracer_image_present_time(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # -- adaptive sampling of the gathered image (rt2.h "Adaptive sampling of the gathered image") -----
+    # adaptive sampling for create_multi and joined tracers (and plain ones): the counts travel with the gather.
+    def image_enable_adaptive(self, on: bool = True) -> None:
+        """enable_adaptive() on every GPU of the tracer (on a joined tracer: on this rank, after join()); gathers
+        then carry each pixel's sample count (needs enable_moments; resets the frame)."""
+        check(lib.rt2_tracer_image_enable_adaptive(self._h, 1 if on else 0))
+
+    def image_adaptive_check(self, threshold: float, window: int = 1) -> dict:
+        """adaptive_check() on every GPU, the checks overlapping; rt2_adaptive of the whole image as a dict
+        (collective on joined tracers: every rank gets the same dict)."""
+        a = Adaptive()
+        check(lib.rt2_tracer_image_adaptive_check(self._h, float(threshold), int(window), ctypes.byref(a)))
+        return a.as_dict()
+
+    def image_render_adaptive(self, threshold: float, max_frames: int, window: int = 1, min_frames: int = 0,
+                              check_every: int = 0) -> dict:
+        """render_adaptive() over image_adaptive_check(): until the whole image has no active pixel or FrameIdx()
+        reaches max_frames; returns the last check."""
+        self._push_camera()
+        a = Adaptive()
+        check(lib.rt2_tracer_image_render_adaptive(self._h, float(threshold), int(window), int(min_frames),
+                                                   int(max_frames), int(check_every), ctypes.byref(a)))
+        return a.as_dict()
+
+    def image_part_adaptive(self, part: int) -> dict:
+        """The last check's rt2_adaptive of GPU `part` alone, before the sum over the GPUs."""
+        a = Adaptive()
+        check(lib.rt2_tracer_image_part_adaptive(self._h, int(part), ctypes.byref(a)))
+        return a.as_dict()
+
+    def image_sample_counts(self) -> np.ndarray:
+        """uint32 sample count n_p per pixel of the gathered image, (H, W), on rank 0 (after gather())."""
+        w, h = self.Dims()
+        out = np.zeros((h, w), np.uint32)
+        check(lib.rt2_tracer_image_sample_counts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
     def enable_stats(self, on: bool = True) -> None:
         check(lib.rt2_tracer_enable_stats(self._h, 1 if on else 0))
 
