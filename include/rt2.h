@@ -656,6 +656,44 @@ RT2_API int rt2_deinterleave_adaptive_host(const float* stacks, const float* sta
                                            float* variance /* may be NULL */, uint32_t* image_counts, int width,
                                            int height, int band_h, int world);
 
+/* ---- Ray queries ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before.
+ * The scene's closest Hit for rays the caller owns (picking, focusing, visibility between two points, feature
+ * buffers for a camera of the caller's own), n rays per call, traced by the kernels' traversal: the threaded
+ * program where the scene has one, else the stack walk (raytrace2_amd/csrc/query.h holds the layouts and the rule).
+ * A ray, 8 floats: ox oy oz tmax | dx dy dz time. The interval is (0.001, tmax); FLT_MAX is "unbounded". The
+ *   direction is taken as given, not normalised, so t is in units of |d|, as the reference's Hit sees it.
+ * An answer, 16 floats, the feature record's layout: 0 flag: 1 hit, 0 miss, -1 not traced; 1 t (model-space under
+ *   a transformed child, the reference's quirk); 2-4 point; 5-7 normal (facing against the ray); 8 front_face; 9
+ *   material index; 10-12 albedo by the feature pass's rule: the material table's albedo (metal, lambertian), (1, 1,
+ *   1) (dielectric), Texture::Value at the hit (texture, diffuse_light, isotropic); 13 dist = sqrt(dot(point - o,
+ *   point - o)); 14-15 0; every operation rounded on its own. A miss: slot 0 = 0, the background in 10-12, every
+ *   other slot 0. A ray that was not traced: slot 0 = -1, every other slot 0.
+ * A ConstantMedium on the way draws from the path stream (`seed`, pixel 0xFFFFFFF0, frame 0) from its start, the
+ *   same for every ray of the call: with the tracer's seed, a normalised pixel-centre ray, tmax FLT_MAX and time 0
+ *   the answer is rt2_tracer_features' record of that pixel, bit for bit.
+ * query_ray_valid: whether a ray is traced (1) or answered -1 (0): all eight words finite; 0.001 < tmax; 0 <= time
+ *   <= 1; every origin coordinate within +-2^64; the largest of |dx|, |dy|, |dz| within [2^-20, 2^20] (so d != 0):
+ *   the domain on which the kernels' exact shortcuts are proven. It contains every unit direction and the
+ *   un-normalised pixel-centre rays of the shipped scenes' cameras. NULL: 0.
+ * intersect: host buffers. It launches queued frames first, as a readback does, copies in, traces and copies out
+ *   in chunks of at most RT2_QUERY_CHUNK rays (environment, read at every call, default 2^22, rounded up to a
+ *   multiple of 64) through two device buffers the tracer keeps and grows on demand, and synchronises.
+ * intersect_device: device pointers on the tracer's device. It only enqueues on the tracer's stream and returns at
+ *   once, adds nothing to rt2_stats.host_waits and is complete after rt2_tracer_synchronize or when
+ *   rt2_tracer_query returns 1. It does not launch queued frames.
+ * intersect_time: GPU time (HIP events) of the last call's kernels (every chunk's, not the copies), in ms; -1
+ *   while that call has not finished, or when there was none. It polls the events and never waits.
+ * A call changes no render state: accumulation, moments, counts, FrameIdx(), feature cache and history are
+ *   unchanged. It works before on_resize, and on a set_partition or joined tracer (the scene is whole on every
+ *   rank and no image is involved). n == 0 is RT2_OK and does nothing.
+ * RT2_ERR_INVALID: a NULL tracer or pointer; n < 0 or n >= 2^31; a create_multi tracer; a scene whose stack is
+ *   deeper than the kernel's with the threaded traversal off (RT2_NO_LINEAR). A refused call changes nothing. */
+RT2_API int rt2_query_ray_valid(const float* ray8);
+RT2_API int rt2_tracer_intersect(rt2_tracer* tr, int64_t n, const float* rays, uint64_t seed, float* out);
+RT2_API int rt2_tracer_intersect_device(rt2_tracer* tr, int64_t n, const float* d_rays, uint64_t seed, float* d_out);
+RT2_API int rt2_tracer_intersect_time(rt2_tracer* tr, double* ms);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -427,6 +427,25 @@ class RayTracer {
     Check(rt2_tracer_image_sample_counts(t_.get(), out.data()));
     return out;
   }
+  // Ray queries (rt2.h "Ray queries"): the scene's closest hit for n rays of the caller, 8 floats each (ox oy oz
+  // tmax dx dy dz time) -> 16 floats each in the feature record's layout (slot 0: 1 hit, 0 miss, -1 not traced,
+  // RayValid). seed keys a ConstantMedium's draws (the default: the tracer's). Intersect: host buffers; it runs
+  // the queued frames and blocks. IntersectDevice: device pointers on the tracer's GPU; it only enqueues and is
+  // complete after Synchronize() or when Query() returns true. IntersectTime: GPU ms of the last call's kernels
+  // (-1: not finished, or none); never waits.
+  static constexpr uint64_t kDefaultSeed = 0x5EED2024ull;
+  static bool RayValid(const float* ray8) { return rt2_query_ray_valid(ray8) == 1; }
+  void Intersect(const float* rays, int64_t n, float* out, uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_intersect(t_.get(), n, rays, seed, out));
+  }
+  void IntersectDevice(const float* d_rays, int64_t n, float* d_out, uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_intersect_device(t_.get(), n, d_rays, seed, d_out));
+  }
+  [[nodiscard]] double IntersectTime() {
+    double ms = -1.0;
+    Check(rt2_tracer_intersect_time(t_.get(), &ms));
+    return ms;
+  }
   [[nodiscard]] bool Query() {
     const int q = rt2_tracer_query(t_.get());
     Check(q);

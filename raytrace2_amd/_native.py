@@ -268,6 +268,10 @@ def _load():
         "rt2_tracer_image_sample_counts": (i32, [vp, ctypes.POINTER(ctypes.c_uint32)]),
         "rt2_deinterleave_adaptive_host": (i32, [fp, fp, ctypes.POINTER(ctypes.c_uint32), fp, fp, fp,
                                                  ctypes.POINTER(ctypes.c_uint32), i32, i32, i32, i32]),
+        "rt2_query_ray_valid": (i32, [fp]),
+        "rt2_tracer_intersect": (i32, [vp, i64, fp, u64, fp]),
+        "rt2_tracer_intersect_device": (i32, [vp, i64, vp, u64, vp]),
+        "rt2_tracer_intersect_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

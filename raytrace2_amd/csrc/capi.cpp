@@ -53,7 +53,8 @@ int LocalRows(int h, int band_h, int rank, int world) {
 template <typename T, typename Fn>
 static void ForSceneBuffers(T* t, Fn&& f) {
   for (auto* d : {&t->d_nodes, &t->d_materials, &t->d_textures, &t->d_perlin_vec, &t->d_perlin_perm, &t->d_lin,
-                  &t->d_lin_wide, &t->d_lind, &t->d_hit, &t->d_flat_wide, &t->d_flat_cert, &t->d_work, &t->d_stats})
+                  &t->d_lin_wide, &t->d_lind, &t->d_hit, &t->d_flat_wide, &t->d_flat_cert, &t->d_work, &t->d_stats,
+                  &t->d_query_rays, &t->d_query_hits})
     f(*d);
 }
 // The frame buffers of the local rows, with their reconstruction.
@@ -535,6 +536,8 @@ rt2_tracer::~rt2_tracer() {
   for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
   recon.DestroyEvents();
   image_recon.DestroyEvents();
+  if (query_e0) (void)hipEventDestroy(query_e0);
+  if (query_e1) (void)hipEventDestroy(query_e1);
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
   if (h_check) (void)hipHostFree(h_check);

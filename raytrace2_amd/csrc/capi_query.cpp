@@ -1,0 +1,171 @@
+// capi_query.cpp — the ray queries of include/rt2.h ("Ray queries"): the scene's closest Hit for rays the caller
+// owns, over render.hip's query kernel. Planned by launch_plan.h PlanQuery; the layouts and the validity rule are
+// query.h's.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "launch_plan.h"
+#include "query.h"
+#include "tracer.h"
+
+using namespace rt2;
+using namespace rt2::detail;
+
+namespace {
+
+constexpr int64_t kQueryChunkDefault = (int64_t)1 << 22;
+
+// Most rays per launch of the host entry: RT2_QUERY_CHUNK, read at every call, rounded up to whole waves.
+int64_t QueryChunk() {
+  int64_t c = kQueryChunkDefault;
+  if (const char* e = getenv("RT2_QUERY_CHUNK")) {
+    const long long v = atoll(e);
+    if (v > 0) c = std::min<long long>(v, 0x7FFFFFC0ll);
+  }
+  return (c + 63) / 64 * 64;
+}
+
+int CheckCall(const rt2_tracer* t, int64_t n, const void* rays, const void* out, const char* call) {
+  // (the arguments first: these refusals need no tracer, so they can be checked without a device)
+  if (n < 0 || n >= ((int64_t)1 << 31)) return Fail(RT2_ERR_INVALID, std::string(call) + ": need 0 <= n < 2^31");
+  if (!rays || !out) return Fail(RT2_ERR_INVALID, std::string(call) + ": null pointer");
+  if (!t) return Fail(RT2_ERR_INVALID, std::string(call) + ": null tracer");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, std::string(call) + ": not on a create_multi tracer");
+  return RT2_OK;
+}
+
+// The launch parameters of a query with this seed and its plan for n rays; refuses a scene no traversal serves.
+int QueryParams(const rt2_tracer* t, uint64_t seed, uint32_t n, const char* call, RenderParams* p, QueryPlan* q) {
+  const CameraParams no_camera = {};  // (no camera is involved)
+  BaseParams(t, no_camera, p);
+  p->seed_lo = (uint32_t)seed;
+  p->seed_hi = (uint32_t)(seed >> 32);
+  for (uint32_t r = 0; r < 10; r++) {
+    p->philox_keys[2 * r] = p->seed_lo + r * 0x9E3779B9u;
+    p->philox_keys[2 * r + 1] = p->seed_hi + r * 0xBB67AE85u;
+  }
+  p->lin = t->d_lin.get<void>();
+  p->lin_wide = t->d_lin_wide.get<void>();
+  p->lind = t->d_lind.get<void>();
+  p->lin_len = t->use_linear ? t->lin_len : 0u;
+  p->flat_xforms = t->flat_xforms ? 1u : 0u;
+  const int variant = RenderVariant(t->features);  // (no kFeatDefocus: no camera is involved)
+  *q = PlanQuery(p->lin_len, variant, RenderVariantFeatures(variant), p->stack_depth, n, RenderBlockSize());
+  if (!q->ok)
+    return Fail(RT2_ERR_INVALID, std::string(call) + ": the scene needs a traversal stack of " + std::to_string(t->max_stack) +
+                                     " entries (kernel has " + std::to_string(kTraversalStack) +
+                                     "): only the threaded traversal can serve it");
+  return RT2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt2_query_ray_valid(const float* ray8) { return ray8 && QueryRayValid(ray8) ? 1 : 0; }
+
+int rt2_tracer_intersect(rt2_tracer* t, int64_t n, const float* rays, uint64_t seed, float* out) {
+  int rc = CheckCall(t, n, rays, out, "intersect");
+  if (rc != RT2_OK) return rc;
+  if (n == 0) return RT2_OK;
+  const int64_t chunk = std::min(QueryChunk(), (n + 63) / 64 * 64);
+  RenderParams p;
+  QueryPlan q;
+  if ((rc = QueryParams(t, seed, (uint32_t)std::min(chunk, n), "intersect", &p, &q)) != RT2_OK) return rc;
+  if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
+  HIP_TRY(hipSetDevice(t->device));
+  const size_t ray_bytes = (size_t)chunk * kQueryRayFloats * sizeof(float);
+  const size_t hit_bytes = (size_t)chunk * kQueryHitFloats * sizeof(float);
+  if (ray_bytes > t->d_query_rays.bytes() || hit_bytes > t->d_query_hits.bytes()) {
+    // (hipFree waits for the device: nothing queued still reads the old buffers)
+    HIP_TRY(t->d_query_rays.Grow(ray_bytes));
+    HIP_TRY(t->d_query_hits.Grow(hit_bytes));
+    NoteDeviceBytes(t);
+  }
+  // one event pair per chunk around its kernel, from the tracer's pool and back to it on every way out
+  std::vector<hipEvent_t> ev;
+  struct Return {
+    rt2_tracer* t;
+    std::vector<hipEvent_t>& ev;
+    ~Return() {
+      for (hipEvent_t e : ev) t->event_pool.push_back(e);
+    }
+  } give_back{t, ev};
+  hipError_t e = hipSuccess;
+  for (int64_t at = 0; at < n && e == hipSuccess; at += chunk) {
+    const uint32_t m = (uint32_t)std::min(chunk, n - at);
+    hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
+    if (e0) ev.push_back(e0);
+    if (e1) ev.push_back(e1);
+    if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
+    e = hipMemcpyAsync(t->d_query_rays.get<float>(), rays + (size_t)at * kQueryRayFloats,
+                       (size_t)m * kQueryRayFloats * sizeof(float), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipEventRecord(e0, t->stream);
+    if (e == hipSuccess) e = LaunchQuery(p, q.variant, t->d_query_rays.get<float>(), t->d_query_hits.get<float>(), m, t->stream);
+    if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(out + (size_t)at * kQueryHitFloats, t->d_query_hits.get<float>(),
+                         (size_t)m * kQueryHitFloats * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+    // (a pageable host buffer makes each copy wait for its own completion; the buffers are reused chunk after
+    // chunk in stream order either way)
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, "intersect");
+  double ms = 0.0;
+  for (size_t k = 0; k + 1 < ev.size(); k += 2) {
+    float f = 0.0f;
+    if (hipEventElapsedTime(&f, ev[k], ev[k + 1]) != hipSuccess) {
+      ms = -1.0;
+      break;
+    }
+    ms += (double)f;
+  }
+  t->query_pending = false;
+  t->query_ms = ms;
+  return RT2_OK;
+}
+
+int rt2_tracer_intersect_device(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, float* d_out) {
+  int rc = CheckCall(t, n, d_rays, d_out, "intersect_device");
+  if (rc != RT2_OK) return rc;
+  if (n == 0) return RT2_OK;
+  RenderParams p;
+  QueryPlan q;
+  if ((rc = QueryParams(t, seed, (uint32_t)n, "intersect_device", &p, &q)) != RT2_OK) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  if (!t->query_e0 && hipEventCreate(&t->query_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  if (!t->query_e1 && hipEventCreate(&t->query_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  t->query_pending = false;
+  t->query_ms = -1.0;
+  HIP_TRY(hipEventRecord(t->query_e0, t->stream));
+  HIP_TRY(LaunchQuery(p, q.variant, d_rays, d_out, (uint32_t)n, t->stream));
+  HIP_TRY(hipEventRecord(t->query_e1, t->stream));
+  t->query_pending = true;
+  return RT2_OK;
+}
+
+int rt2_tracer_intersect_time(rt2_tracer* t, double* ms) {
+  if (!t || !ms) return Fail(RT2_ERR_INVALID, "intersect_time: null argument");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "intersect_time: not on a create_multi tracer");
+  if (t->query_pending) {
+    HIP_TRY(hipSetDevice(t->device));
+    const hipError_t q = hipEventQuery(t->query_e1);
+    if (q == hipSuccess) {
+      float f = -1.0f;
+      if (hipEventElapsedTime(&f, t->query_e0, t->query_e1) != hipSuccess) f = -1.0f;
+      t->query_ms = (double)f;
+      t->query_pending = false;
+    } else if (q != hipErrorNotReady) {
+      return HipFail(q, "intersect_time");
+    }
+  }
+  *ms = t->query_pending ? -1.0 : t->query_ms;
+  return RT2_OK;
+}
+
+}  // extern "C"

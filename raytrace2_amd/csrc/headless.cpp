@@ -7,6 +7,10 @@
 //                [--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]]
 //                [--denoise [--denoise-iterations N]]
 //
+//   rt2_headless <scene.json> --pick X Y [--size W H]
+// --pick X Y renders nothing and writes no image: it prints the hit record (rt2.h "Ray queries": 16 floats, the
+// feature record's layout) of the ray through the centre of pixel (X, Y) of a W x H image (default: the
+// scene's dims, else 1600x900) as one JSON line: the record RayTracer::Features holds for that pixel.
 // Without --settings the reference's Settings.hpp defaults apply (num_samples 1, max_depth 50);
 // --samples / --size override num_samples and the output dims (App.cpp:115-124: scene dims, else
 // 1600x900). --gpus N renders on GPUs 0..N-1 (row bands + RCCL gather, rt2_tracer_create_multi).
@@ -23,7 +27,9 @@
 // --gpus N --adaptive THRESHOLD takes the members for adaptive sampling of the gathered image (ImageEnableAdaptive,
 // ImageRenderAdaptive: every GPU's check, the scalars summed, the sample counts gathered with the image) and prints
 // the same line; the image is the one-GPU command's, byte for byte.
+#include <cfloat>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,11 +41,15 @@ int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene.json> <out.png> [--settings f] [--samples N] [--size WxH] [--gpus N] "
                          "[--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]] "
-                         "[--denoise [--denoise-iterations N]] (--denoise with --gpus N filters the gathered image)\n",
+                         "[--denoise [--denoise-iterations N]] (--denoise with --gpus N filters the gathered image)\n"
+                         "       %s <scene.json> --pick X Y [--size W H]\n",
+                 argv[0],
                  argv[0]);
     return 2;
   }
-  const std::string scene_path = argv[1], out_path = argv[2];
+  // (--pick: no output image, the options start right after the scene)
+  const bool no_image = !std::strncmp(argv[2], "--", 2);
+  const std::string scene_path = argv[1], out_path = no_image ? "" : argv[2];
   rt2::AppSettings settings;
   long samples = -1;
   rt2::ivec2 size{0, 0};
@@ -50,8 +60,10 @@ int main(int argc, char** argv) {
   int window = 1;
   bool denoise = false;
   int denoise_iterations = 0;  // 0: the default
+  bool pick = false;
+  rt2::ivec2 pick_at{0, 0};
   try {
-    for (int i = 3; i < argc; i += 2) {
+    for (int i = no_image ? 2 : 3; i < argc; i += 2) {
       if (!std::strcmp(argv[i], "--denoise")) {  // a flag: no value follows
         denoise = true;
         i -= 1;
@@ -86,12 +98,25 @@ int main(int argc, char** argv) {
         window = (int)v;
       } else if (!std::strcmp(argv[i], "--max-samples")) {
         max_samples = std::atol(argv[i + 1]);
+      } else if (!std::strcmp(argv[i], "--pick")) {  // two values follow
+        if (i + 2 >= argc || std::sscanf(argv[i + 1], "%d", &pick_at.x) != 1 || std::sscanf(argv[i + 2], "%d", &pick_at.y) != 1)
+          return 2;
+        pick = true;
+        i += 1;
       } else if (!std::strcmp(argv[i], "--size")) {
-        if (std::sscanf(argv[i + 1], "%dx%d", &size.x, &size.y) != 2) return 2;
+        if (std::sscanf(argv[i + 1], "%dx%d", &size.x, &size.y) != 2) {  // WxH, or W H
+          if (i + 2 >= argc || std::sscanf(argv[i + 1], "%d", &size.x) != 1 || std::sscanf(argv[i + 2], "%d", &size.y) != 1)
+            return 2;
+          i += 1;
+        }
       } else {
         std::fprintf(stderr, "unknown option %s\n", argv[i]);
         return 2;
       }
+    }
+    if (no_image && !pick) {
+      std::fprintf(stderr, "no output image given\n");
+      return 2;
     }
     if (samples > 0) settings.num_samples = (size_t)samples;
     const bool until = noise_target >= 0.f, adapt = adaptive >= 0.f;
@@ -108,6 +133,37 @@ int main(int argc, char** argv) {
     rt2::ivec2 dims{1600, 900};
     if (scene.dims.x != 0 && scene.dims.y != 0) dims = scene.dims;
     if (size.x > 0 && size.y > 0) dims = size;
+
+    if (pick) {
+      if (pick_at.x < 0 || pick_at.x >= dims.x || pick_at.y < 0 || pick_at.y >= dims.y) {
+        std::fprintf(stderr, "--pick: pixel outside the %dx%d image\n", dims.x, dims.y);
+        return 2;
+      }
+      // the feature pass's ray (rt2.h "Feature buffers and denoiser"), every operation rounded on its own
+      float cp[21];
+      rt2::Check(rt2_camera_params(scene.handle(), dims.x, dims.y, (int)settings.num_samples, cp));
+      float v[3], ray[8], rec[16];
+      for (int k = 0; k < 3; k++) {
+        const float pc = (cp[k] + (float)pick_at.x * cp[3 + k]) + (float)pick_at.y * cp[6 + k];
+        v[k] = pc - cp[9 + k];
+        ray[k] = cp[9 + k];
+      }
+      const float inv = 1.0f / std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+      ray[3] = FLT_MAX;
+      for (int k = 0; k < 3; k++) ray[4 + k] = v[k] * inv;
+      ray[7] = 0.0f;
+      rt2::RayTracer picker(scene, 0);
+      picker.Intersect(ray, 1, rec);
+      std::printf("{\"pick\": [%d, %d], \"size\": [%d, %d], \"record\": [", pick_at.x, pick_at.y, dims.x, dims.y);
+      for (int k = 0; k < 16; k++) {  // nine digits round-trip a float; "-0.0", not "-0": a JSON reader keeps the sign
+        char num[32];
+        std::snprintf(num, sizeof num, "%.9g", (double)rec[k]);
+        const bool integral = !std::strpbrk(num, ".e");
+        std::printf("%s%s%s", k ? ", " : "", num, integral ? ".0" : "");
+      }
+      std::printf("]}\n");
+      return 0;
+    }
 
     rt2::RayTracer tracer(scene, 0, gpus);
     tracer.max_depth = settings.max_depth;

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "query.h"
 #include "rt2_layout.h"
 
 namespace rt2 {
@@ -129,6 +130,33 @@ inline LaunchItems PlanItems(uint32_t n_chunks, uint32_t tile_items, bool frame_
   it.batch_div = (uint32_t)std::max<int64_t>(1, (resident / 64) * 2);
   it.grid = std::max((int)std::min<int64_t>(resident, (int64_t)it.n_items) / block, 1);
   return it;
+}
+
+// A ray-query launch (rt2.h "Ray queries"; render.hip query_kernel) over n rays, 0 < n < 2^31, from the scene's
+// facts: lin_len, the steps of its threaded program (0: none, or switched off); variant and variant_features,
+// the instantiation of its feature set (RenderVariant, RenderVariantFeatures); stack_depth, the entries its stack
+// walk needs; block, the workgroup's lanes. The threaded program wherever there is one, else the stack walk, which
+// has one instantiation (variant -1) and cannot serve a scene whose stack is deeper than the kernel's (ok false:
+// the call is refused). grid: workgroups over n rounded up to whole waves. lds_dynamic: what the launch asks for
+// (the stack walk's per-lane stacks); lds_static: the threaded kernels' box-boundary candidate planes (the
+// instantiations with media and no spheres, render.hip BoxPair).
+struct QueryPlan {
+  bool ok, threaded;
+  int variant;
+  uint32_t grid;
+  size_t lds_dynamic, lds_static;
+};
+inline QueryPlan PlanQuery(uint32_t lin_len, int variant, uint32_t variant_features, int stack_depth, uint32_t n,
+                           int block) {
+  QueryPlan q;
+  q.threaded = lin_len != 0;
+  q.ok = q.threaded || stack_depth <= kTraversalStack;
+  q.variant = q.threaded ? variant : -1;
+  q.grid = QueryGrid(n, (uint32_t)block);
+  q.lds_dynamic = q.threaded ? 0 : (size_t)stack_depth * (size_t)block * 4;
+  const bool planes = q.threaded && (variant_features & kFeatMedium) != 0u && (variant_features & kFeatSphere) == 0u;
+  q.lds_static = planes ? (size_t)(block / 64) * kBoundaryAAMax * 64 * 4 : 0;
+  return q;
 }
 
 }  // namespace rt2

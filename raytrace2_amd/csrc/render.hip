@@ -40,6 +40,7 @@
 #define RT2_BOXAA_FN __device__ __forceinline__
 #include "boxaa.h"
 #include "kernels.h"
+#include "query.h"
 
 namespace rt2 {
 namespace dev {
@@ -1403,14 +1404,16 @@ struct HitRef {
 
 // Stack traversal (any scene): each lane walks its own steps — LDS stack pops, or the next child of
 // a leaf list through a per-lane cursor — one step per loop trip.
-template <uint32_t F, int kMode, bool kStats, class G>
+// kTmax (the query kernel): the interval ends at the caller's tmax0 instead of FLT_MAX.
+template <uint32_t F, int kMode, bool kStats, bool kTmax = false, class G>
 __device__ __forceinline__ bool trace_stack(const RenderParams& P, const Nodes<kMode>& N, f3 wo, f3 wd, float time,
-                                            G& path, HitRef& h, uint32_t* stk, Counters& cnt, bool& overflow) {
+                                            G& path, HitRef& h, uint32_t* stk, Counters& cnt, bool& overflow,
+                                            float tmax0 = FLT_MAX) {
   f3 o = wo, d = wd;
   const f3 winv = recip3(wd);
   f3 inv = winv;
   const float tmin = 0.001f;  // Interval{0.001, kInfinity}
-  float tmax = FLT_MAX;
+  float tmax = kTmax ? tmax0 : FLT_MAX;
   bool any = false;
   uint32_t cur_xf = kRefNone;
   const int cap = P.stack_depth;
@@ -1583,10 +1586,11 @@ constexpr bool BoxOn() {
 // on the winner's certificate box from the table with the world ray: for a winner under a transform the box
 // is its transform's and T = the lane's tmax at that transform's entry (the entry rule, evaluated lazily:
 // only the winner's transform's verdict is ever read); for a winner in world space T = its t (the end rule).
-template <uint32_t F, bool kStats, bool kFlat = false, class W, class G>
+// kTmax (the query kernel): the interval ends at the caller's tmax0 (0.001 < tmax0 <= FLT_MAX) instead of FLT_MAX.
+template <uint32_t F, bool kStats, bool kFlat = false, bool kTmax = false, class W, class G>
 __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wray, float time, G& path, HitRef& h,
                                              lds_u32* cand, lds_u32* xray, Counters& cnt, bool tab = false,
-                                             bool* uncert = nullptr) {
+                                             bool* uncert = nullptr, float tmax0 = FLT_MAX) {
   const Nodes<kModeLinear> N{reinterpret_cast<const float4*>(P.lind)};  // boundaries / nested xforms
   const void* recs = P.lind;
   const void* prog = kFlat ? P.flat_wide : P.lin_wide;
@@ -1601,7 +1605,7 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   bool fin = finite3(inv);  // inv finite: the NaN-free slab test applies
   const bool wfin = fin;
   const float tmin = 0.001f;
-  float tmax = FLT_MAX;
+  float tmax = kTmax ? tmax0 : FLT_MAX;
   uint32_t prim = kRefNone;  // closest primitive so far (h.xf: its transform, quads: from the record)
   uint32_t cur_xf = kRefNone;
   f3 acc_pinv = mk(0.0f, 0.0f, 0.0f);  // accelerated list: this ray's box padding x inv
@@ -2035,7 +2039,7 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
 // The closest hit's record in world space (what the reference's rec holds after the chain of
 // TransformedHittable::Hit returns): point, normal, front_face, material. kMediumNormal (the feature pass): a
 // medium's (1, 0, 0) goes through the enclosing transforms too, as the reference's record has it; the render
-// kernels never read it.
+// kernels never read it. The query kernel takes it too, for the threaded program's records.
 template <uint32_t F, int kMode, bool kMediumNormal = false>
 __device__ __forceinline__ void resolve_hit(const Nodes<kMode>& N, const HitRef& h, f3 wo, f3 wd, float time, f3& p,
                                             f3& n, bool& front, uint32_t& mat, const lds_u32* xray = nullptr,
@@ -2069,7 +2073,9 @@ __device__ __forceinline__ void resolve_hit(const Nodes<kMode>& N, const HitRef&
     n = front ? qn : -qn;
     const float4 r3 = N[off + 3];
     mat = bits(r3.w);
-    if (Has<F, kFeatXform>() && h.xf != kRefNone) {
+    // (not with kMediumNormal, the query kernel's record as the reference has it: for a back face the negated world
+    // normal gives a zero component the opposite sign from the loop's sum of products, which no render reads)
+    if (!kMediumNormal && Has<F, kFeatXform>() && h.xf != kRefNone) {
       // the quad's world normal from the record (compile.cpp WorldNormal: the same operations as the
       // loop below on the same values); the loop then moves only the point
       const f3 wn = xyz(r3);
@@ -3187,6 +3193,112 @@ __global__ __launch_bounds__(kBlock) void features_kernel(const RenderParams P, 
 }
 
 // ------------------------------------------------------------------------------------------
+// Ray queries (rt2.h "Ray queries", query.h): the scene's Hit for n rays of the caller, one ray per lane, the
+// answer in the feature record's layout. A hot path (callers trace millions of rays), so it walks what the
+// render kernels walk: the threaded lockstep program with scalar-loaded steps wherever the launch has one
+// (kMode == kModeLinear: trace_linear with the world ray in registers, one instantiation per entry of
+// kVariants, no hit table and no kept model-space ray), else the stack traversal over the node array in global
+// memory (kModeStackGlobal, every feature compiled in, as the feature pass). The interval is (0.001, the ray's
+// tmax) (the trace functions' kTmax). A ConstantMedium on the way draws from the path stream (seed, pixel
+// 0xFFFFFFF0, frame 0) from its start, the same for every ray (the stream oracle_scene_hit opens; the seed is
+// the launch's, in the argument segment: RenderParams first). A ray that is not valid (query.h QueryRayValid) is
+// masked off before the trace, as the render kernel masks lanes at depth 0, and answers -1, 0, ... Two
+// template parameters and no bool: the mangled names share no tag with render_kernel's.
+template <uint32_t F, int kMode>
+__global__ __launch_bounds__(kBlock) void query_kernel(const RenderParams P, const float4* __restrict__ rays,
+                                                       float4* __restrict__ out, uint32_t n) {
+  static_assert(kMode == kModeLinear || kMode == kModeStackGlobal, "threaded program or global-memory stack walk");
+  const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  float r[kQueryRayFloats] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool valid = false;
+  if (i < n) {
+    const float4 a = rays[2ull * i], b = rays[2ull * i + 1ull];
+    r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w;
+    r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
+    valid = QueryRayValid(r);
+  }
+  const f3 ro = mk(r[kQrOx], r[kQrOy], r[kQrOz]), rd = mk(r[kQrDx], r[kQrDy], r[kQrDz]);
+  const float time = r[kQrTime];
+  // the wave's box-boundary candidate planes (boundary_aa_pair), as the render kernel's kCandP
+  lds_u32* cand = nullptr;
+  if constexpr (BoxPair<F, kMode>()) {
+    __shared__ uint32_t s_cand[(kBlock / 64) * kBoundaryAAMax * 64];
+    cand = (lds_u32*)(s_cand) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kBoundaryAAMax * 64u) +
+           (uint32_t)__lane_id();
+  }
+  bool hit = false;
+  f3 hp = mk(0.0f, 0.0f, 0.0f), hn = mk(0.0f, 0.0f, 0.0f);
+  bool front = false;
+  uint32_t mat = 0;
+  HitRef h{0.0f, kRefNone, kRefNone};
+  // (a wave without a valid ray skips the trace by a scalar branch: no step is loaded for it)
+  if (__ballot(valid) != 0ull) {
+    if (valid) {
+      PathT<false> path;
+      path.rb = nullptr;
+      path.pix = 0xFFFFFFF0u;
+      path.sij = 0;
+      path.r0 = path.r1 = path.r2 = path.r3 = 0;
+      path.start(0);
+      Counters cnt = {};
+      if constexpr (kMode == kModeLinear) {
+        hit = trace_linear<F, false, false, true>(P, RegRay{ro, rd}, time, path, h, cand, nullptr, cnt, false, nullptr,
+                                                  r[kQrTmax]);
+        if (hit)
+          resolve_hit<F, kModeLinear, true>(Nodes<kModeLinear>{reinterpret_cast<const float4*>(P.lind)}, h, ro, rd, time,
+                                            hp, hn, front, mat);
+      } else {
+        uint32_t* stk = reinterpret_cast<uint32_t*>(s_dyn) + threadIdx.x;
+        const Nodes<kModeStackGlobal> N{reinterpret_cast<const float4*>(P.nodes), 0u};
+        bool overflow = false;  // (the launcher refuses a scene whose stack is deeper than the kernel's)
+        hit = trace_stack<F, kModeStackGlobal, false, true>(P, N, ro, rd, time, path, h, stk, cnt, overflow, r[kQrTmax]);
+        if (hit) resolve_hit<F, kModeStackGlobal, true>(N, h, ro, rd, time, hp, hn, front, mat);
+      }
+    }
+  }
+  if (i >= n) return;
+  float4* o = out + 4ull * i;
+  if (!hit) {
+    const float flag = valid ? 0.0f : -1.0f;
+    const float bx = valid ? P.background[0] : 0.0f, by = valid ? P.background[1] : 0.0f,
+                bz = valid ? P.background[2] : 0.0f;
+    o[0] = make_float4(flag, 0.0f, 0.0f, 0.0f);
+    o[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    o[2] = make_float4(0.0f, 0.0f, bx, by);
+    o[3] = make_float4(bz, 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  // albedo and dist by the feature pass's rule, each operation rounded on its own in its order
+  const ShadeArgs S{reinterpret_cast<const float4*>(P.materials), reinterpret_cast<const float4*>(P.textures),
+                    reinterpret_cast<const float4*>(P.perlin_vec), P.perlin_perm};
+  const float4 m0 = S.materials[2 * mat], m1 = S.materials[2 * mat + 1];
+  const uint32_t type = bits(m0.x);
+  f3 alb = mk(m0.y, m0.z, m0.w);
+  if (type == kMatDielectric) alb = mk(1.0f, 1.0f, 1.0f);
+  if (type == kMatTexture || type == kMatDiffuseLight || type == kMatIsotropic) alb = tex_value<F>(S, bits(m1.z), hp);
+  const f3 dp = hp - ro;
+  const float dist = sqrtf(dot(dp, dp));
+  o[0] = make_float4(1.0f, h.t, hp.x, hp.y);
+  o[1] = make_float4(hp.z, hn.x, hn.y, hn.z);
+  o[2] = make_float4(front ? 1.0f : 0.0f, (float)mat, alb.x, alb.y);
+  o[3] = make_float4(alb.z, dist, 0.0f, 0.0f);
+}
+
+using QueryFn = void (*)(RenderParams, const float4*, float4*, uint32_t);
+// threaded: the instantiation of kVariants[v]; else the one stack instantiation
+QueryFn QueryKernel(int v, bool threaded) {
+  if (!threaded) return &query_kernel<kFeatAll, kModeStackGlobal>;
+  switch (v) {
+    case 0: return &query_kernel<kVariants[0], kModeLinear>;
+    case 1: return &query_kernel<kVariants[1], kModeLinear>;
+    case 2: return &query_kernel<kVariants[2], kModeLinear>;
+    case 3: return &query_kernel<kVariants[3], kModeLinear>;
+    case 4: return &query_kernel<kVariants[4], kModeLinear>;
+  }
+  return nullptr;
+}
+
+// ------------------------------------------------------------------------------------------
 // Self-tests of the kernel's exact shortcuts on random inputs (rt2_selftest):
 //   which 0: div_by_inv(a, b, fl(1/b)) == a / b for |b| > 1e-8, |a / b| >= 1e-3 (accepted quad t)
 //   which 3: the same for any quotient with 2^-100 <= |a| < 2^21 (medium box boundaries, any t)
@@ -3469,6 +3581,22 @@ hipError_t LaunchFeatures(const RenderParams& p, float* out, hipStream_t stream)
   if (npix == 0) return hipSuccess;
   hipLaunchKernelGGL(dev::features_kernel, dim3((npix + (uint32_t)dev::kBlock - 1u) / (uint32_t)dev::kBlock), dim3(dev::kBlock),
                      (size_t)p.stack_depth * dev::kBlock * 4, stream, p, reinterpret_cast<float4*>(out));
+  return hipGetLastError();
+}
+
+// Dynamic LDS of a query launch: the stack walk's per-lane stacks; the threaded kernels' planes are static.
+size_t QueryLdsBytes(const RenderParams& p) { return p.lin_len ? 0 : (size_t)p.stack_depth * dev::kBlock * 4; }
+
+// The query kernel over n rays (8 floats each) into out (16 floats each), both on the stream's device. p: the
+// scene tables, root, background, seed and stack_depth of BaseParams and, for the threaded walk, lin_wide, lind
+// and lin_len (0: the stack walk).
+hipError_t LaunchQuery(const RenderParams& p, int variant, const float* rays, float* out, uint32_t n,
+                       hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  dev::QueryFn fn = dev::QueryKernel(variant, p.lin_len != 0);
+  if (!fn || n > 0x7FFFFFFFu || (!p.lin_len && p.stack_depth > kTraversalStack)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3(QueryGrid(n, (uint32_t)dev::kBlock)), dim3(dev::kBlock), QueryLdsBytes(p), stream, p,
+                     reinterpret_cast<const float4*>(rays), reinterpret_cast<float4*>(out), n);
   return hipGetLastError();
 }
 

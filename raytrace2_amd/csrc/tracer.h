@@ -248,6 +248,15 @@ struct rt2_tracer {
   rt2::detail::Recon recon;
   double features_ms = -1.0, denoise_ms = -1.0, temporal_ms = -1.0;
   int n_materials = 0;  // materials in d_materials
+  // ray queries (rt2.h "Ray queries", capi_query.cpp): the host entry's two device buffers (rays in, records out),
+  // grown on demand and kept; the events around the device entry's kernel (created at its first call), whether
+  // that call's time is still to be read from them (rt2_tracer_intersect_time polls, never waits), and the GPU
+  // time of the last call's kernels (-1: none)
+  rt2::DeviceBuffer d_query_rays;
+  rt2::DeviceBuffer d_query_hits;
+  hipEvent_t query_e0 = nullptr, query_e1 = nullptr;
+  bool query_pending = false;
+  double query_ms = -1.0;
   rt2::DeviceBuffer d_work;  // one work counter per launch slot (words 0 and 16)
   rt2::DeviceBuffer d_stats;
   bool stats_on = false;

@@ -313,6 +313,14 @@ def _present_params(params: dict):
     return ctypes.byref(p)
 
 
+def ray_valid(rays) -> np.ndarray:
+    """rt2_query_ray_valid for each of rays (n, 8) float32 (one ray: (8,)): whether intersect() traces it (all
+    words finite, 0.001 < tmax, 0 <= time <= 1, origin within +-2^64, the direction's largest component within
+    [2^-20, 2^20]) or answers -1. Returns (n,) bool."""
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    return np.array([bool(lib.rt2_query_ray_valid(_fp(r[i:i + 1]))) for i in range(len(r))], bool)
+
+
 def present_buffers(color, device: int = 0) -> np.ndarray:
     """rt2_present_buffers: the tone map of present() over a caller image, color (H, W, 3) float32, on `device`.
     Returns (H, W, 4) uint8."""
@@ -353,6 +361,7 @@ class RayTracer:
         self.device = self.devices[0]
         self._max_depth = 50
         self._moments = False
+        self._seed = DEFAULT_SEED  # the tracer's seed (rt2_tracer_set_seed), intersect()'s default
         self.camera: Optional[Camera] = None
 
     def close(self):
@@ -468,6 +477,7 @@ class RayTracer:
 
     def set_seed(self, seed: int) -> None:
         check(lib.rt2_tracer_set_seed(self._h, int(seed)))
+        self._seed = int(seed)
 
     def set_partition(self, band_h: int, rank: int, world: int) -> None:
         check(lib.rt2_tracer_set_partition(self._h, int(band_h), int(rank), int(world)))
@@ -613,6 +623,43 @@ class RayTracer:
         f, d = ctypes.c_double(-1.0), ctypes.c_double(-1.0)
         check(lib.rt2_tracer_denoise_times(self._h, ctypes.byref(f), ctypes.byref(d)))
         return {"features_ms": f.value, "denoise_ms": d.value}
+
+    # -- ray queries (rt2.h "Ray queries") -------------------------------------------------------
+    def intersect(self, rays, seed: Optional[int] = None):
+        """The scene's closest hit for rays of the caller: rays (n, 8) float32, ox oy oz tmax dx dy dz time ->
+        (n, 16) float32 in the feature record's layout, slot 0 = 1 hit, 0 miss, -1 not traced (ray_valid). seed
+        keys a ConstantMedium's draws (default: the tracer's seed). A numpy array goes through the host entry
+        (queued frames are launched first) and a numpy array comes back; a CUDA torch tensor on the tracer's
+        device goes through the device entry into a new tensor, complete on return."""
+        seed = self._seed if seed is None else int(seed)
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+            import torch
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise ValueError(f"intersect: need a tensor on cuda:{self.device}")
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("intersect: need rays (n, 8) float32")
+            rays = rays.contiguous()
+            out = torch.empty((rays.shape[0], 16), dtype=torch.float32, device=rays.device)
+            if rays.shape[0] == 0:
+                return out
+            torch.cuda.current_stream(rays.device).synchronize()  # the rays are written; `out` is allocated
+            check(lib.rt2_tracer_intersect_device(self._h, rays.shape[0], ctypes.c_void_p(rays.data_ptr()), seed,
+                                                  ctypes.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("intersect: need rays (n, 8) float32")
+        out = np.zeros((rays.shape[0], 16), np.float32)
+        if rays.shape[0]:
+            check(lib.rt2_tracer_intersect(self._h, rays.shape[0], _fp(rays), seed, _fp(out)))
+        return out
+
+    def intersect_time(self) -> float:
+        """GPU ms of the last intersect's kernels (-1: not finished yet, or none). Never waits."""
+        ms = ctypes.c_double(-1.0)
+        check(lib.rt2_tracer_intersect_time(self._h, ctypes.byref(ms)))
+        return ms.value
 
     # -- temporal reuse (rt2.h "Temporal reuse") ------------------------------------------------
     def temporal_resolve(self, denoise=False, variance: bool = False, length: bool = False, **params):
