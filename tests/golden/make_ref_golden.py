@@ -14,6 +14,10 @@ tests/test_reference_build.py regenerates them from the live library and compare
                       texture on an emitter the kernel's path stream and the reference's agree draw for draw
                       up to the first hit and the result is emission or background, so the kernel must equal
                       the reference's own Update.
+  <scene>_edges.npy   float32 (n, 18), n <= 400: rays of the scene's edge batch (tests/edge_rays.py: every class,
+                      pairs kept together), each as its 8 ray words followed by ref_hit's 10 floats on it
+                      (t in (0.001, the ray's tmax), the ray's time); a miss has its record zeroed. One for every
+                      scene without a medium and one for each node order of the authored scene `ties`.
 
 Run from anywhere: python tests/golden/make_ref_golden.py"""
 import io
@@ -103,9 +107,32 @@ def depth1_fixture(name):
     return acc
 
 
+def edge_scenes():
+    import edge_rays as E
+    return [n for n, _ in hit_scenes()] + list(E.TIES)
+
+
+def edge_fixture(name):
+    import edge_rays as E
+    from oracle.ref import RefScene
+    b, rows = E.batch(name), E.fixture_rows(name)
+    r = RefScene(E.scene_file(name), SEED)
+    out = np.zeros((len(rows), 18), np.float32)
+    for k, i in enumerate(rows):
+        ray = b.rays[i]
+        rec = r.hit(ray[0:3], ray[4:7], float(ray[7]), 0.001, float(ray[3]), seed=SEED)[:10]
+        out[k, :8] = ray
+        if rec[0] == 1:
+            out[k, 8:] = rec
+    assert (out[:, 8] == 1).any() and (out[:, 8] == 0).any(), name
+    return out
+
+
 def fixtures():
     """{file name: array} of every fixture, from the live library."""
     out = {}
+    for name in edge_scenes():
+        out[name + "_edges.npy"] = edge_fixture(name)
     for name, spp in hit_scenes():
         out[name + "_hits.npy"] = hit_fixture(name, spp)
     d1 = depth1_scenes()

@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+import edge_rays as E
 from conftest import ROOT, scene_path
 from denoise_ref import feature_rays
 from helpers import SEED
@@ -224,6 +225,33 @@ def test_hits(name):
     _, kinds = _kinds_by_material(name)
     seen = _kinds_hit(name, a[hit])
     assert seen >= kinds, f"no hit on {kinds - seen}"
+
+
+# ---- hits at the decision boundaries ----------------------------------------------------------------------
+@pytest.mark.parametrize("name", NAMES + list(E.TIES))
+def test_edge_batches(name):
+    """ref_hit against oracle.hit on the scene's edge batch (tests/edge_rays.py: pairs an ulp apart across a
+    silhouette and across either end of the interval, rays leaving a surface, rays aimed at corners and edges;
+    the authored scene's ties, tangents and in-plane rays in both node orders), the ray's own tmax and time: the
+    flag agrees on every ray and all 10 floats are bit-equal where hit. Media are keyed by ray as in test_hits.
+    Without a medium CTL_REF_MATH changes no hit, so these are also the answers the GPU tests compare with."""
+    batch = E.batch(name)  # built under the default controls, as the GPU tests build it
+    path = E.scene_file(name)
+    with O.controls(O.CTL_REF_MATH):
+        o = O.OracleScene(path, SEED)
+        r = R.RefScene(path, SEED)
+        args = [(q[0:3], q[4:7], float(q[7]), 0.001, float(q[3])) for q in batch.rays]
+        a = np.array([o.hit(*x, seed=HIT_KEY + i) for i, x in enumerate(args)])
+        b = np.array([r.hit(*x, seed=HIT_KEY + i) for i, x in enumerate(args)])
+    flags_differ = np.flatnonzero(a[:, 0] != b[:, 0])
+    assert len(flags_differ) == 0, f"hit flag differs on rays {flags_differ[:5]} ({batch.cls[flags_differ[:5]]})"
+    hit = a[:, 0] == 1
+    words = _bits(a[hit]) != _bits(b[hit][:, :10])
+    assert not words.any(), f"{np.count_nonzero(words)} words differ, first ray {np.flatnonzero(hit)[np.argwhere(words)[0][0]]}"
+    assert np.count_nonzero(hit) >= 0.1 * len(a) and np.count_nonzero(~hit) >= 0.1 * len(a)
+    if name not in E.MEDIA:
+        mine = E.answers(name)
+        assert np.array_equal(mine[:, 0], a[:, 0]) and _same(mine[hit], a[hit])
 
 
 # ---- whole paths ------------------------------------------------------------------------------------------
