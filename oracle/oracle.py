@@ -171,6 +171,8 @@ CTL_SINGLE_LEAF = 2  # span-1 BVH leaves tested once (BVH.cpp:18-20,50-55 quirk 
 CTL_INF = 4          # kInfinity = +inf instead of FLT_MAX (Defs.hpp:17)
 # ... and one that RESTORES the reference's sampling and libm calls where the restatement deviates
 CTL_REF_MATH = 8     # rejection RandInUnitSphere/Disk, std::log, std::sin(float), std::pow(double, 5)
+# ... and one that removes a pruning step the images depend on (a transformed child's model-space t)
+CTL_NO_SLAB = 16     # BVHNode::Hit skips its slab test and visits both children (BVH.cpp:51)
 
 
 class controls:

@@ -65,7 +65,12 @@ using real = float;
 //      std::log(float) in ConstantMedium (ConstantMedium.cpp:42), std::sin(float) in the marble
 //      texture (Texture.cpp:16), glm::pow(1 - cos, 5) = std::pow(double, int) in Schlick
 //      (Material.cpp:24; glm's scalar pow is std::pow, and (float, int) promotes to double)
-enum : int { kCtlWorldT = 1, kCtlSingleLeaf = 2, kCtlInf = 4, kCtlRefMath = 8 };
+// and one bit that removes no quirk but a pruning step, to measure what the images can see of it:
+//   16: BVHNode::Hit skips its slab test (BVH.cpp:51) and visits both children: all leaves in pre-order
+//       with a running tmax, the product's flat walk without its certificate (DESIGN.md §4 "Flat walk of
+//       small BVHs"). The slab test is no pure optimisation: a transformed child reports model-space t, so
+//       a hit's tmax can cull the subtree that holds a nearer surface. The bvh counter still counts.
+enum : int { kCtlWorldT = 1, kCtlSingleLeaf = 2, kCtlInf = 4, kCtlRefMath = 8, kCtlNoSlab = 16 };
 static int g_controls = 0;
 #define kInfinity ((g_controls & kCtlInf) ? (real)INFINITY : (real)FLT_MAX)  // Defs.hpp:17
 
@@ -701,7 +706,7 @@ struct BVHNode : Hittable {
   }
   bool Hit(Ctx& c, const Ray& r, Interval ray_t, HitRecord& rec) const override {
     c.cnt->bvh++;
-    if (!aabb.Hit(r, ray_t)) return false;
+    if (!(g_controls & kCtlNoSlab) && !aabb.Hit(r, ray_t)) return false;
     bool hit_left = left->Hit(c, r, ray_t, rec);
     if ((g_controls & kCtlSingleLeaf) && left == right) return hit_left;
     bool hit_right = right->Hit(c, r, Interval(ray_t.min, hit_left ? rec.t : ray_t.max), rec);
