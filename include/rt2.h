@@ -656,7 +656,7 @@ RT2_API int rt2_deinterleave_adaptive_host(const float* stacks, const float* sta
                                            float* variance /* may be NULL */, uint32_t* image_counts, int width,
                                            int height, int band_h, int world);
 
-/* ---- Ray queries (DESIGN.md §6j) ----
+/* ---- Ray queries (DESIGN.md §6j, §6k) ----
  * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before.
  * The scene's closest Hit for rays the caller owns (picking, focusing, visibility between two points, feature
  * buffers for a camera of the caller's own), n rays per call, traced by the kernels' traversal: the threaded
@@ -682,8 +682,16 @@ RT2_API int rt2_deinterleave_adaptive_host(const float* stacks, const float* sta
  * intersect_device: device pointers on the tracer's device. It only enqueues on the tracer's stream and returns at
  *   once, adds nothing to rt2_stats.host_waits and is complete after rt2_tracer_synchronize or when
  *   rt2_tracer_query returns 1. It does not launch queued frames.
- * intersect_time: GPU time (HIP events) of the last call's kernels (every chunk's, not the copies), in ms; -1
- *   while that call has not finished, or when there was none. It polls the events and never waits.
+ * occluded, occluded_device: "is anything in the way?" for the same ray records under the same validity rule,
+ *   interval (0.001, tmax) and medium stream: one int8_t per ray, 1 occluded, 0 clear, -1 not traced, which is slot
+ *   0 of the record intersect writes for that ray and seed, for every valid ray, seed and traversal (the walk is
+ *   intersect's up to its first accepted primitive and ends there; nothing is resolved or shaded). The host entry
+ *   behaves as intersect (queued frames first, RT2_QUERY_CHUNK, the same two device buffers, one wait) and moves 32
+ *   bytes in and 1 byte out per ray; the device entry only enqueues, as intersect_device, and writes exactly n
+ *   bytes. Refusals as intersect's.
+ * intersect_time: GPU time (HIP events) of the last query's kernels, of either kind: the last intersect,
+ *   intersect_device, occluded or occluded_device call (every chunk's, not the copies), in ms; -1 while that
+ *   call has not finished, or when there was none. It polls the events and never waits.
  * A call changes no render state: accumulation, moments, counts, FrameIdx(), feature cache and history are
  *   unchanged. It works before on_resize, and on a set_partition or joined tracer (the scene is whole on every
  *   rank and no image is involved). n == 0 is RT2_OK and does nothing.
@@ -692,6 +700,8 @@ RT2_API int rt2_deinterleave_adaptive_host(const float* stacks, const float* sta
 RT2_API int rt2_query_ray_valid(const float* ray8);
 RT2_API int rt2_tracer_intersect(rt2_tracer* tr, int64_t n, const float* rays, uint64_t seed, float* out);
 RT2_API int rt2_tracer_intersect_device(rt2_tracer* tr, int64_t n, const float* d_rays, uint64_t seed, float* d_out);
+RT2_API int rt2_tracer_occluded(rt2_tracer* tr, int64_t n, const float* rays, uint64_t seed, int8_t* out);
+RT2_API int rt2_tracer_occluded_device(rt2_tracer* tr, int64_t n, const float* d_rays, uint64_t seed, int8_t* d_out);
 RT2_API int rt2_tracer_intersect_time(rt2_tracer* tr, double* ms);
 
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n

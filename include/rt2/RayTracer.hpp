@@ -441,6 +441,14 @@ class RayTracer {
   void IntersectDevice(const float* d_rays, int64_t n, float* d_out, uint64_t seed = kDefaultSeed) {
     Check(rt2_tracer_intersect_device(t_.get(), n, d_rays, seed, d_out));
   }
+  // Occluded / OccludedDevice: one int8_t per ray, 1 occluded, 0 clear, -1 not traced: slot 0 of Intersect's
+  // record for the same ray and seed, from a walk that ends at its first hit. Host and device entry as above.
+  void Occluded(const float* rays, int64_t n, int8_t* out, uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_occluded(t_.get(), n, rays, seed, out));
+  }
+  void OccludedDevice(const float* d_rays, int64_t n, int8_t* d_out, uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_occluded_device(t_.get(), n, d_rays, seed, d_out));
+  }
   [[nodiscard]] double IntersectTime() {
     double ms = -1.0;
     Check(rt2_tracer_intersect_time(t_.get(), &ms));

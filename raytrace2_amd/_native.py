@@ -272,6 +272,8 @@ def _load():
         "rt2_tracer_intersect": (i32, [vp, i64, fp, u64, fp]),
         "rt2_tracer_intersect_device": (i32, [vp, i64, vp, u64, vp]),
         "rt2_tracer_intersect_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
+        "rt2_tracer_occluded": (i32, [vp, i64, fp, u64, ctypes.POINTER(ctypes.c_int8)]),
+        "rt2_tracer_occluded_device": (i32, [vp, i64, vp, u64, vp]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

@@ -1,5 +1,5 @@
 // capi_query.cpp — the ray queries of include/rt2.h ("Ray queries"): the scene's closest Hit for rays the caller
-// owns, over render.hip's query kernel. Planned by launch_plan.h PlanQuery; the layouts and the validity rule are
+// owns, over render.hip's query kernel, and whether anything is in their way, over its occlusion kernel. Planned by launch_plan.h PlanQuery; the layouts and the validity rule are
 // query.h's.
 #include <hip/hip_runtime_api.h>
 
@@ -62,20 +62,33 @@ int QueryParams(const rt2_tracer* t, uint64_t seed, uint32_t n, const char* call
   return RT2_OK;
 }
 
-}  // namespace
+// The two kinds of query: what one writes per ray and the launcher of its kernel.
+struct QueryKind {
+  size_t out_bytes;  // per ray
+  hipError_t (*launch)(const RenderParams& p, int variant, const float* rays, void* out, uint32_t n, hipStream_t stream);
+};
+const QueryKind kClosestHit = {kQueryHitFloats * sizeof(float),
+                               [](const RenderParams& p, int variant, const float* rays, void* out, uint32_t n,
+                                  hipStream_t stream) {
+                                 return LaunchQuery(p, variant, rays, static_cast<float*>(out), n, stream);
+                               }};
+// (one byte per ray instead of a record)
+const QueryKind kOcclusion = {sizeof(int8_t), [](const RenderParams& p, int variant, const float* rays, void* out,
+                                                 uint32_t n, hipStream_t stream) {
+                                return LaunchOcclusion(p, variant, rays, static_cast<int8_t*>(out), n, stream);
+                              }};
 
-extern "C" {
-
-int rt2_query_ray_valid(const float* ray8) { return ray8 && QueryRayValid(ray8) ? 1 : 0; }
-
-int rt2_tracer_intersect(rt2_tracer* t, int64_t n, const float* rays, uint64_t seed, float* out) {
-  int rc = CheckCall(t, n, rays, out, "intersect");
+// The host entry of either kind: queued frames first, then chunks through the tracer's two device buffers (sized for
+// the closest hit's records, which hold an occlusion chunk's bytes 64 times over), one event pair per chunk, one wait.
+int HostQuery(rt2_tracer* t, int64_t n, const float* rays, uint64_t seed, void* out, const QueryKind& kind,
+              const char* call) {
+  int rc = CheckCall(t, n, rays, out, call);
   if (rc != RT2_OK) return rc;
   if (n == 0) return RT2_OK;
   const int64_t chunk = std::min(QueryChunk(), (n + 63) / 64 * 64);
   RenderParams p;
   QueryPlan q;
-  if ((rc = QueryParams(t, seed, (uint32_t)std::min(chunk, n), "intersect", &p, &q)) != RT2_OK) return rc;
+  if ((rc = QueryParams(t, seed, (uint32_t)std::min(chunk, n), call, &p, &q)) != RT2_OK) return rc;
   if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
   HIP_TRY(hipSetDevice(t->device));
   const size_t ray_bytes = (size_t)chunk * kQueryRayFloats * sizeof(float);
@@ -105,17 +118,17 @@ int rt2_tracer_intersect(rt2_tracer* t, int64_t n, const float* rays, uint64_t s
     e = hipMemcpyAsync(t->d_query_rays.get<float>(), rays + (size_t)at * kQueryRayFloats,
                        (size_t)m * kQueryRayFloats * sizeof(float), hipMemcpyHostToDevice, t->stream);
     if (e == hipSuccess) e = hipEventRecord(e0, t->stream);
-    if (e == hipSuccess) e = LaunchQuery(p, q.variant, t->d_query_rays.get<float>(), t->d_query_hits.get<float>(), m, t->stream);
+    if (e == hipSuccess) e = kind.launch(p, q.variant, t->d_query_rays.get<float>(), t->d_query_hits.get<void>(), m, t->stream);
     if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
     if (e == hipSuccess)
-      e = hipMemcpyAsync(out + (size_t)at * kQueryHitFloats, t->d_query_hits.get<float>(),
-                         (size_t)m * kQueryHitFloats * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+      e = hipMemcpyAsync(static_cast<char*>(out) + (size_t)at * kind.out_bytes, t->d_query_hits.get<void>(),
+                         (size_t)m * kind.out_bytes, hipMemcpyDeviceToHost, t->stream);
     // (a pageable host buffer makes each copy wait for its own completion; the buffers are reused chunk after
     // chunk in stream order either way)
   }
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   t->host_waits++;
-  if (e != hipSuccess) return HipFail(e, "intersect");
+  if (e != hipSuccess) return HipFail(e, call);
   double ms = 0.0;
   for (size_t k = 0; k + 1 < ev.size(); k += 2) {
     float f = 0.0f;
@@ -130,23 +143,47 @@ int rt2_tracer_intersect(rt2_tracer* t, int64_t n, const float* rays, uint64_t s
   return RT2_OK;
 }
 
-int rt2_tracer_intersect_device(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, float* d_out) {
-  int rc = CheckCall(t, n, d_rays, d_out, "intersect_device");
+// The device entry of either kind: two events around one launch, no wait.
+int DeviceQuery(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, void* d_out, const QueryKind& kind,
+                const char* call) {
+  int rc = CheckCall(t, n, d_rays, d_out, call);
   if (rc != RT2_OK) return rc;
   if (n == 0) return RT2_OK;
   RenderParams p;
   QueryPlan q;
-  if ((rc = QueryParams(t, seed, (uint32_t)n, "intersect_device", &p, &q)) != RT2_OK) return rc;
+  if ((rc = QueryParams(t, seed, (uint32_t)n, call, &p, &q)) != RT2_OK) return rc;
   HIP_TRY(hipSetDevice(t->device));
   if (!t->query_e0 && hipEventCreate(&t->query_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
   if (!t->query_e1 && hipEventCreate(&t->query_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
   t->query_pending = false;
   t->query_ms = -1.0;
   HIP_TRY(hipEventRecord(t->query_e0, t->stream));
-  HIP_TRY(LaunchQuery(p, q.variant, d_rays, d_out, (uint32_t)n, t->stream));
+  HIP_TRY(kind.launch(p, q.variant, d_rays, d_out, (uint32_t)n, t->stream));
   HIP_TRY(hipEventRecord(t->query_e1, t->stream));
   t->query_pending = true;
   return RT2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt2_query_ray_valid(const float* ray8) { return ray8 && QueryRayValid(ray8) ? 1 : 0; }
+
+int rt2_tracer_intersect(rt2_tracer* t, int64_t n, const float* rays, uint64_t seed, float* out) {
+  return HostQuery(t, n, rays, seed, out, kClosestHit, "intersect");
+}
+
+int rt2_tracer_intersect_device(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, float* d_out) {
+  return DeviceQuery(t, n, d_rays, seed, d_out, kClosestHit, "intersect_device");
+}
+
+int rt2_tracer_occluded(rt2_tracer* t, int64_t n, const float* rays, uint64_t seed, int8_t* out) {
+  return HostQuery(t, n, rays, seed, out, kOcclusion, "occluded");
+}
+
+int rt2_tracer_occluded_device(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, int8_t* d_out) {
+  return DeviceQuery(t, n, d_rays, seed, d_out, kOcclusion, "occluded_device");
 }
 
 int rt2_tracer_intersect_time(rt2_tracer* t, double* ms) {

@@ -25,6 +25,8 @@ hipError_t LaunchAccumulate(const float* samples, float* accum, float* moment2, 
 hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsigned long long* d_out, hipStream_t stream);
 hipError_t LaunchFeatures(const RenderParams& p, float* out, hipStream_t stream);
 hipError_t LaunchQuery(const RenderParams& p, int variant, const float* rays, float* out, uint32_t n, hipStream_t stream);
+hipError_t LaunchOcclusion(const RenderParams& p, int variant, const float* rays, int8_t* out, uint32_t n,
+                           hipStream_t stream);
 size_t QueryLdsBytes(const RenderParams& p);
 int RenderMode(const RenderParams& p);
 int RenderBlockSize();

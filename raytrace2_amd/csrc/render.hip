@@ -1405,7 +1405,9 @@ struct HitRef {
 // Stack traversal (any scene): each lane walks its own steps — LDS stack pops, or the next child of
 // a leaf list through a per-lane cursor — one step per loop trip.
 // kTmax (the query kernel): the interval ends at the caller's tmax0 instead of FLT_MAX.
-template <uint32_t F, int kMode, bool kStats, bool kTmax = false, class G>
+// kAny (the occlusion kernel): the walk ends with the step that accepted a hit (the walk never gives a hit up
+// again, so the returned flag is the complete walk's); h is not the closest hit then.
+template <uint32_t F, int kMode, bool kStats, bool kTmax = false, bool kAny = false, class G>
 __device__ __forceinline__ bool trace_stack(const RenderParams& P, const Nodes<kMode>& N, f3 wo, f3 wd, float time,
                                             G& path, HitRef& h, uint32_t* stk, Counters& cnt, bool& overflow,
                                             float tmax0 = FLT_MAX) {
@@ -1537,6 +1539,9 @@ __device__ __forceinline__ bool trace_stack(const RenderParams& P, const Nodes<k
         acc_best = off;
       }
     }
+    if constexpr (kAny) {
+      if (any) break;
+    }
     // next step: the leaf-list cursor first, then the stack
     if (lrem != 0u) {
       cur = N.word(0, lword++);
@@ -1587,7 +1592,11 @@ constexpr bool BoxOn() {
 // is its transform's and T = the lane's tmax at that transform's entry (the entry rule, evaluated lazily:
 // only the winner's transform's verdict is ever read); for a winner in world space T = its t (the end rule).
 // kTmax (the query kernel): the interval ends at the caller's tmax0 (0.001 < tmax0 <= FLT_MAX) instead of FLT_MAX.
-template <uint32_t F, bool kStats, bool kFlat = false, bool kTmax = false, class W, class G>
+// kAny (the occlusion kernel): a lane whose step accepted a hit is done, its `next` is the program's end (the
+// walk never gives a hit up again, so the returned flag is the complete walk's); the accelerated list's lane-by-lane
+// walk leaves at its first accept (a quad run's records come by scalar loads, so it runs to its end for the
+// wave's other lanes anyway). h is not the closest hit then (h.t, h.prim and h.xf are not to be read).
+template <uint32_t F, bool kStats, bool kFlat = false, bool kTmax = false, bool kAny = false, class W, class G>
 __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wray, float time, G& path, HitRef& h,
                                              lds_u32* cand, lds_u32* xray, Counters& cnt, bool tab = false,
                                              bool* uncert = nullptr, float tmax0 = FLT_MAX) {
@@ -1605,6 +1614,7 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
   bool fin = finite3(inv);  // inv finite: the NaN-free slab test applies
   const bool wfin = fin;
   const float tmin = 0.001f;
+  static_assert(!(kAny && kFlat), "the early exit is the BVH program's walk");
   float tmax = kTmax ? tmax0 : FLT_MAX;
   uint32_t prim = kRefNone;  // closest primitive so far (h.xf: its transform, quads: from the record)
   uint32_t cur_xf = kRefNone;
@@ -1964,6 +1974,7 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
               prim = make_ref(kSphere, e0.z);
               h.xf = cur_xf;
               acc_best = e0.w;
+              if constexpr (kAny) break;
             }
             j++;
           }
@@ -1991,6 +2002,9 @@ __device__ __forceinline__ bool trace_linear(const RenderParams& P, const W& wra
         prim = make_ref(kMedium, off);
         h.xf = cur_xf;
       }
+    }
+    if constexpr (kAny) {
+      if (prim != kRefNone) next = P.lin_len;  // done: the wave's walk ends when every lane is
     }
     }  // next == at
     i = kFlat ? next : wave_min_next(next);
@@ -3299,6 +3313,74 @@ QueryFn QueryKernel(int v, bool threaded) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Occlusion queries (rt2.h "Ray queries"): whether anything lies in (0.001, tmax) along n rays of
+// the caller, one ray per lane, one byte per ray: 1 occluded, 0 clear, -1 not traced, slot 0 of the record the
+// query kernel above writes for the same ray and seed. The same ray load, masking, whole-wave skip, medium
+// stream and choice of walk as there; the trace ends at its first accept (the trace functions' kAny), and
+// nothing is resolved or shaded: no hit point, no normal, no material. Lanes past n store nothing.
+template <uint32_t F, int kMode>
+__global__ __launch_bounds__(kBlock) void occlusion_kernel(const RenderParams P, const float4* __restrict__ rays,
+                                                           int8_t* __restrict__ out, uint32_t n) {
+  static_assert(kMode == kModeLinear || kMode == kModeStackGlobal, "threaded program or global-memory stack walk");
+  const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  float r[kQueryRayFloats] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool valid = false;
+  if (i < n) {
+    const float4 a = rays[2ull * i], b = rays[2ull * i + 1ull];
+    r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w;
+    r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
+    valid = QueryRayValid(r);
+  }
+  const f3 ro = mk(r[kQrOx], r[kQrOy], r[kQrOz]), rd = mk(r[kQrDx], r[kQrDy], r[kQrDz]);
+  const float time = r[kQrTime];
+  lds_u32* cand = nullptr;  // the wave's box-boundary candidate planes, as the query kernel's
+  if constexpr (BoxPair<F, kMode>()) {
+    __shared__ uint32_t s_cand[(kBlock / 64) * kBoundaryAAMax * 64];
+    cand = (lds_u32*)(s_cand) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kBoundaryAAMax * 64u) +
+           (uint32_t)__lane_id();
+  }
+  bool hit = false;
+  if (__ballot(valid) != 0ull) {
+    if (valid) {
+      PathT<false> path;
+      path.rb = nullptr;
+      path.pix = 0xFFFFFFF0u;
+      path.sij = 0;
+      path.r0 = path.r1 = path.r2 = path.r3 = 0;
+      path.start(0);
+      Counters cnt = {};
+      HitRef h{0.0f, kRefNone, kRefNone};  // (not read: the trace's flag is the answer)
+      if constexpr (kMode == kModeLinear) {
+        hit = trace_linear<F, false, false, true, true>(P, RegRay{ro, rd}, time, path, h, cand, nullptr, cnt, false,
+                                                        nullptr, r[kQrTmax]);
+      } else {
+        uint32_t* stk = reinterpret_cast<uint32_t*>(s_dyn) + threadIdx.x;
+        const Nodes<kModeStackGlobal> N{reinterpret_cast<const float4*>(P.nodes), 0u};
+        bool overflow = false;  // (the launcher refuses a scene whose stack is deeper than the kernel's)
+        hit = trace_stack<F, kModeStackGlobal, false, true, true>(P, N, ro, rd, time, path, h, stk, cnt, overflow,
+                                                                  r[kQrTmax]);
+      }
+    }
+  }
+  if (i >= n) return;
+  out[i] = valid ? (hit ? (int8_t)1 : (int8_t)0) : (int8_t)-1;
+}
+
+using OcclusionFn = void (*)(RenderParams, const float4*, int8_t*, uint32_t);
+// chosen as QueryKernel chooses
+OcclusionFn OcclusionKernel(int v, bool threaded) {
+  if (!threaded) return &occlusion_kernel<kFeatAll, kModeStackGlobal>;
+  switch (v) {
+    case 0: return &occlusion_kernel<kVariants[0], kModeLinear>;
+    case 1: return &occlusion_kernel<kVariants[1], kModeLinear>;
+    case 2: return &occlusion_kernel<kVariants[2], kModeLinear>;
+    case 3: return &occlusion_kernel<kVariants[3], kModeLinear>;
+    case 4: return &occlusion_kernel<kVariants[4], kModeLinear>;
+  }
+  return nullptr;
+}
+
+// ------------------------------------------------------------------------------------------
 // Self-tests of the kernel's exact shortcuts on random inputs (rt2_selftest):
 //   which 0: div_by_inv(a, b, fl(1/b)) == a / b for |b| > 1e-8, |a / b| >= 1e-3 (accepted quad t)
 //   which 3: the same for any quotient with 2^-100 <= |a| < 2^21 (medium box boundaries, any t)
@@ -3597,6 +3679,18 @@ hipError_t LaunchQuery(const RenderParams& p, int variant, const float* rays, fl
   if (!fn || n > 0x7FFFFFFFu || (!p.lin_len && p.stack_depth > kTraversalStack)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3(QueryGrid(n, (uint32_t)dev::kBlock)), dim3(dev::kBlock), QueryLdsBytes(p), stream, p,
                      reinterpret_cast<const float4*>(rays), reinterpret_cast<float4*>(out), n);
+  return hipGetLastError();
+}
+
+// The occlusion kernel over n rays (8 floats each) into out (one byte each, exactly n written), both on the
+// stream's device. p and the choice of walk: as LaunchQuery.
+hipError_t LaunchOcclusion(const RenderParams& p, int variant, const float* rays, int8_t* out, uint32_t n,
+                           hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  dev::OcclusionFn fn = dev::OcclusionKernel(variant, p.lin_len != 0);
+  if (!fn || n > 0x7FFFFFFFu || (!p.lin_len && p.stack_depth > kTraversalStack)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3(QueryGrid(n, (uint32_t)dev::kBlock)), dim3(dev::kBlock), QueryLdsBytes(p), stream, p,
+                     reinterpret_cast<const float4*>(rays), out, n);
   return hipGetLastError();
 }
 

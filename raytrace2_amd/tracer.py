@@ -655,8 +655,61 @@ class RayTracer:
             check(lib.rt2_tracer_intersect(self._h, rays.shape[0], _fp(rays), seed, _fp(out)))
         return out
 
+    def occluded(self, rays, seed: Optional[int] = None):
+        """Whether anything lies in (0.001, tmax) along rays of the caller: rays (n, 8) float32 as intersect's ->
+        (n,) int8, 1 occluded, 0 clear, -1 not traced (ray_valid): slot 0 of intersect's record for the same ray and
+        seed, from a walk that ends at its first hit and resolves nothing. A numpy array goes through the host
+        entry and a numpy array comes back; a CUDA torch tensor on the tracer's device goes through the device
+        entry into a new int8 tensor, complete on return."""
+        seed = self._seed if seed is None else int(seed)
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+            import torch
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise ValueError(f"occluded: need a tensor on cuda:{self.device}")
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("occluded: need rays (n, 8) float32")
+            rays = rays.contiguous()
+            out = torch.empty((rays.shape[0],), dtype=torch.int8, device=rays.device)
+            if rays.shape[0] == 0:
+                return out
+            torch.cuda.current_stream(rays.device).synchronize()  # the rays are written; `out` is allocated
+            check(lib.rt2_tracer_occluded_device(self._h, rays.shape[0], ctypes.c_void_p(rays.data_ptr()), seed,
+                                                 ctypes.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("occluded: need rays (n, 8) float32")
+        out = np.zeros((rays.shape[0],), np.int8)
+        if rays.shape[0]:
+            check(lib.rt2_tracer_occluded(self._h, rays.shape[0], _fp(rays), seed,
+                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_int8))))
+        return out
+
+    def visible(self, a, b, time: float = 0.0, seed: Optional[int] = None) -> np.ndarray:
+        """Whether the segment from a[i] to b[i] is clear, points (n, 3): (n,) int8, 1 visible, 0 blocked, -1 not
+        traced (a == b, or a segment outside ray_valid's domain). The ray is o = a, d = b - a (one float32
+        subtraction per component) over the interval (0.001, 0.999): both margins are fractions of the segment,
+        not distances, so a surface within a thousandth of the segment's length of either end point does not
+        block it. The answer is the reference's Hit on that interval, with its quirk: a transformed child compares
+        its model-space t, taken along the normalised direction, with the same 0.999, so it blocks a segment
+        only where that t is below 0.999. Where transformed geometry must block, call occluded() with a unit
+        direction and tmax = the distance, which both kinds of children read alike."""
+        a = np.asarray(a, np.float32).reshape(-1, 3)
+        b = np.asarray(b, np.float32).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError("visible: need as many points b as points a")
+        rays = np.zeros((len(a), 8), np.float32)
+        rays[:, 0:3] = a
+        rays[:, 3] = np.float32(0.999)
+        rays[:, 4:7] = b - a
+        rays[:, 7] = np.float32(time)
+        occ = self.occluded(rays, seed)
+        return np.where(occ < 0, np.int8(-1), np.int8(1) - occ).astype(np.int8)
+
     def intersect_time(self) -> float:
-        """GPU ms of the last intersect's kernels (-1: not finished yet, or none). Never waits."""
+        """GPU ms of the last query's kernels, intersect's or occluded's (-1: not finished yet, or none). Never
+        waits."""
         ms = ctypes.c_double(-1.0)
         check(lib.rt2_tracer_intersect_time(self._h, ctypes.byref(ms)))
         return ms.value

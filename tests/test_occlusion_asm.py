@@ -1,0 +1,78 @@
+"""Static checks on the occlusion kernel's generated code (hipcc cross-compiles here, no GPU): one instantiation per
+kernel variant plus the one stack walk, names that neither the query kernel's count nor the render kernels' tags
+pick up, no scratch in the Cornell instantiation, and an occupancy no lower than the query kernel's of the same
+variant. Reads the compiler's resource remarks only: names and resource numbers."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+SRC = os.path.join(ROOT, "raytrace2_amd", "csrc", "render.hip")
+# the tags by which tests/test_kernel_asm.py and the tools find render kernels in the ISA
+RENDER_TAGS = ["ILj4ELi2ELb0E", "ILj6ELi2ELb0E", "ILj815ELi2ELb0E", "ILj1073741828ELi2ELb0E", "render_kernel",
+               "features_kernel"]
+
+
+def makefile_hipflags():
+    mk = open(os.path.join(ROOT, "raytrace2_amd", "csrc", "Makefile")).read()
+    line = re.search(r"^HIPFLAGS\s*:=(.*)$", mk, re.M).group(1)
+    return [f for f in line.split() if not f.startswith("$(") and f not in ("-fPIC", "-Wall")]
+
+
+@pytest.fixture(scope="module")
+def remarks(tmp_path_factory):
+    out = tmp_path_factory.mktemp("isa") / "render.s"
+    r = subprocess.run(["/opt/rocm/bin/hipcc", *makefile_hipflags(), "--cuda-device-only", "-S", "-o", str(out), SRC,
+                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
+    return {b.split()[0]: b for b in blocks}
+
+
+def _variants():
+    """The entries of render.hip kVariants."""
+    src = open(SRC).read()
+    body = re.search(r"constexpr uint32_t kVariants\[\] = \{(.*?)\n\};", src, re.S).group(1)
+    return [l for l in body.split("\n") if l.strip().startswith("kFeat")]
+
+
+def _number(block, what):
+    return int(re.search(re.escape(what) + r": (\d+)", block).group(1))
+
+
+def test_one_instantiation_per_variant_and_one_stack_walk(remarks):
+    names = [n for n in remarks if "occlusion_kernel" in n]
+    nvar = len(_variants())
+    assert nvar == 5 and len(names) == nvar + 1, names
+    threaded = [n for n in names if re.search(r"occlusion_kernelILj\d+ELi2EE", n)]
+    stack = [n for n in names if re.search(r"occlusion_kernelILj\d+ELi0EE", n)]
+    assert len(threaded) == nvar and len(stack) == 1, names
+    assert len(set(re.search(r"ILj(\d+)E", n).group(1) for n in threaded)) == nvar
+
+
+def test_names_share_no_tag_with_the_other_kernels(remarks):
+    for n in remarks:
+        if "occlusion_kernel" in n:
+            assert "query_kernel" not in n and not any(t in n for t in RENDER_TAGS), n
+    for t in RENDER_TAGS[:4]:
+        assert len([n for n in remarks if t in n]) == 1, t
+
+
+def test_cornell_instantiation_has_no_more_scratch_than_the_query_kernel_may(remarks):
+    cornell = [b for n, b in remarks.items() if re.search(r"occlusion_kernelILj4ELi2EE", n)]
+    assert len(cornell) == 1
+    assert _number(cornell[0], "ScratchSize [bytes/lane]") <= 16
+
+
+def test_occupancy_is_not_below_the_query_kernel_s(remarks):
+    """The occlusion kernel carries less live state than the query kernel of the same variant and walk."""
+    occ = {re.search(r"occlusion_kernel(ILj\d+ELi\d)EE", n).group(1): b for n, b in remarks.items()
+           if "occlusion_kernel" in n}
+    qry = {re.search(r"query_kernel(ILj\d+ELi\d)EE", n).group(1): b for n, b in remarks.items() if "query_kernel" in n}
+    assert set(occ) == set(qry) and len(occ) == len(_variants()) + 1
+    for k in occ:
+        a, q = _number(occ[k], "Occupancy [waves/SIMD]"), _number(qry[k], "Occupancy [waves/SIMD]")
+        assert a >= q, (k, a, q)
