@@ -35,6 +35,8 @@
 
 #include <cfloat>
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 
 #include "rt2_layout.h"
 #define RT2_BOXAA_FN __device__ __forceinline__
@@ -2314,82 +2316,94 @@ __device__ __forceinline__ uint32_t local_index(const LoopArgs& A, uint32_t x, u
   return r * (uint32_t)A.width() + x;
 }
 
-// Occupancy target (waves per SIMD the register allocation must allow), chosen per variant by
-// measurement (threaded kernels): Cornell 8 (7: -3 %), Cornell volume 8 (round 3, with box boundaries
-// as one block: 7 / 8 waves 19.9 k / 20.6 k Mray/s), book 1 8, book 2 8 (6 / 7: -11 / -5 %; spills
-// VGPRs, but its scalar loads are latency bound), the book 2 / all-features stack kernels 6. Other
-// stack and the counting kernels keep the compiler's own allocation.
-template <uint32_t F, int kMode, bool kStats>
-constexpr int MinWaves() {
-  if (RT2_MIN_WAVES_PER_EU > 0) return RT2_MIN_WAVES_PER_EU;
-  constexpr uint32_t kBook2 = kFeatSphere | kFeatMedium | kFeatXform | kFeatNoise | kFeatSpecular | kFeatAccList | kFeatMotion;
-  if ((F == kFeatAll || F == kBook2) && !kStats && (kMode == kModeStackGlobal || kMode == kModeStackHybrid))
-    return RT2_MIN_WAVES_ALL;  // book 2
-  if (F == kBook2 && !kStats && kMode == kModeLinear) return RT2_MIN_WAVES_B2LIN;
-  if (kStats || kMode != kModeLinear) return 1;
-  if (F == kFeatXform) return RT2_MIN_WAVES_CORNELL;  // Cornell: 64 VGPRs at 8
-  if (F == (kFeatXform | kFeatMedium)) return RT2_MIN_WAVES_VOL;  // Cornell volume
-  if (F == kFeatAll) return 1;
-  return RT2_MIN_WAVES_BOOK1;                     // book 1
-}
+// RTNW book 2's feature word (kVariants[3]): the traits below single its kernels out by it.
+constexpr uint32_t kFeatBook2 = kFeatSphere | kFeatMedium | kFeatXform | kFeatNoise | kFeatSpecular | kFeatAccList | kFeatMotion;
 
-// Samples staged in LDS (rt2_layout.h kOctet): a lane keeps the first samples of a group of
-// consecutive frames in LDS planes and writes the group with 16-B stores when its last sample is
-// done; a chunk edge inside a group writes its samples one by one. Groups of 8 (an octet: 96 B,
-// three whole 32-B sectors; 5.25 KB of LDS per wave, so at most 7 waves per SIMD) or, for kernels
-// at 8 waves, of 4 (48 B; 2.25 KB per wave; the middle sector of an octet is written in two halves,
-// 4/3 of the sample bytes reach memory). Returns the group size, 0 = direct 12-B stores.
-// The threaded product kernels at 8 waves per SIMD keep the Philox block in LDS (PathT; 1 KB per
-// wave): four VGPRs fewer live across the loop, which removed the Cornell kernel's spills at 8
-// waves (12 VGPRs; +1 %). Kernels at 7 waves or fewer keep it in VGPRs and stage whole sample
-// octets instead.
-template <uint32_t F, int kMode, bool kStats>
-constexpr bool LdsRng() {
-  return kMode == kModeLinear && !kStats && MinWaves<F, kMode, kStats>() >= 8;
-}
-// Book 2's threaded kernel parks the path state in LDS while a ray is traced (ParkedPath): its
-// trace needs more registers than 8 waves per SIMD leave. Its samples are stored directly (12-B
-// stores: staging measured no faster for it), which leaves the LDS room for the park planes.
-template <uint32_t F, int kMode, bool kStats>
-constexpr bool Park() {
-  constexpr uint32_t kBook2 = kFeatSphere | kFeatMedium | kFeatXform | kFeatNoise | kFeatSpecular | kFeatAccList | kFeatMotion;
-  return F == kBook2 && kMode == kModeLinear && !kStats && LdsRng<F, kMode, kStats>();
-}
 // Kernels whose threaded medium step takes both box-boundary queries in one pass (boundary_aa_pair):
-// their LDS holds the candidates.
+// their LDS holds the candidates. (Of F and kMode alone: the probe kernels ask it too.)
 template <uint32_t F, int kMode>
 constexpr bool BoxPair() {
   return kMode == kModeLinear && Has<F, kFeatMedium>() && !Has<F, kFeatSphere>();
 }
 
-// Kernels with the two-block Philox ring (PathT kRing): 8 Philox planes, where the LDS room allows it (not
-// beside the Cornell volume kernel's candidate planes or book 2's park planes).
-template <uint32_t F, int kMode, bool kStats>
-constexpr bool Ring() {
-  return LdsRng<F, kMode, kStats>() && !Park<F, kMode, kStats>() && !BoxPair<F, kMode>();
-}
-// Kernels that stage the launch's hit table (rt2_layout.h HIT) in dynamic LDS and resolve hits from it
-// (resolve_hit_tab): the ring kernels with transforms, i.e. the Cornell box kernel, whose trace keeps
-// the hit's model-space ray. The Cornell volume kernel has no LDS room for it, and the sphere kernels
-// spend under 1 % of their time resolving hits. A launch without a table (RenderParams::hit_bytes 0)
-// takes the global-memory path in these kernels too.
 #ifndef RT2_HIT_TABLE_KERNEL
 #define RT2_HIT_TABLE_KERNEL 1  // 0: no kernel takes the table; 2: the stage A probe (resolve_hit_tab)
 #endif
+
+// What a render_kernel<F, kMode, kStats> is: its occupancy target, what it keeps in LDS and where. The
+// kernel reads it, and so does the host (RenderTakesHitTable).
 template <uint32_t F, int kMode, bool kStats>
-constexpr bool HitTable() {
-  return RT2_HIT_TABLE_KERNEL && Ring<F, kMode, kStats>() && Has<F, kFeatXform>() &&
-         !Has<F, kFeatSphere | kFeatMedium>();
-}
-template <uint32_t F, int kMode, bool kStats>
-constexpr uint32_t StageGroup() {
-  if (kMode != kModeLinear || kStats || Park<F, kMode, kStats>()) return 0u;
-  // the ring kernels (Cornell, book 1) store samples directly: their staging logic cost more time than
-  // the write traffic it saves (round 4, same box: C2 +0.9 %, book 1 +1 %; 12-B stores write the
-  // octets' sectors partially, about 3x the sample bytes, 2.5 % of HBM bandwidth at the headline)
-  if (Ring<F, kMode, kStats>()) return 0u;
-  // octets need 5.25 KB per wave: with the LDS Philox blocks beside them they fit no occupancy >= 7
-  return MinWaves<F, kMode, kStats>() <= 7 && !LdsRng<F, kMode, kStats>() ? 8u : 4u;
+struct KernelTraits {
+  // Occupancy target (waves per SIMD the register allocation must allow), chosen per variant by
+  // measurement (threaded kernels): Cornell 8 (7: -3 %), Cornell volume 8 (round 3, with box boundaries
+  // as one block: 7 / 8 waves 19.9 k / 20.6 k Mray/s), book 1 8, book 2 8 (6 / 7: -11 / -5 %; spills
+  // VGPRs, but its scalar loads are latency bound), the book 2 / all-features stack kernels 6. Other
+  // stack and the counting kernels keep the compiler's own allocation.
+  static constexpr int MinWaves() {
+    if (RT2_MIN_WAVES_PER_EU > 0) return RT2_MIN_WAVES_PER_EU;
+    if ((F == kFeatAll || F == kFeatBook2) && !kStats && (kMode == kModeStackGlobal || kMode == kModeStackHybrid))
+      return RT2_MIN_WAVES_ALL;  // book 2
+    if (F == kFeatBook2 && !kStats && kMode == kModeLinear) return RT2_MIN_WAVES_B2LIN;
+    if (kStats || kMode != kModeLinear) return 1;
+    if (F == kFeatXform) return RT2_MIN_WAVES_CORNELL;  // Cornell: 64 VGPRs at 8
+    if (F == (kFeatXform | kFeatMedium)) return RT2_MIN_WAVES_VOL;  // Cornell volume
+    if (F == kFeatAll) return 1;
+    return RT2_MIN_WAVES_BOOK1;                     // book 1
+  }
+  // The threaded product kernels at 8 waves per SIMD keep the Philox block in LDS (PathT; 1 KB per
+  // wave): four VGPRs fewer live across the loop, which removed the Cornell kernel's spills at 8
+  // waves (12 VGPRs; +1 %). Kernels at 7 waves or fewer keep it in VGPRs and stage whole sample
+  // octets instead.
+  static constexpr bool LdsRng() { return kMode == kModeLinear && !kStats && MinWaves() >= 8; }
+  // Book 2's threaded kernel parks the path state in LDS while a ray is traced (ParkedPath): its
+  // trace needs more registers than 8 waves per SIMD leave. Its samples are stored directly (12-B
+  // stores: staging measured no faster for it), which leaves the LDS room for the park planes.
+  static constexpr bool Park() { return F == kFeatBook2 && kMode == kModeLinear && !kStats && LdsRng(); }
+  // Kernels with the two-block Philox ring (PathT kRing): 8 Philox planes, where the LDS room allows it (not
+  // beside the Cornell volume kernel's candidate planes or book 2's park planes).
+  static constexpr bool Ring() { return LdsRng() && !Park() && !BoxPair<F, kMode>(); }
+  // Kernels that stage the launch's hit table (rt2_layout.h HIT) in dynamic LDS and resolve hits from it
+  // (resolve_hit_tab): the ring kernels with transforms, i.e. the Cornell box kernel, whose trace keeps
+  // the hit's model-space ray. The Cornell volume kernel has no LDS room for it, and the sphere kernels
+  // spend under 1 % of their time resolving hits. A launch without a table (RenderParams::hit_bytes 0)
+  // takes the global-memory path in these kernels too.
+  static constexpr bool HitTable() {
+    return RT2_HIT_TABLE_KERNEL && Ring() && Has<F, kFeatXform>() && !Has<F, kFeatSphere | kFeatMedium>();
+  }
+  // Samples staged in LDS (rt2_layout.h kOctet): a lane keeps the first samples of a group of
+  // consecutive frames in LDS planes and writes the group with 16-B stores when its last sample is
+  // done; a chunk edge inside a group writes its samples one by one. Groups of 8 (an octet: 96 B,
+  // three whole 32-B sectors; 5.25 KB of LDS per wave, so at most 7 waves per SIMD) or, for kernels
+  // at 8 waves, of 4 (48 B; 2.25 KB per wave; the middle sector of an octet is written in two halves,
+  // 4/3 of the sample bytes reach memory). Returns the group size, 0 = direct 12-B stores.
+  static constexpr uint32_t StageGroup() {
+    if (kMode != kModeLinear || kStats || Park()) return 0u;
+    // the ring kernels (Cornell, book 1) store samples directly: their staging logic cost more time than
+    // the write traffic it saves (round 4, same box: C2 +0.9 %, book 1 +1 %; 12-B stores write the
+    // octets' sectors partially, about 3x the sample bytes, 2.5 % of HBM bandwidth at the headline)
+    if (Ring()) return 0u;
+    // octets need 5.25 KB per wave: with the LDS Philox blocks beside them they fit no occupancy >= 7
+    return MinWaves() <= 7 && !LdsRng() ? 8u : 4u;
+  }
+  // the model-space ray of the transform holding the closest hit, kept by the trace for resolve_hit
+  // (the ring kernels with transforms: the Cornell box)
+  static constexpr bool Xray() { return Ring() && Has<F, kFeatXform>(); }
+  // The wave's LDS planes (lds_u32, 64 lanes each), by first plane: Philox block, sample staging
+  // ([slot][component]), box-boundary candidates, parked path, kept model-space ray; kWavePlanes in all.
+  static constexpr uint32_t kStagePlanes = StageGroup() ? 3u * (StageGroup() - 1u) : 1u;
+  static constexpr uint32_t kRngP = 0u;
+  static constexpr uint32_t kOctP = kRngP + (LdsRng() ? (Ring() ? 8u : 4u) : 0u);
+  static constexpr uint32_t kCandP = kOctP + (StageGroup() ? kStagePlanes : 0u);
+  static constexpr uint32_t kParkP = kCandP + (BoxPair<F, kMode>() ? kBoundaryAAMax : 0u);
+  static constexpr uint32_t kXrayP = kParkP + (Park() ? (uint32_t)kParkWords : 0u);
+  static constexpr uint32_t kWavePlanes = kXrayP + (Xray() ? 6u : 0u);
+};
+
+// This lane's word of plane 0 of its wave's planes in `base`, the block's array of `planes` LDS planes (64 lanes
+// each) per wave. The __shared__ array stays declared in the kernel that owns it.
+__device__ __forceinline__ lds_u32* wave_planes(lds_u32* base, uint32_t planes) {
+  const uint32_t lane = __lane_id();  // (read first: the order the kernels' code was generated in)
+  return base + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (planes * 64u) + lane;
 }
 
 // FL: the scene's feature set F, and for the list kernels (adaptive sampling) the bit kFeatList: their work
@@ -2403,23 +2417,23 @@ constexpr uint32_t kFeatList = 0x80000000u;
 // the kernel it is with its hit table staged: a launch without the table in LDS walks the BVH program.
 constexpr uint32_t kFeatFlat = 0x40000000u;
 template <uint32_t FL, int kMode, bool kStats>
-__global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~(kFeatList | kFeatFlat)), kMode, kStats>())) void render_kernel(const RenderParams P) {
+__global__ __launch_bounds__(kBlock, (KernelTraits<(FL & ~(kFeatList | kFeatFlat)), kMode, kStats>::MinWaves())) void render_kernel(const RenderParams P) {
   constexpr uint32_t F = FL & ~(kFeatList | kFeatFlat);
   constexpr bool kList = (FL & kFeatList) != 0u;
   constexpr bool kFlat = (FL & kFeatFlat) != 0u;
   static_assert(!kFlat || (kMode == kModeLinear && !kStats), "the flat walk: threaded product kernels only");
   static_assert(!kFlat || (F & (kFeatSphere | kFeatMedium | kFeatAccList)) == 0u,
                 "the flat walk's scalar step index: no step kind that sets a per-lane next (sphere, medium, accelerated list)");
+  using T = KernelTraits<F, kMode, kStats>;
   constexpr bool kLds = kMode == kModeStackLds || kMode == kModeStackHybrid;
-  constexpr uint32_t kGroup = StageGroup<F, kMode, kStats>();
-  constexpr uint32_t kPlanes = kGroup ? 3u * (kGroup - 1u) : 1u;  // [slot][component] planes of 64 lanes
+  constexpr uint32_t kGroup = T::StageGroup(), kPlanes = T::kStagePlanes;
   Nodes<kMode> N{reinterpret_cast<const float4*>(P.nodes), P.lds_nodes};
   if constexpr (kLds) {
     const float4* src = reinterpret_cast<const float4*>(P.nodes);
     for (uint32_t i = threadIdx.x; i < P.lds_nodes; i += kBlock) s_dyn[i] = src[i];
     __syncthreads();
   }
-  constexpr bool kHitTab = HitTable<F, kMode, kStats>();
+  constexpr bool kHitTab = T::HitTable();
   if constexpr (kHitTab) {
     if (P.hit_bytes != 0u) {  // wave-uniform; the table is whole float4 records (RenderLdsBytes)
       const float4* src = reinterpret_cast<const float4*>(P.hit_table);
@@ -2429,22 +2443,12 @@ __global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~(kFeatList | kFeatFlat)), 
   }
   uint32_t* stk = reinterpret_cast<uint32_t*>(s_dyn + (kLds ? P.lds_nodes : 0u)) + threadIdx.x;
   const int lane = (int)__lane_id();
-  constexpr bool kLdsRng = LdsRng<F, kMode, kStats>();
-  constexpr bool kPark = Park<F, kMode, kStats>();
-  // the wave's LDS planes (lds_u32): Philox block, sample staging, box-boundary candidates, parked path
-  constexpr uint32_t kRngP = 0u,
-                     kOctP = kRngP + (kLdsRng ? (Ring<F, kMode, kStats>() ? 8u : 4u) : 0u),
-                     kCandP = kOctP + (kGroup ? kPlanes : 0u);
-  constexpr uint32_t kParkP = kCandP + (BoxPair<F, kMode>() ? kBoundaryAAMax : 0u);
-  // the model-space ray of the transform holding the closest hit, kept by the trace for resolve_hit
-  // (the ring kernels with transforms: the Cornell box)
-  constexpr bool kXray = Ring<F, kMode, kStats>() && Has<F, kFeatXform>();
-  constexpr uint32_t kXrayP = kParkP + (kPark ? (uint32_t)kParkWords : 0u);
-  constexpr uint32_t kWavePlanes = kXrayP + (kXray ? 6u : 0u);
+  constexpr bool kLdsRng = T::LdsRng(), kPark = T::Park(), kXray = T::Xray();
+  constexpr uint32_t kRngP = T::kRngP, kOctP = T::kOctP, kCandP = T::kCandP, kParkP = T::kParkP, kXrayP = T::kXrayP;
   lds_u32* lp = nullptr;  // this lane's word of plane 0
-  if constexpr (kWavePlanes != 0u) {
-    __shared__ uint32_t s_planes[(kBlock / 64) * kWavePlanes * 64];
-    lp = (lds_u32*)(s_planes) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kWavePlanes * 64u) + lane;
+  if constexpr (T::kWavePlanes != 0u) {
+    __shared__ uint32_t s_planes[(kBlock / 64) * T::kWavePlanes * 64];
+    lp = wave_planes((lds_u32*)(s_planes), T::kWavePlanes);
   }
   const f3 bg = mk(P.background[0], P.background[1], P.background[2]);
   bool need = true;   // lane wants a work item
@@ -2453,7 +2457,7 @@ __global__ __launch_bounds__(kBlock, (MinWaves<(FL & ~(kFeatList | kFeatFlat)), 
   unsigned long long rays = 0;  // rays cast by the wave (popcounts of a ballot at the loop head)
   uint32_t bnext = 0, bend = 0;  // the wave's reserved batch of work items (wave-uniform)
   uint32_t item_rays = 0;
-  constexpr bool kRing = Ring<F, kMode, kStats>();  // two-block Philox ring
+  constexpr bool kRing = T::Ring();  // two-block Philox ring
   PathT<kLdsRng, kRing, !Has<F, kFeatSphere>()> path;
   path.rb = lp + 64u * kRngP;
   lds_u32* pk = lp + 64u * kParkP;  // this lane's park planes (kPark)
@@ -3069,10 +3073,24 @@ constexpr uint32_t kVariants[] = {
     kFeatXform,                                   // Cornell box
     kFeatXform | kFeatMedium,                     // Cornell volume
     kFeatSphere | kFeatSpecular | kFeatDefocus,   // RTIOW book 1
-    kFeatSphere | kFeatMedium | kFeatXform | kFeatNoise | kFeatSpecular | kFeatAccList | kFeatMotion,  // RTNW book 2
+    kFeatBook2,                                   // RTNW book 2
     kFeatAll,                                     // everything (scene graphs, checker textures)
 };
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+
+// The one place that turns a launch's variant index into a compile-time one: f(std::integral_constant<int, V>{})
+// for v == V, one instantiation of f per entry of kVariants; a value-initialised result (null, false) for any
+// other v.
+template <class Fn, int... V>
+auto WithVariant(int v, Fn f, std::integer_sequence<int, V...>) {
+  decltype(f(std::integral_constant<int, 0>{})) r{};
+  (void)((v == V && (r = f(std::integral_constant<int, V>{}), true)) || ...);
+  return r;
+}
+template <class Fn>
+auto WithVariant(int v, Fn f) {
+  return WithVariant(v, f, std::make_integer_sequence<int, kNumVariants>{});
+}
 
 using KernelFn = void (*)(RenderParams);
 
@@ -3083,7 +3101,7 @@ KernelFn Pick(bool stats) {
 }
 
 template <int V>
-KernelFn PickMode(int mode, bool stats) {
+KernelFn PickMode(std::integral_constant<int, V>, int mode, bool stats) {
   switch (mode) {
     case kModeStackLds: return Pick<V, kModeStackLds>(stats);
     case kModeLinear: return Pick<V, kModeLinear>(stats);
@@ -3095,7 +3113,7 @@ KernelFn PickMode(int mode, bool stats) {
 // The kernels over an active list (rt2.h "Adaptive sampling"): instantiated for the threaded traversal only,
 // the mode launches select by default.
 template <int V>
-KernelFn PickList(bool stats) {
+KernelFn PickList(std::integral_constant<int, V>, bool stats) {
   return stats ? reinterpret_cast<KernelFn>(&render_kernel<kVariants[V] | kFeatList, kModeLinear, true>)
                : reinterpret_cast<KernelFn>(&render_kernel<kVariants[V] | kFeatList, kModeLinear, false>);
 }
@@ -3116,24 +3134,59 @@ KernelFn Kernel(int v, int mode, bool stats, bool list = false, bool flat = fals
   }
   if (list) {
     if (mode != kModeLinear) return nullptr;
-    switch (v) {
-      case 0: return PickList<0>(stats);
-      case 1: return PickList<1>(stats);
-      case 2: return PickList<2>(stats);
-      case 3: return PickList<3>(stats);
-      case 4: return PickList<4>(stats);
-    }
-    return nullptr;
+    return WithVariant(v, [&](auto V) { return PickList(V, stats); });
   }
-  switch (v) {
-    case 0: return PickMode<0>(mode, stats);
-    case 1: return PickMode<1>(mode, stats);
-    case 2: return PickMode<2>(mode, stats);
-    case 3: return PickMode<3>(mode, stats);
-    case 4: return PickMode<4>(mode, stats);
-  }
-  return nullptr;
+  return WithVariant(v, [&](auto V) { return PickMode(V, mode, stats); });
 #endif
+}
+
+// What the probe kernels below (feature pass, ray queries, occlusion queries) must agree on bit for bit, stated
+// once. Their argument lists are the ones under which every kernel's generated code stayed what it was with the
+// code written out in place (tools/isa_same.py): handed RenderParams or a HitRef by reference, or with
+// QueryRayValid inside the loader, the same source scheduled differently.
+// The path stream a ConstantMedium on a probe ray's way draws from: (seed, pixel 0xFFFFFFF0, frame 0) from its
+// start, the block in registers (the stream oracle_scene_hit opens).
+__device__ __forceinline__ PathT<false> probe_path() {
+  PathT<false> path;
+  path.rb = nullptr;
+  path.pix = 0xFFFFFFF0u;
+  path.sij = 0;
+  path.r0 = path.r1 = path.r2 = path.r3 = 0;
+  path.start(0);
+  return path;
+}
+// The 16-float record of a hit (layout and albedo rule: features_kernel's comment): dist = |hp - origin|, each
+// operation rounded on its own in its order.
+template <uint32_t F>
+__device__ __forceinline__ void store_hit_record(float4* o, const ShadeArgs& S, float t, f3 hp, f3 hn,
+                                                 bool front, uint32_t mat, f3 origin) {
+  const float4 m0 = S.materials[2 * mat], m1 = S.materials[2 * mat + 1];
+  const uint32_t type = bits(m0.x);
+  f3 alb = mk(m0.y, m0.z, m0.w);
+  if (type == kMatDielectric) alb = mk(1.0f, 1.0f, 1.0f);
+  if (type == kMatTexture || type == kMatDiffuseLight || type == kMatIsotropic) alb = tex_value<F>(S, bits(m1.z), hp);
+  const f3 dp = hp - origin;
+  const float dist = sqrtf(dot(dp, dp));
+  o[0] = make_float4(1.0f, t, hp.x, hp.y);
+  o[1] = make_float4(hp.z, hn.x, hn.y, hn.z);
+  o[2] = make_float4(front ? 1.0f : 0.0f, (float)mat, alb.x, alb.y);
+  o[3] = make_float4(alb.z, dist, 0.0f, 0.0f);
+}
+// The record of a miss (hit 0, albedo = the background) or, valid false, of a ray that was not traced (-1, 0, ...).
+__device__ __forceinline__ void store_miss_record(float4* o, f3 bg, bool valid) {
+  const float flag = valid ? 0.0f : -1.0f;
+  const float bx = valid ? bg.x : 0.0f, by = valid ? bg.y : 0.0f, bz = valid ? bg.z : 0.0f;
+  o[0] = make_float4(flag, 0.0f, 0.0f, 0.0f);
+  o[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  o[2] = make_float4(0.0f, 0.0f, bx, by);
+  o[3] = make_float4(bz, 0.0f, 0.0f, 0.0f);
+}
+// Ray i of the caller's array (query.h: 8 floats) into r; the caller masks it by QueryRayValid(r).
+__device__ __forceinline__ void load_query_ray(const float4* __restrict__ rays, uint32_t i,
+                                               float (&r)[kQueryRayFloats]) {
+  const float4 a = rays[2ull * i], b = rays[2ull * i + 1ull];
+  r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w;
+  r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3168,12 +3221,7 @@ __global__ __launch_bounds__(kBlock) void features_kernel(const RenderParams P, 
   const f3 c = mk(C.center[0], C.center[1], C.center[2]);
   const f3 pc = (p00 + ((float)x * du)) + ((float)y * dv);
   const f3 d = normalize(pc - c);
-  PathT<false> path;
-  path.rb = nullptr;
-  path.pix = 0xFFFFFFF0u;
-  path.sij = 0;
-  path.r0 = path.r1 = path.r2 = path.r3 = 0;
-  path.start(0);
+  PathT<false> path = probe_path();
   const Nodes<kModeStackGlobal> N{reinterpret_cast<const float4*>(P.nodes), 0u};
   HitRef h{0.0f, kRefNone, kRefNone};
   Counters cnt = {};
@@ -3181,10 +3229,7 @@ __global__ __launch_bounds__(kBlock) void features_kernel(const RenderParams P, 
   const bool hit = trace_stack<F, kModeStackGlobal, false>(P, N, c, d, 0.0f, path, h, stk, cnt, overflow);
   float4* o = out + 4ull * i;
   if (!hit) {
-    o[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    o[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    o[2] = make_float4(0.0f, 0.0f, P.background[0], P.background[1]);
-    o[3] = make_float4(P.background[2], 0.0f, 0.0f, 0.0f);
+    store_miss_record(o, mk(P.background[0], P.background[1], P.background[2]), true);
     return;
   }
   f3 hp, hn;
@@ -3193,17 +3238,7 @@ __global__ __launch_bounds__(kBlock) void features_kernel(const RenderParams P, 
   resolve_hit<F, kModeStackGlobal, true>(N, h, c, d, 0.0f, hp, hn, front, mat);
   const ShadeArgs S{reinterpret_cast<const float4*>(P.materials), reinterpret_cast<const float4*>(P.textures),
                     reinterpret_cast<const float4*>(P.perlin_vec), P.perlin_perm};
-  const float4 m0 = S.materials[2 * mat], m1 = S.materials[2 * mat + 1];
-  const uint32_t type = bits(m0.x);
-  f3 alb = mk(m0.y, m0.z, m0.w);
-  if (type == kMatDielectric) alb = mk(1.0f, 1.0f, 1.0f);
-  if (type == kMatTexture || type == kMatDiffuseLight || type == kMatIsotropic) alb = tex_value<F>(S, bits(m1.z), hp);
-  const f3 dp = hp - c;
-  const float dist = sqrtf(dot(dp, dp));
-  o[0] = make_float4(1.0f, h.t, hp.x, hp.y);
-  o[1] = make_float4(hp.z, hn.x, hn.y, hn.z);
-  o[2] = make_float4(front ? 1.0f : 0.0f, (float)mat, alb.x, alb.y);
-  o[3] = make_float4(alb.z, dist, 0.0f, 0.0f);
+  store_hit_record<F>(o, S, h.t, hp, hn, front, mat, c);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3226,9 +3261,7 @@ __global__ __launch_bounds__(kBlock) void query_kernel(const RenderParams P, con
   float r[kQueryRayFloats] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   bool valid = false;
   if (i < n) {
-    const float4 a = rays[2ull * i], b = rays[2ull * i + 1ull];
-    r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w;
-    r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
+    load_query_ray(rays, i, r);
     valid = QueryRayValid(r);
   }
   const f3 ro = mk(r[kQrOx], r[kQrOy], r[kQrOz]), rd = mk(r[kQrDx], r[kQrDy], r[kQrDz]);
@@ -3237,8 +3270,7 @@ __global__ __launch_bounds__(kBlock) void query_kernel(const RenderParams P, con
   lds_u32* cand = nullptr;
   if constexpr (BoxPair<F, kMode>()) {
     __shared__ uint32_t s_cand[(kBlock / 64) * kBoundaryAAMax * 64];
-    cand = (lds_u32*)(s_cand) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kBoundaryAAMax * 64u) +
-           (uint32_t)__lane_id();
+    cand = wave_planes((lds_u32*)(s_cand), kBoundaryAAMax);
   }
   bool hit = false;
   f3 hp = mk(0.0f, 0.0f, 0.0f), hn = mk(0.0f, 0.0f, 0.0f);
@@ -3248,12 +3280,7 @@ __global__ __launch_bounds__(kBlock) void query_kernel(const RenderParams P, con
   // (a wave without a valid ray skips the trace by a scalar branch: no step is loaded for it)
   if (__ballot(valid) != 0ull) {
     if (valid) {
-      PathT<false> path;
-      path.rb = nullptr;
-      path.pix = 0xFFFFFFF0u;
-      path.sij = 0;
-      path.r0 = path.r1 = path.r2 = path.r3 = 0;
-      path.start(0);
+      PathT<false> path = probe_path();
       Counters cnt = {};
       if constexpr (kMode == kModeLinear) {
         hit = trace_linear<F, false, false, true>(P, RegRay{ro, rd}, time, path, h, cand, nullptr, cnt, false, nullptr,
@@ -3273,43 +3300,19 @@ __global__ __launch_bounds__(kBlock) void query_kernel(const RenderParams P, con
   if (i >= n) return;
   float4* o = out + 4ull * i;
   if (!hit) {
-    const float flag = valid ? 0.0f : -1.0f;
-    const float bx = valid ? P.background[0] : 0.0f, by = valid ? P.background[1] : 0.0f,
-                bz = valid ? P.background[2] : 0.0f;
-    o[0] = make_float4(flag, 0.0f, 0.0f, 0.0f);
-    o[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    o[2] = make_float4(0.0f, 0.0f, bx, by);
-    o[3] = make_float4(bz, 0.0f, 0.0f, 0.0f);
+    store_miss_record(o, mk(P.background[0], P.background[1], P.background[2]), valid);
     return;
   }
-  // albedo and dist by the feature pass's rule, each operation rounded on its own in its order
   const ShadeArgs S{reinterpret_cast<const float4*>(P.materials), reinterpret_cast<const float4*>(P.textures),
                     reinterpret_cast<const float4*>(P.perlin_vec), P.perlin_perm};
-  const float4 m0 = S.materials[2 * mat], m1 = S.materials[2 * mat + 1];
-  const uint32_t type = bits(m0.x);
-  f3 alb = mk(m0.y, m0.z, m0.w);
-  if (type == kMatDielectric) alb = mk(1.0f, 1.0f, 1.0f);
-  if (type == kMatTexture || type == kMatDiffuseLight || type == kMatIsotropic) alb = tex_value<F>(S, bits(m1.z), hp);
-  const f3 dp = hp - ro;
-  const float dist = sqrtf(dot(dp, dp));
-  o[0] = make_float4(1.0f, h.t, hp.x, hp.y);
-  o[1] = make_float4(hp.z, hn.x, hn.y, hn.z);
-  o[2] = make_float4(front ? 1.0f : 0.0f, (float)mat, alb.x, alb.y);
-  o[3] = make_float4(alb.z, dist, 0.0f, 0.0f);
+  store_hit_record<F>(o, S, h.t, hp, hn, front, mat, ro);  // the feature pass's record
 }
 
 using QueryFn = void (*)(RenderParams, const float4*, float4*, uint32_t);
 // threaded: the instantiation of kVariants[v]; else the one stack instantiation
 QueryFn QueryKernel(int v, bool threaded) {
   if (!threaded) return &query_kernel<kFeatAll, kModeStackGlobal>;
-  switch (v) {
-    case 0: return &query_kernel<kVariants[0], kModeLinear>;
-    case 1: return &query_kernel<kVariants[1], kModeLinear>;
-    case 2: return &query_kernel<kVariants[2], kModeLinear>;
-    case 3: return &query_kernel<kVariants[3], kModeLinear>;
-    case 4: return &query_kernel<kVariants[4], kModeLinear>;
-  }
-  return nullptr;
+  return WithVariant(v, [](auto V) -> QueryFn { return &query_kernel<kVariants[V], kModeLinear>; });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3326,9 +3329,7 @@ __global__ __launch_bounds__(kBlock) void occlusion_kernel(const RenderParams P,
   float r[kQueryRayFloats] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   bool valid = false;
   if (i < n) {
-    const float4 a = rays[2ull * i], b = rays[2ull * i + 1ull];
-    r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w;
-    r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
+    load_query_ray(rays, i, r);
     valid = QueryRayValid(r);
   }
   const f3 ro = mk(r[kQrOx], r[kQrOy], r[kQrOz]), rd = mk(r[kQrDx], r[kQrDy], r[kQrDz]);
@@ -3336,18 +3337,12 @@ __global__ __launch_bounds__(kBlock) void occlusion_kernel(const RenderParams P,
   lds_u32* cand = nullptr;  // the wave's box-boundary candidate planes, as the query kernel's
   if constexpr (BoxPair<F, kMode>()) {
     __shared__ uint32_t s_cand[(kBlock / 64) * kBoundaryAAMax * 64];
-    cand = (lds_u32*)(s_cand) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kBoundaryAAMax * 64u) +
-           (uint32_t)__lane_id();
+    cand = wave_planes((lds_u32*)(s_cand), kBoundaryAAMax);
   }
   bool hit = false;
   if (__ballot(valid) != 0ull) {
     if (valid) {
-      PathT<false> path;
-      path.rb = nullptr;
-      path.pix = 0xFFFFFFF0u;
-      path.sij = 0;
-      path.r0 = path.r1 = path.r2 = path.r3 = 0;
-      path.start(0);
+      PathT<false> path = probe_path();
       Counters cnt = {};
       HitRef h{0.0f, kRefNone, kRefNone};  // (not read: the trace's flag is the answer)
       if constexpr (kMode == kModeLinear) {
@@ -3370,14 +3365,7 @@ using OcclusionFn = void (*)(RenderParams, const float4*, int8_t*, uint32_t);
 // chosen as QueryKernel chooses
 OcclusionFn OcclusionKernel(int v, bool threaded) {
   if (!threaded) return &occlusion_kernel<kFeatAll, kModeStackGlobal>;
-  switch (v) {
-    case 0: return &occlusion_kernel<kVariants[0], kModeLinear>;
-    case 1: return &occlusion_kernel<kVariants[1], kModeLinear>;
-    case 2: return &occlusion_kernel<kVariants[2], kModeLinear>;
-    case 3: return &occlusion_kernel<kVariants[3], kModeLinear>;
-    case 4: return &occlusion_kernel<kVariants[4], kModeLinear>;
-  }
-  return nullptr;
+  return WithVariant(v, [](auto V) -> OcclusionFn { return &occlusion_kernel<kVariants[V], kModeLinear>; });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3612,15 +3600,8 @@ bool RenderTakesFlat(int variant, int mode, bool stats, bool list) {
 }
 
 bool RenderTakesHitTable(int variant, int mode, bool stats) {
-  if (variant < 0 || variant >= dev::kNumVariants || mode != kModeLinear || stats) return false;
-  switch (variant) {
-    case 0: return dev::HitTable<dev::kVariants[0], kModeLinear, false>();
-    case 1: return dev::HitTable<dev::kVariants[1], kModeLinear, false>();
-    case 2: return dev::HitTable<dev::kVariants[2], kModeLinear, false>();
-    case 3: return dev::HitTable<dev::kVariants[3], kModeLinear, false>();
-    case 4: return dev::HitTable<dev::kVariants[4], kModeLinear, false>();
-  }
-  return false;
+  if (mode != kModeLinear || stats) return false;
+  return dev::WithVariant(variant, [](auto V) { return dev::KernelTraits<dev::kVariants[V], kModeLinear, false>::HitTable(); });
 }
 
 size_t RenderLdsBytes(const RenderParams& p) {
@@ -3669,29 +3650,28 @@ hipError_t LaunchFeatures(const RenderParams& p, float* out, hipStream_t stream)
 // Dynamic LDS of a query launch: the stack walk's per-lane stacks; the threaded kernels' planes are static.
 size_t QueryLdsBytes(const RenderParams& p) { return p.lin_len ? 0 : (size_t)p.stack_depth * dev::kBlock * 4; }
 
-// The query kernel over n rays (8 floats each) into out (16 floats each), both on the stream's device. p: the
-// scene tables, root, background, seed and stack_depth of BaseParams and, for the threaded walk, lin_wide, lind
-// and lin_len (0: the stack walk).
-hipError_t LaunchQuery(const RenderParams& p, int variant, const float* rays, float* out, uint32_t n,
-                       hipStream_t stream) {
+// One launch body for both probe kernels over n rays (8 floats each), rays and out on the stream's device.
+template <class Out>
+static hipError_t LaunchProbe(void (*fn)(RenderParams, const float4*, Out*, uint32_t), const RenderParams& p,
+                              const float* rays, Out* out, uint32_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  dev::QueryFn fn = dev::QueryKernel(variant, p.lin_len != 0);
-  if (!fn || n > 0x7FFFFFFFu || (!p.lin_len && p.stack_depth > kTraversalStack)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(fn, dim3(QueryGrid(n, (uint32_t)dev::kBlock)), dim3(dev::kBlock), QueryLdsBytes(p), stream, p,
-                     reinterpret_cast<const float4*>(rays), reinterpret_cast<float4*>(out), n);
-  return hipGetLastError();
-}
-
-// The occlusion kernel over n rays (8 floats each) into out (one byte each, exactly n written), both on the
-// stream's device. p and the choice of walk: as LaunchQuery.
-hipError_t LaunchOcclusion(const RenderParams& p, int variant, const float* rays, int8_t* out, uint32_t n,
-                           hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  dev::OcclusionFn fn = dev::OcclusionKernel(variant, p.lin_len != 0);
   if (!fn || n > 0x7FFFFFFFu || (!p.lin_len && p.stack_depth > kTraversalStack)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3(QueryGrid(n, (uint32_t)dev::kBlock)), dim3(dev::kBlock), QueryLdsBytes(p), stream, p,
                      reinterpret_cast<const float4*>(rays), out, n);
   return hipGetLastError();
+}
+
+// The query kernel into out (16 floats per ray). p: the scene tables, root, background, seed and stack_depth of
+// BaseParams and, for the threaded walk, lin_wide, lind and lin_len (0: the stack walk).
+hipError_t LaunchQuery(const RenderParams& p, int variant, const float* rays, float* out, uint32_t n,
+                       hipStream_t stream) {
+  return LaunchProbe(dev::QueryKernel(variant, p.lin_len != 0), p, rays, reinterpret_cast<float4*>(out), n, stream);
+}
+
+// The occlusion kernel into out (one byte per ray, exactly n written). p and the choice of walk: as LaunchQuery.
+hipError_t LaunchOcclusion(const RenderParams& p, int variant, const float* rays, int8_t* out, uint32_t n,
+                           hipStream_t stream) {
+  return LaunchProbe(dev::OcclusionKernel(variant, p.lin_len != 0), p, rays, out, n, stream);
 }
 
 hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsigned long long* d_out, hipStream_t stream) {

@@ -7,12 +7,9 @@ the quad-run loop remain: 3 of 4). The kernel's resources stay what they were (6
 scratch, 16 SGPR spills), and the kernel it is instantiated from, which walks the BVH program and keeps the
 per-lane index, keeps its figures (64 VGPRs, 78 SGPRs, 14 SGPR spills, no scratch). Compiled with
 -DRT2_ONLY_VARIANT=0 (the Cornell kernels only)."""
-import re
-import subprocess
-
 import pytest
 
-from test_kernel_asm import SRC, _kernel, _loops, _salu, makefile_hipflags
+from kernel_isa import compile_isa, kernel, loops, resources, salu
 
 FLAT = "ILj1073741828ELi2ELb0E"  # render_kernel<kFeatXform | kFeatFlat, kModeLinear, false>
 BVH = "ILj4ELi2ELb0E"  # render_kernel<kFeatXform, kModeLinear, false>
@@ -22,19 +19,8 @@ FLAT_TRACE_LOOP_INNER_LOOPS_BEFORE = 4
 
 
 @pytest.fixture(scope="module")
-def cornell_isa(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa_scalar_step") / "render0.s"
-    r = subprocess.run(["/opt/rocm/bin/hipcc", *makefile_hipflags(), "--cuda-device-only", "-S", "-o", str(out),
-                        "-DRT2_ONLY_VARIANT=0", SRC, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out.read_text(), r.stderr
-
-
-def _resources(remarks, tag):
-    blk = [b for b in re.split(r"remark: Function Name: ", remarks)[1:] if tag in b.split()[0]]
-    assert len(blk) == 1, tag
-    return lambda k: int(re.search(re.escape(k) + r": (\d+)", blk[0]).group(1))
+def cornell_isa():
+    return compile_isa(("RT2_ONLY_VARIANT=0",))
 
 
 def _valu(c):
@@ -42,7 +28,7 @@ def _valu(c):
 
 
 def test_flat_kernel_keeps_its_resources(cornell_isa):
-    g = _resources(cornell_isa[1], FLAT)
+    g = resources(cornell_isa[1], FLAT)
     got = {k: g(k) for k in ("VGPRs", "Occupancy [waves/SIMD]", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill")}
     print("flat kernel:", got)
     assert got["VGPRs"] <= 63 and got["Occupancy [waves/SIMD]"] == 8, got
@@ -51,27 +37,27 @@ def test_flat_kernel_keeps_its_resources(cornell_isa):
 
 
 def test_flat_trace_loop_lost_the_per_lane_index(cornell_isa):
-    _, body = _kernel(cornell_isa, FLAT)
-    loops = _loops(body)
-    trace = [j for j, (h, d, c) in enumerate(loops) if d == 2 and _salu(c) > 60]
-    assert len(trace) == 2, [(h, d) for h, d, _ in loops]
-    c = loops[trace[0]][2]
+    _, body = kernel(cornell_isa, FLAT)
+    lps = loops(body)
+    trace = [j for j, (h, d, c) in enumerate(lps) if d == 2 and salu(c) > 60]
+    assert len(trace) == 2, [(h, d) for h, d, _ in lps]
+    c = lps[trace[0]][2]
     # the first trace loop's own loops: the depth-3 loops listed before the next depth-2 loop
     inner = []
-    for h, d, _ in loops[trace[0] + 1:]:
+    for h, d, _ in lps[trace[0] + 1:]:
         if d <= 2:
             break
         if d == 3:
             inner.append(h)
-    print("flat trace loop: VALU", _valu(c), "SALU", _salu(c), "depth-3 loops", inner,
-          "| second trace loop: VALU", _valu(loops[trace[1]][2]), "SALU", _salu(loops[trace[1]][2]))
-    assert _salu(c) <= FLAT_TRACE_LOOP_SALU_BEFORE, _salu(c)
+    print("flat trace loop: VALU", _valu(c), "SALU", salu(c), "depth-3 loops", inner,
+          "| second trace loop: VALU", _valu(lps[trace[1]][2]), "SALU", salu(lps[trace[1]][2]))
+    assert salu(c) <= FLAT_TRACE_LOOP_SALU_BEFORE, salu(c)
     assert _valu(c) <= FLAT_TRACE_LOOP_VALU_BEFORE - 30, _valu(c)
     assert len(inner) == FLAT_TRACE_LOOP_INNER_LOOPS_BEFORE - 1, inner
 
 
 def test_bvh_program_kernel_keeps_its_figures(cornell_isa):
-    g = _resources(cornell_isa[1], BVH)
+    g = resources(cornell_isa[1], BVH)
     got = {k: g(k) for k in ("VGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]")}
     print("BVH-program kernel:", got)
     assert got == {"VGPRs": 64, "TotalSGPRs": 78, "SGPRs Spill": 14, "VGPRs Spill": 0, "ScratchSize [bytes/lane]": 0}, got

@@ -2,33 +2,17 @@
  * no inline-asm block issues a scalar load whose base/offset registers an earlier load of the same
    block writes (that load's data may land first: a wrong address, i.e. a GPU memory fault);
  * no scratch (spill) memory in the variants the benchmark uses."""
-import os
 import re
 import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-SRC = os.path.join(ROOT, "raytrace2_amd", "csrc", "render.hip")
-
-
-def makefile_hipflags():
-    """The kernel's compile flags as the build uses them (raytrace2_amd/csrc/Makefile HIPFLAGS)."""
-    mk = open(os.path.join(ROOT, "raytrace2_amd", "csrc", "Makefile")).read()
-    line = re.search(r"^HIPFLAGS\s*:=(.*)$", mk, re.M).group(1)
-    return [f for f in line.split() if not f.startswith("$(") and f not in ("-fPIC", "-Wall")]
+from kernel_isa import HIPCC, SRC, compile_isa, kernel, loops, makefile_hipflags, remarks_by_function, salu
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "render.s"
-    flags = makefile_hipflags()
-    assert "--offload-arch=gfx950" in flags
-    r = subprocess.run(["/opt/rocm/bin/hipcc", *flags, "--cuda-device-only", "-S", "-o", str(out), SRC,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return out.read_text(), r.stderr
+def isa():
+    return compile_isa()
 
 
 def test_inline_scalar_loads_have_no_register_hazards(isa):
@@ -54,10 +38,8 @@ def test_no_scratch_in_bench_variants(isa):
     At 8 waves (64 VGPRs) the compiler parks a few loop-invariant values in scratch (at most 16 B per
     lane) once before the path loop and reloads them (L1-hit loads, no store traffic)."""
     s, remarks = isa
-    blocks = re.split(r"remark: Function Name: ", remarks)[1:]
     seen = 0
-    for b in blocks:
-        name = b.split()[0]
+    for name, b in remarks_by_function(remarks).items():
         if "ILj4ELi2ELb0E" not in name:
             continue
         seen += 1
@@ -83,22 +65,12 @@ def _loop_depth_scratch(body):
     return out
 
 
-def _kernel(isa, tag):
-    s, remarks = isa
-    blk = [b for b in re.split(r"remark: Function Name: ", remarks)[1:] if tag in b.split()[0]]
-    assert len(blk) == 1, tag
-    name = blk[0].split()[0]
-    scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blk[0]).group(1))
-    body = s.split(f"\n{name}:", 1)[1].split(".Lfunc_end", 1)[0]
-    return scratch, body
-
-
 def test_cornell_volume_bench_kernel_spills_at_most_one_pair(isa):
     """the Cornell volume kernel the C4 bench runs (threaded, 8 waves) spills at most one
     8-byte register pair (the path's pixel word, stored once per work item, reloaded at the Philox
     refills) and no spill store sits inside the trace's loops (round 3's one-pass box boundaries had
     pushed it to 25 spilled VGPRs, 56 B per lane, stored and reloaded in the trace)."""
-    scratch, body = _kernel(isa, "ILj6ELi2ELb0E")
+    scratch, body = kernel(isa, "ILj6ELi2ELb0E")
     deep = [x for x in _loop_depth_scratch(body) if x[0] >= 2 and x[1].startswith("scratch_store")]
     assert scratch <= 16 and not deep, (scratch, deep[:5])
 
@@ -109,7 +81,7 @@ def test_book2_bench_kernel_spills_stay_out_of_the_trace(isa):
     34 SGPRs spilled): 72 B of it were the marble texture's double-precision sin coefficients, hoisted
     out of the loop into registers; the float restatement (render.hip sin_f) took them out (VERDICT r05
     item 4)."""
-    scratch, body = _kernel(isa, "ILj815ELi2ELb0E")
+    scratch, body = kernel(isa, "ILj815ELi2ELb0E")
     deep = [x for x in _loop_depth_scratch(body) if x[0] >= 2]
     assert scratch <= 16 and not deep, (scratch, deep[:5])
 
@@ -122,56 +94,19 @@ def test_book2_trace_loops_keep_the_scalar_issue_code_generation(isa):
     most 32 SALU (27); its trace loop, which holds the box-level test of flagged MakeBox runs (boxaa.h), at
     most 440 SALU (377; 361 before the box test; 586 without -structurizecfg-skip-uniform-regions, and
     without -simplifycfg-sink-common=false the quad bodies merge into one: 2 v_or3)."""
-    _, body = _kernel(isa, "ILj815ELi2ELb0E")
-    loops = _loops(body)
-    quad = [(h, c) for h, d, c in loops if d == 3 and c["v_or3_b32"] > 0 and any(k.startswith("s_load") for k in c)]
-    assert len(quad) == 1, [(h, d) for h, d, _ in loops]
+    _, body = kernel(isa, "ILj815ELi2ELb0E")
+    lps = loops(body)
+    quad = [(h, c) for h, d, c in lps if d == 3 and c["v_or3_b32"] > 0 and any(k.startswith("s_load") for k in c)]
+    assert len(quad) == 1, [(h, d) for h, d, _ in lps]
     _, c = quad[0]
     assert c["v_or3_b32"] == 6, ("per-axis QUADAA bodies merged", c["v_or3_b32"])
     assert c["s_and_saveexec_b64"] == 0, c["s_and_saveexec_b64"]
-    assert _salu(c) <= 28, _salu(c)
-    trace = [(h, c) for h, d, c in loops if d == 2 and _salu(c) > 60]
-    assert len(trace) == 1 and _salu(trace[0][1]) <= 440, [_salu(c) for _, c in trace]
+    assert salu(c) <= 28, salu(c)
+    trace = [(h, c) for h, d, c in lps if d == 2 and salu(c) > 60]
+    assert len(trace) == 1 and salu(trace[0][1]) <= 440, [salu(c) for _, c in trace]
     # the BVH-step run: the first depth-3 loop nested in the trace loop
-    bvh = [c for h, d, c in loops if d == 3 and c["v_or3_b32"] == 0 and _salu(c) > 10]
-    assert bvh and _salu(bvh[0]) <= 32, [_salu(c) for c in bvh]
-
-
-def _loops(body, lines=False):
-    """Every loop of a kernel body: (header label, depth, opcode counts of the loop's blocks), and with
-    lines=True the loop's instruction lines as a fourth element."""
-    import collections
-    blocks, cur = [], None
-    for line in body.split("\n"):
-        if line.startswith(".LBB") or line.startswith("; %bb"):
-            cur = [line.split()[0].rstrip(":") if line.startswith(".LBB") else line.split()[1], [line], [], []]
-            blocks.append(cur)
-        elif cur is not None and line.strip().startswith(";"):
-            if not cur[2]:
-                cur[1].append(line)
-        elif cur is not None and line.startswith("\t") and not line.strip().startswith("."):
-            cur[2].append(line.split()[0])
-            cur[3].append(line.strip())
-    out = []
-    for b in blocks:
-        m = re.search(r"Loop Header: Depth=(\d+)", " ".join(b[1]))
-        if not m:
-            continue
-        h = b[0].lstrip(".L")
-        c = collections.Counter()
-        ls = []
-        for bb in blocks:
-            txt = " ".join(bb[1])
-            if bb is b or f"Header={h} " in txt or f"Parent Loop {h} " in txt or txt.endswith(f"Header={h}"):
-                c.update(bb[2])
-                ls.extend(bb[3])
-        out.append((b[0], int(m.group(1)), c, ls) if lines else (b[0], int(m.group(1)), c))
-    return out
-
-
-def _salu(c):
-    return sum(v for k, v in c.items()
-               if k.startswith("s_") and not k.startswith(("s_load", "s_waitcnt", "s_nop", "s_cbranch", "s_branch")))
+    bvh = [c for h, d, c in lps if d == 3 and c["v_or3_b32"] == 0 and salu(c) > 10]
+    assert bvh and salu(bvh[0]) <= 32, [salu(c) for c in bvh]
 
 
 def test_cornell_quad_run_loop_keeps_the_scalar_issue_code_generation(isa):
@@ -185,16 +120,16 @@ def test_cornell_quad_run_loop_keeps_the_scalar_issue_code_generation(isa):
     and at most 28 SALU instructions (with the options: 22; without them: one merged body, 12 SALU but
     every axis's copies); its trace loop at most 150 SALU (140 with the box-level test of the boxes'
     MakeBox runs, 124 before it; without the options: 205)."""
-    _, body = _kernel(isa, "ILj4ELi2ELb0E")
-    loops = _loops(body)
-    quad = [(h, c) for h, d, c in loops if d == 3 and c["v_or3_b32"] > 0 and any(k.startswith("s_load") for k in c)]
-    assert len(quad) == 1, [(h, d) for h, d, _ in loops]
+    _, body = kernel(isa, "ILj4ELi2ELb0E")
+    lps = loops(body)
+    quad = [(h, c) for h, d, c in lps if d == 3 and c["v_or3_b32"] > 0 and any(k.startswith("s_load") for k in c)]
+    assert len(quad) == 1, [(h, d) for h, d, _ in lps]
     _, c = quad[0]
     assert c["v_or3_b32"] == 6, ("per-axis QUADAA bodies merged", c["v_or3_b32"])
     assert c["s_and_saveexec_b64"] == 0, c["s_and_saveexec_b64"]
-    assert _salu(c) <= 28, _salu(c)
-    trace = [c for h, d, c in loops if d == 2 and _salu(c) > 60]
-    assert len(trace) == 1 and _salu(trace[0]) <= 150, [_salu(c) for c in trace]
+    assert salu(c) <= 28, salu(c)
+    trace = [c for h, d, c in lps if d == 2 and salu(c) > 60]
+    assert len(trace) == 1 and salu(trace[0]) <= 150, [salu(c) for c in trace]
 
 
 @pytest.mark.parametrize("define", ["RT2_EXP_TRACE_TWICE=1", "RT2_EXP_TWICE=16383", "RT2_EXP_WAVESTEPS=1",
@@ -204,7 +139,7 @@ def test_diagnostic_builds_compile(define, tmp_path):
     counts, section stamps, launch-tail times, no-store traffic split): each compiles
     for the Cornell and book 2 kernels (RT2_ONLY_VARIANT: one threaded kernel per build)."""
     for v in (0, 3):
-        r = subprocess.run(["/opt/rocm/bin/hipcc", *makefile_hipflags(), "--cuda-device-only", "-c", "-o",
+        r = subprocess.run([HIPCC, *makefile_hipflags(), "--cuda-device-only", "-c", "-o",
                             str(tmp_path / f"k{v}.o"), f"-DRT2_ONLY_VARIANT={v}", f"-D{define}", SRC],
                            capture_output=True, text=True)
         assert r.returncode == 0, (define, v, r.stderr[-2000:])

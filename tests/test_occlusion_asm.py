@@ -2,41 +2,16 @@
 kernel variant plus the one stack walk, names that neither the query kernel's count nor the render kernels' tags
 pick up, no scratch in the Cornell instantiation, and an occupancy no lower than the query kernel's of the same
 variant. Reads the compiler's resource remarks only: names and resource numbers."""
-import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-SRC = os.path.join(ROOT, "raytrace2_amd", "csrc", "render.hip")
-# the tags by which tests/test_kernel_asm.py and the tools find render kernels in the ISA
-RENDER_TAGS = ["ILj4ELi2ELb0E", "ILj6ELi2ELb0E", "ILj815ELi2ELb0E", "ILj1073741828ELi2ELb0E", "render_kernel",
-               "features_kernel"]
-
-
-def makefile_hipflags():
-    mk = open(os.path.join(ROOT, "raytrace2_amd", "csrc", "Makefile")).read()
-    line = re.search(r"^HIPFLAGS\s*:=(.*)$", mk, re.M).group(1)
-    return [f for f in line.split() if not f.startswith("$(") and f not in ("-fPIC", "-Wall")]
+from kernel_isa import RENDER_TAGS, compile_isa, remarks_by_function, variants
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "render.s"
-    r = subprocess.run(["/opt/rocm/bin/hipcc", *makefile_hipflags(), "--cuda-device-only", "-S", "-o", str(out), SRC,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
-    return {b.split()[0]: b for b in blocks}
-
-
-def _variants():
-    """The entries of render.hip kVariants."""
-    src = open(SRC).read()
-    body = re.search(r"constexpr uint32_t kVariants\[\] = \{(.*?)\n\};", src, re.S).group(1)
-    return [l for l in body.split("\n") if l.strip().startswith("kFeat")]
+def remarks():
+    return remarks_by_function(compile_isa()[1])
 
 
 def _number(block, what):
@@ -45,7 +20,7 @@ def _number(block, what):
 
 def test_one_instantiation_per_variant_and_one_stack_walk(remarks):
     names = [n for n in remarks if "occlusion_kernel" in n]
-    nvar = len(_variants())
+    nvar = len(variants())
     assert nvar == 5 and len(names) == nvar + 1, names
     threaded = [n for n in names if re.search(r"occlusion_kernelILj\d+ELi2EE", n)]
     stack = [n for n in names if re.search(r"occlusion_kernelILj\d+ELi0EE", n)]
@@ -72,7 +47,7 @@ def test_occupancy_is_not_below_the_query_kernel_s(remarks):
     occ = {re.search(r"occlusion_kernel(ILj\d+ELi\d)EE", n).group(1): b for n, b in remarks.items()
            if "occlusion_kernel" in n}
     qry = {re.search(r"query_kernel(ILj\d+ELi\d)EE", n).group(1): b for n, b in remarks.items() if "query_kernel" in n}
-    assert set(occ) == set(qry) and len(occ) == len(_variants()) + 1
+    assert set(occ) == set(qry) and len(occ) == len(variants()) + 1
     for k in occ:
         a, q = _number(occ[k], "Occupancy [waves/SIMD]"), _number(qry[k], "Occupancy [waves/SIMD]")
         assert a >= q, (k, a, q)

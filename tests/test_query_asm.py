@@ -1,46 +1,21 @@
 """Static checks on the query kernel's generated code (hipcc cross-compiles here, no GPU): one instantiation per
 kernel variant plus the one stack walk, names that none of the render kernels' tags pick up, and no scratch in the
 Cornell instantiation. Reads the compiler's resource remarks only."""
-import os
 import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-SRC = os.path.join(ROOT, "raytrace2_amd", "csrc", "render.hip")
-# the tags by which tests/test_kernel_asm.py and the tools find render kernels in the ISA
-RENDER_TAGS = ["ILj4ELi2ELb0E", "ILj6ELi2ELb0E", "ILj815ELi2ELb0E", "ILj1073741828ELi2ELb0E", "render_kernel",
-               "features_kernel"]
-
-
-def makefile_hipflags():
-    mk = open(os.path.join(ROOT, "raytrace2_amd", "csrc", "Makefile")).read()
-    line = re.search(r"^HIPFLAGS\s*:=(.*)$", mk, re.M).group(1)
-    return [f for f in line.split() if not f.startswith("$(") and f not in ("-fPIC", "-Wall")]
+from kernel_isa import RENDER_TAGS, compile_isa, remarks_by_function, variants
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "render.s"
-    r = subprocess.run(["/opt/rocm/bin/hipcc", *makefile_hipflags(), "--cuda-device-only", "-S", "-o", str(out), SRC,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: Function Name: ", r.stderr)[1:]
-    return {b.split()[0]: b for b in blocks}
-
-
-def _variants():
-    """The entries of render.hip kVariants."""
-    src = open(SRC).read()
-    body = re.search(r"constexpr uint32_t kVariants\[\] = \{(.*?)\n\};", src, re.S).group(1)
-    return [l for l in body.split("\n") if l.strip().startswith("kFeat")]
+def remarks():
+    return remarks_by_function(compile_isa()[1])
 
 
 def test_one_instantiation_per_variant_and_one_stack_walk(remarks):
     names = [n for n in remarks if "query_kernel" in n]
-    nvar = len(_variants())
+    nvar = len(variants())
     assert nvar == 5 and len(names) == nvar + 1, names
     threaded = [n for n in names if re.search(r"query_kernelILj\d+ELi2EE", n)]
     stack = [n for n in names if re.search(r"query_kernelILj\d+ELi0EE", n)]
