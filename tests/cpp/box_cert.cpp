@@ -24,41 +24,11 @@
 #include <string>
 #include <vector>
 
-#include "scene.h"
-#define RT2_BOXAA_FN inline
-#include "boxaa.h"
+#include "kernel_model.h"  // B, F, Ulps, HostMath, kAbove1e8
 
-using namespace rt2;
+using namespace kernel_model;
 
 namespace {
-uint32_t B(float f) {
-  uint32_t b;
-  memcpy(&b, &f, 4);
-  return b;
-}
-float F(uint32_t b) {
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
-}
-struct HostMath {
-  static float div(float a, float b, float inv) {
-    const float q = a * inv;
-    return std::fma(std::fma(-b, q, a), inv, q);
-  }
-  static float min(float a, float b) { return std::fmin(a, b); }
-  static float max(float a, float b) { return std::fmax(a, b); }
-  static float min3(float a, float b, float c) { return std::fmin(std::fmin(a, b), c); }
-  static float max3(float a, float b, float c) { return std::fmax(std::fmax(a, b), c); }
-  static float amin3(float a, float b, float c) { return min3(std::fabs(a), std::fabs(b), std::fabs(c)); }
-  static float amax3(float a, float b, float c) { return max3(std::fabs(a), std::fabs(b), std::fabs(c)); }
-  static float med3(float a, float b, float c) { return std::fmax(std::fmin(a, b), std::fmin(std::fmax(a, b), c)); }
-  static float fma(float a, float b, float c) { return std::fma(a, b, c); }
-  static float abs(float a) { return std::fabs(a); }
-  static uint32_t bits(float a) { return B(a); }
-};
-constexpr float kAbove1e8 = 0x1.5798f0p-27f;
-
 struct Box {
   float w[kBoxAAWords];
   float mB;
@@ -106,12 +76,6 @@ bool Pair(const Box& bx, const float o[3], const float d[3], float& t1, float& t
 
 std::mt19937_64 rng;
 float U(float lo, float hi) { return std::uniform_real_distribution<float>(lo, hi)(rng); }
-float Ulps(float x, int n) {  // x moved by n ulps
-  uint32_t b = B(x);
-  if (x == 0.0f) return n == 0 ? x : std::ldexp((float)n, -149);
-  if ((x > 0) == (n > 0)) b += (uint32_t)std::abs(n); else b -= (uint32_t)std::abs(n);
-  return F(b);
-}
 void Dir(float d[3], bool unit) {
   float l;
   do {

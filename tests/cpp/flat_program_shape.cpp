@@ -13,34 +13,18 @@
 // One line per scene: flat, steps, moves of the walk, transforms. Any violation is printed and the exit status
 // is 1.
 // Scenes: the files on the command line, and generated scenes of 2 to 8 BVH leaves (the generator of
-// flat_cert.cpp: walls with shared edges and corners, MakeBox boxes plain and rotated about y, thin boxes,
+// gen_scenes.h: walls with shared edges and corners, MakeBox boxes plain and rotated about y, thin boxes,
 // integer coordinates, far-off coordinates).
-#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <random>
 #include <string>
-#include <vector>
 
-#include "scene.h"
+#include "gen_scenes.h"
 
-using namespace rt2;
+using namespace gen_scenes;
 
 namespace {
-std::mt19937_64 rng;
-float U(float lo, float hi) { return lo + (hi - lo) * (float)((rng() >> 11) * (1.0 / 9007199254740992.0)); }
-
-bool Compile(const std::string& path, CompiledScene& c) {
-  Scene s;
-  std::string err;
-  if (!LoadScene(path, 1, s, err) || !CompileScene(s, c, err)) {
-    fprintf(stderr, "%s: %s\n", path.c_str(), err.c_str());
-    return false;
-  }
-  return true;
-}
-
 struct Shape {
   int moves = 0, xforms = 0, quad_steps = 0;
 };
@@ -99,69 +83,6 @@ bool CheckShape(const CompiledScene& c, const std::string& what, Shape& out) {
   out.xforms = entered;
   return true;
 }
-
-bool WriteFile(const std::string& path, const std::string& text) {
-  FILE* f = fopen(path.c_str(), "w");
-  if (!f) return false;
-  fputs(text.c_str(), f);
-  fclose(f);
-  return true;
-}
-std::string Vec(float x, float y, float z) {
-  char b[128];
-  snprintf(b, sizeof b, "[%.9g, %.9g, %.9g]", x, y, z);
-  return b;
-}
-const char* kHead = "{\"camera\": {\"center\": [0, 0, -10], \"look_at\": [0, 0, 0]}, \"materials\": [{\"type\": "
-                    "\"lambertian\", \"albedo\": [0.5, 0.5, 0.5]}], \"primitives\": [";
-
-// A generated scene of `leaves` BVH leaves around `origin` at scale `sc`: walls on a shared grid of plane
-// coordinates (shared edges and corners), plain boxes, thin boxes, boxes rotated about y.
-std::string GeneratedScene(int leaves, float sc, const float origin[3], bool integer) {
-  std::string prims, nodes;
-  const float grid[4] = {0.0f, 1.0f, 2.0f, 3.0f};
-  for (int i = 0; i < leaves; i++) {
-    const int kind = (int)(rng() % 5);
-    auto co = [&](int k, float g) {
-      float v = origin[k] + sc * g;
-      return integer ? std::round(v) : v;
-    };
-    char buf[512];
-    if (kind <= 1) {  // a wall: one plane coordinate and a rectangle of the grid
-      const int k = (int)(rng() % 3), a = (k + 1) % 3, b = (k + 2) % 3;
-      float q[3], u[3] = {0, 0, 0}, v[3] = {0, 0, 0};
-      const int ga = (int)(rng() % 3), gb = (int)(rng() % 3);
-      q[k] = co(k, grid[rng() % 4]);
-      q[a] = co(a, grid[ga]);
-      q[b] = co(b, grid[gb]);
-      u[a] = co(a, grid[ga + 1 + (int)(rng() % (3 - ga))]) - q[a];
-      v[b] = co(b, grid[gb + 1 + (int)(rng() % (3 - gb))]) - q[b];
-      snprintf(buf, sizeof buf, "{\"type\": \"quad\", \"q\": %s, \"u\": %s, \"v\": %s, \"material\": 0}", Vec(q[0], q[1], q[2]).c_str(),
-               Vec(u[0], u[1], u[2]).c_str(), Vec(v[0], v[1], v[2]).c_str());
-      nodes += std::string(i ? ", " : "") + "{\"primitive\": " + std::to_string(i) + "}";
-    } else {
-      float a[3], e[3];
-      for (int k = 0; k < 3; k++) {
-        a[k] = kind == 4 ? 0.0f : co(k, U(0.0f, 2.0f));
-        e[k] = sc * U(0.2f, 1.0f);
-        if (integer) e[k] = std::round(e[k]) + 1.0f;
-      }
-      if (kind == 3) e[(int)(rng() % 3)] *= 1e-4f;  // thin
-      snprintf(buf, sizeof buf, "{\"type\": \"box\", \"a\": %s, \"b\": %s, \"material\": 0}", Vec(a[0], a[1], a[2]).c_str(),
-               Vec(a[0] + e[0], a[1] + e[1], a[2] + e[2]).c_str());
-      if (kind == 4) {  // unit scale, rotated about y, placed on the grid
-        char tb[256];
-        snprintf(tb, sizeof tb, "{\"primitive\": %d, \"transform\": {\"translation\": %s, \"rotation\": [%.9g, 0, 1, 0]}}", i,
-                 Vec(co(0, U(0.0f, 2.5f)), co(1, U(0.0f, 2.5f)), co(2, U(0.0f, 2.5f))).c_str(), U(-40.0f, 40.0f));
-        nodes += std::string(i ? ", " : "") + tb;
-      } else {
-        nodes += std::string(i ? ", " : "") + "{\"primitive\": " + std::to_string(i) + "}";
-      }
-    }
-    prims += std::string(i ? ", " : "") + buf;
-  }
-  return std::string(kHead) + prims + "], \"scene\": [" + nodes + "]}";
-}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -187,13 +108,9 @@ int main(int argc, char** argv) {
   // generated scenes
   int gen_flat = 0, gen_xforms = 0, gen_moves = 0, gen_steps = 0, leaves_seen = 0;
   for (int g = 0; g < ngen; g++) {
-    const int leaves = 2 + g % 7;
-    const int cls = (g / 7) % 4;
-    const float sc = cls == 0 ? 1.0f : cls == 1 ? 185.0f : cls == 2 ? 555.0f : 1.0f;
-    const float far = cls == 3 ? 16384.0f : (cls == 2 ? 0.0f : U(-4.0f, 4.0f) * sc);
-    const float origin[3] = {far, cls == 3 ? 4096.0f : 0.0f, -far};
+    int leaves;
     const std::string path = dir + "/flat_program_shape_gen.json";
-    if (!WriteFile(path, GeneratedScene(leaves, sc, origin, cls == 2))) return 2;
+    if (!WriteFile(path, GeneratedScene(g, leaves))) return 2;
     CompiledScene c;
     if (!Compile(path, c)) return 2;
     if (c.flat_wide.empty()) continue;

@@ -31,6 +31,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from bits import same_bits
 from conftest import scene_path
 from helpers import SEED
 
@@ -106,17 +107,13 @@ def _unit(v):
     return v / np.sqrt((v * v).sum(-1, keepdims=True))
 
 
-def _same(a, b):
-    return a.tobytes() == b.tobytes()
-
-
 def _bisect(kf, a, b, ka, kb):
     """Float32 vectors a, b with kf(a) = ka != kb = kf(b): one end is replaced by fl(0.5 a + 0.5 b) until that
     midpoint equals an end bit for bit. Every component then differs by at most 1 ulp: a gap of 2 ulps has a float
     in its middle, and a step whose midpoint rounds to a in one component and to b in another closes a component."""
     for _ in range(600):
         m = HALF * a + HALF * b
-        if _same(m, a) or _same(m, b):
+        if same_bits(m, a) or same_bits(m, b):
             return a, b, ka, kb
         km = kf(m)
         if km == ka:

@@ -8,20 +8,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build as H
 import raytrace2_amd as R
 from adaptive_ref import AdaptiveSim, over_flags, window_or
 from conftest import ROOT
 from raytrace2_amd._native import Adaptive
 
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
 
 
-def _build(tmp_path, name, extra=()):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra, "-I", CSRC,
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "adaptive_host.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+def _build(sanitize):
+    return H.program("adaptive_host.cpp", [*H.HOST, *(H.HOST_SAN if sanitize else ())])
 
 
 def _sums(rng, width, kind):
@@ -77,8 +73,7 @@ def _run(exe, tmp_path, rows):
 @pytest.mark.parametrize("sanitize", [False, True])
 def test_retire_rule_matches_the_simulator(tmp_path, sanitize):
     """tests/cpp/adaptive_host.cpp over adaptive.h, plain and with the host sanitizers (a stand-alone program)."""
-    exe = _build(tmp_path, "adaptive_host_san" if sanitize else "adaptive_host",
-                 ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g") if sanitize else ())
+    exe = _build(sanitize)
     rows = _rows()
     got = _run(exe, tmp_path, rows)
     at = 0
@@ -141,9 +136,7 @@ def test_null_arguments_return_invalid():
 
 def test_cpp_mirror_adaptive_members_compile():
     """include/rt2/RayTracer.hpp: EnableAdaptive, SampleCounts, AdaptiveCheck, RenderAdaptive."""
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only",
-                        os.path.join(ROOT, "tests", "cpp", "mirror_adaptive.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.syntax_only("mirror_adaptive.cpp")
 
 
 def test_adaptive_struct_matches_the_header(tmp_path):

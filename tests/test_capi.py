@@ -6,6 +6,7 @@ import subprocess
 
 import pytest
 
+import host_build as H
 import raytrace2_amd as R
 from conftest import ROOT, scene_path
 
@@ -57,25 +58,16 @@ def test_version_string():
 
 def test_cpp_mirror_header_compiles():
     # include/rt2/RayTracer.hpp: the C++ drop-in mirror of cpu::RayTracer over the C ABI
-    src = os.path.join(ROOT, "tests", "cpp", "mirror_compile.cpp")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-fsyntax-only", src], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.syntax_only("mirror_compile.cpp")
 
 
 @pytest.mark.parametrize("scene,expect", [("book2_final_scene_10000_samples", 1), ("final_render_book_1", 1),
                                           ("cornell_box_original", 0)])
-def test_paired_program_steps_are_well_formed(tmp_path, scene, expect):
+def test_paired_program_steps_are_well_formed(scene, expect):
     """compile.cpp's paired BVH / list-tree steps (host only): a paired step precedes its near child,
     carries that child's box and skip index, and no skip index lands on the child; sphere scenes
     pair, the Cornell box does not (its kernel has no second test)."""
-    csrc = os.path.join(ROOT, "raytrace2_amd", "csrc")
-    exe = str(tmp_path / "program_pairs")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", csrc,
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "program_pairs.cpp")]
-                       + [os.path.join(csrc, f) for f in ("json.cpp", "scene.cpp", "compile.cpp")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = H.program("program_pairs.cpp", H.PAIRS, H.COMPILER_SOURCES)
     r = subprocess.run([exe, os.path.join(ROOT, "scenes", scene + ".json"), str(expect)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert r.stdout.startswith("pairs=")
@@ -88,13 +80,7 @@ def test_box_level_test_decides_as_the_six_face_run(tmp_path):
     exactly the six-face run's answer (face and final interval key), and every lane BoxAAPair certifies
     gets exactly the two ConstantMedium boundary queries' answers (t1, t2); the certified fractions are
     printed (tests/cpp/box_cert.cpp)."""
-    csrc = os.path.join(ROOT, "raytrace2_amd", "csrc")
-    exe = str(tmp_path / "box_cert")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                        "-I", csrc, "-o", exe, os.path.join(ROOT, "tests", "cpp", "box_cert.cpp")]
-                       + [os.path.join(csrc, f) for f in ("json.cpp", "scene.cpp", "compile.cpp")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = H.program("box_cert.cpp", H.COMPILER_O2, H.COMPILER_SOURCES)
     for seed in (1, 2):
         r = subprocess.run([exe, "300", "12000", str(seed), str(tmp_path)], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr + r.stdout
@@ -104,18 +90,12 @@ def test_box_level_test_decides_as_the_six_face_run(tmp_path):
         assert cert["enter face"] > 0.9 and cert["inside"] > 0.99, cert
 
 
-def test_quadaa_bounds_decide_as_quad_hit(tmp_path):
+def test_quadaa_bounds_decide_as_quad_hit():
     """compile.cpp CoordRange (host only): the kernel's QUADAA interior test, lo <= p <= hi on the hit
     point's two in-plane coordinates, decides as Quad::Hit's alpha/beta test (Quad.cpp:27-36) for
     random rectangles of every orientation and hit points on, beside and far from the bounds, +-0,
     +-inf and NaN (about 10 M decisions)."""
-    csrc = os.path.join(ROOT, "raytrace2_amd", "csrc")
-    exe = str(tmp_path / "quadaa_bounds")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                        "-I", csrc, "-o", exe, os.path.join(ROOT, "tests", "cpp", "quadaa_bounds.cpp")]
-                       + [os.path.join(csrc, f) for f in ("json.cpp", "scene.cpp", "compile.cpp")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = H.program("quadaa_bounds.cpp", H.COMPILER, H.COMPILER_SOURCES)
     r = subprocess.run([exe, "20000", "7"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr + r.stdout
     assert r.stdout.startswith("rects=")

@@ -20,8 +20,9 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
+import host_build as H
+from host_build import ROOT
+
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "compiled_scene_digests.json")))
 ROWS = ["default", "lists_plain", "flat_bvh=0", "flat_bvh=2", "box_aa=0", "bvh_pairs=0", "acc_octants=0", "acc_sah=0",
         "hit_table=0", "acc_depth_slack=0"]
@@ -40,14 +41,9 @@ def scenes():
 
 
 @pytest.fixture(scope="module")
-def digests(tmp_path_factory):
+def digests():
     """{mode: {scene: {row: {field: text}}}} of both modes"""
-    exe = str(tmp_path_factory.mktemp("digest") / "compile_digest")
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                        "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "cpp", "compile_digest.cpp")]
-                       + [os.path.join(CSRC, f) for f in ("json.cpp", "scene.cpp", "compile.cpp")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = H.program("compile_digest.cpp", H.COMPILER_O2, H.COMPILER_SOURCES)
     out = {}
     env = {k: v for k, v in os.environ.items() if not k.startswith("RT2_")}
     for mode in ("env", "options"):

@@ -12,31 +12,21 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build as H
 import raytrace2_amd as R
+from bits import same_bits
 from conftest import ROOT, scene_path
 from denoise_ref import DEFAULTS, FEATURE_FLOATS, denoise_ref, features_ref, params, synthetic_case, variance_of_sem
 from helpers import SEED, rmse
 from noise_ref import noise_ref
 from raytrace2_amd._native import DenoiseParams
 
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
 F32 = np.float32
 SIZES = [(1, 1), (1, 9), (9, 1), (33, 9), (70, 37)]
 
 
-@functools.lru_cache(maxsize=None)
-def _exe(tmp, sanitize):
-    exe = os.path.join(tmp, "denoise_host_san" if sanitize else "denoise_host")
-    extra = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g") if sanitize else ()
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra, "-I", CSRC,
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "denoise_host.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def build_dir(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("denoise_host"))
+def _exe(sanitize):
+    return H.program("denoise_host.cpp", [*H.HOST, *(H.HOST_SAN if sanitize else ())])
 
 
 def _run(exe, tmp_path, c, v, f, **kw):
@@ -55,30 +45,22 @@ def _run(exe, tmp_path, c, v, f, **kw):
     return out[:3 * w * h].reshape(h, w, 3), out[3 * w * h:].reshape(h, w)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
 @pytest.mark.parametrize("sanitize", [False, True])
-def test_host_program_matches_numpy_bit_for_bit(build_dir, tmp_path, sanitize):
+def test_host_program_matches_numpy_bit_for_bit(tmp_path, sanitize):
     """Every size and iteration count of the GPU test; the sanitized build is its own program."""
-    exe = _exe(build_dir, sanitize)
+    exe = _exe(sanitize)
     for (w, h) in SIZES:
         c, v, f = synthetic_case(w, h)
         for it in ((1, 3, 5, 8) if not sanitize else (5,)):
             rc, rv = denoise_ref(c, v, f, iterations=it)
             gc, gv = _run(exe, tmp_path, c, v, f, iterations=it)
-            assert _same(gc, rc) and _same(gv, rv), (w, h, it)
+            assert same_bits(gc, rc) and same_bits(gv, rv), (w, h, it)
     # other parameters than the defaults
     c, v, f = synthetic_case(33, 9, seed=5)
     kw = dict(iterations=2, normal_power_log2=0, sigma_l=0.5, sigma_p=0.25, sigma_a=2.0, eps_l=0.125)
     rc, rv = denoise_ref(c, v, f, **kw)
     gc, gv = _run(exe, tmp_path, c, v, f, **kw)
-    assert _same(gc, rc) and _same(gv, rv)
+    assert same_bits(gc, rc) and same_bits(gv, rv)
 
 
 def test_synthetic_case_reaches_the_branches():
@@ -91,7 +73,7 @@ def test_synthetic_case_reaches_the_branches():
     fin = np.isfinite(c).all(-1) & np.isfinite(v)
     # no finite input gives a NaN or an inf; the others pass through bit for bit
     assert np.isfinite(rc[fin]).all() and np.isfinite(rv[fin]).all()
-    assert _same(rc[~fin], c[~fin]) and _same(rv[~fin], v[~fin])
+    assert same_bits(rc[~fin], c[~fin]) and same_bits(rv[~fin], v[~fin])
     # the filter does something, and the noisy region's variance shrinks
     assert (rc[fin] != c[fin]).any()
     noisy = fin & (v == F32(1.5))
@@ -113,13 +95,13 @@ def _flat(w, h, value=0.5, var=0.01):
     return c, v, f
 
 
-def test_degenerate_cases(build_dir, tmp_path):
-    exe = _exe(build_dir, False)
+def test_degenerate_cases(tmp_path):
+    exe = _exe(False)
 
     def both(c, v, f, **kw):
         rc, rv = denoise_ref(c, v, f, **kw)
         gc, gv = _run(exe, tmp_path, c, v, f, **kw)
-        assert _same(gc, rc) and _same(gv, rv)
+        assert same_bits(gc, rc) and same_bits(gv, rv)
         return rc, rv
 
     # every neighbour rejected (perpendicular normals all round): the centre comes back bit for bit,
@@ -131,7 +113,7 @@ def test_degenerate_cases(build_dir, tmp_path):
     f[..., 5:8] = [1, 0, 0]
     f[2, 2, 5:8] = [0, 0, 1]
     rc, rv = both(c, v, f, iterations=2)
-    assert _same(rc[2, 2], c[2, 2]) and _same(rv[2, 2], v[2, 2])
+    assert same_bits(rc[2, 2], c[2, 2]) and same_bits(rv[2, 2], v[2, 2])
     # ... and with every neighbour a miss or not finite
     c2, v2, f2 = c.copy(), v.copy(), f.copy()
     f2[..., 5:8] = [0, 0, 1]
@@ -139,10 +121,10 @@ def test_degenerate_cases(build_dir, tmp_path):
     f2[2, 2, 0] = 1
     c2[2, 3] = np.nan
     rc, rv = both(c2, v2, f2, iterations=3)
-    assert _same(rc[2, 2], c2[2, 2]) and _same(rv[2, 2], v2[2, 2])
+    assert same_bits(rc[2, 2], c2[2, 2]) and same_bits(rv[2, 2], v2[2, 2])
     # a 1x1 image: nothing to average
     rc, rv = both(c[:1, :1], v[:1, :1], f[:1, :1], iterations=8)
-    assert _same(rc, c[:1, :1]) and _same(rv, v[:1, :1])
+    assert same_bits(rc, c[:1, :1]) and same_bits(rv, v[:1, :1])
     # dist == 0: wp = 1, no 0 / 0; with equal colours everywhere the image stays finite and equal
     c, v, f = _flat(6, 4)
     f[..., 13] = 0
@@ -165,7 +147,7 @@ def test_degenerate_cases(build_dir, tmp_path):
     rc, rv = both(c, v, f, iterations=4)
     fin = np.isfinite(c).all(-1) & np.isfinite(v)
     assert np.isfinite(rc[fin]).all() and np.isfinite(rv[fin]).all()
-    assert _same(rc[~fin], c[~fin]) and _same(rv[~fin], v[~fin])
+    assert same_bits(rc[~fin], c[~fin]) and same_bits(rv[~fin], v[~fin])
     # huge finite colours whose luminances overflow: the luminance weight is 0, no NaN
     c, v, f = _flat(4, 3)
     c[1, 1] = 3e38
@@ -252,9 +234,7 @@ def test_argument_checks_return_invalid():
 
 def test_cpp_mirror_denoise_members_compile():
     """include/rt2/RayTracer.hpp: DenoiseDefaults, Features, Denoise."""
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only",
-                        os.path.join(ROOT, "tests", "cpp", "mirror_denoise.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.syntax_only("mirror_denoise.cpp")
 
 
 def test_params_struct_matches_the_header(tmp_path):

@@ -9,37 +9,20 @@ stand-alone, plainly and with ASan + UBSan.
 Cases, drawn as tests/cpp/flat_cert.cpp draws them: the committed scenes that get a flat program at 60,000 rays
 each, generated scenes of 2 to 8 BVH leaves, the four-leaf scene."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
-SAN = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+import host_build as H
+from host_build import ROOT, SAN
+
 FLAT_SCENES = ["cornell_box_original", "cornell_box1", "cornell_box2", "quad_scene1"]
 
 
 @pytest.mark.parametrize("flags,rays,generated", [([], 60000, 56), (SAN, 6000, 28)], ids=["plain", "asan_ubsan"])
 def test_one_lazy_rule_decides_what_the_entry_and_end_rules_decided(tmp_path, flags, rays, generated):
-    exe = str(tmp_path / "flat_cert_once")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *flags, "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", "-I", CSRC, "-o", exe,
-                        os.path.join(ROOT, "tests", "cpp", "flat_cert_once.cpp")]
-                       + [os.path.join(CSRC, f) for f in ("json.cpp", "scene.cpp", "compile.cpp")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    env.pop("RT2_FLAT_BVH", None)
+    exe = H.program("flat_cert_once.cpp", [*H.COMPILER, *flags], H.COMPILER_SOURCES)
     scenes = [os.path.join(ROOT, "scenes", n + ".json") for n in FLAT_SCENES]
-    r = subprocess.run([exe, str(tmp_path), "1", str(rays), str(generated), *scenes], capture_output=True, text=True,
-                       env=env, timeout=900)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    got = {}
-    for line in r.stdout.splitlines():
-        f = line.split()
-        got[f[0]] = {k: int(v) for k, v in (x.split("=") for x in f[1:])}
+    got = H.parse(H.run(exe, [str(tmp_path), "1", str(rays), str(generated), *scenes], 900, drop=["RT2_FLAT_BVH"]))
     assert set(got) == {"scene:" + n + ".json" for n in FLAT_SCENES} | {"generated", "four_leaf"}, sorted(got)
     # 0 disagreements, every scene walked
     for k, v in got.items():

@@ -9,13 +9,12 @@ Cases: the committed scenes (those that qualify get a flat program, the others n
 to 8 BVH leaves (the generator of tests/cpp/flat_cert.cpp)."""
 import glob
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
-SAN = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+import host_build as H
+from host_build import ROOT, SAN
+
 QUALIFY = {"cornell_box_original", "cornell_box1", "cornell_box2", "quad_scene1", "cornell_original_10000_samples"}
 
 
@@ -27,24 +26,8 @@ def scenes():
 
 @pytest.mark.parametrize("flags,generated", [([], 112), (SAN, 56)], ids=["plain", "asan_ubsan"])
 def test_no_flat_program_step_sends_lanes_to_different_places(tmp_path, flags, generated):
-    exe = str(tmp_path / "flat_program_shape")
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *flags, "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", "-I", CSRC, "-o", exe,
-                        os.path.join(ROOT, "tests", "cpp", "flat_program_shape.cpp")]
-                       + [os.path.join(CSRC, f) for f in ("json.cpp", "scene.cpp", "compile.cpp")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    env.pop("RT2_FLAT_BVH", None)
-    r = subprocess.run([exe, str(tmp_path), "1", str(generated), *scenes()], capture_output=True, text=True, env=env,
-                       timeout=600)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    got = {}
-    for line in r.stdout.splitlines():
-        f = line.split()
-        got[f[0]] = {k: int(v) for k, v in (x.split("=") for x in f[1:])}
+    exe = H.program("flat_program_shape.cpp", [*H.COMPILER, *flags], H.COMPILER_SOURCES)
+    got = H.parse(H.run(exe, [str(tmp_path), "1", str(generated), *scenes()], 600, drop=["RT2_FLAT_BVH"]))
     # which committed scenes qualify: every one of them was checked
     flat = {k[len("scene:"):-len(".json")] for k, v in got.items() if k.startswith("scene:") and v["flat"]}
     assert flat == QUALIFY, flat

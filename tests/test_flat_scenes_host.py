@@ -14,20 +14,16 @@ needs them to be. No GPU.
 
 D as measured here (the oracle is deterministic, so these are properties of the scene files):
 mix 170, eight 254 (199 at max_depth 2), nine 253, nonuni 96, norot 95, side 191, metal 188, two 0."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import flat_scenes as S
+import host_build as H
 import raytrace2_amd as R
 from helpers import SEED
+from host_build import SAN
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
-SAN = ["-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 # flat_cert's `steps` per scene: what the product's compiler gives these files
 STEPS = {"mix": 35, "eight": 43, "nine": 0, "nonuni": 27, "norot": 19, "side": 35, "metal": 35, "two": 16}
 
@@ -107,24 +103,9 @@ def test_the_product_loader_gives_each_scene_its_program(name, monkeypatch):
 
 
 def _run(tmp_path, source, flags, rays, names):
-    exe = str(tmp_path / source)
-    r = subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *flags, "-D__HIP_PLATFORM_AMD__",
-                        "-I/opt/rocm/include", "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "cpp", source + ".cpp")]
-                       + [os.path.join(CSRC, f) for f in ("json.cpp", "scene.cpp", "compile.cpp")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    env.pop("RT2_FLAT_BVH", None)
-    r = subprocess.run([exe, str(tmp_path), "1", str(rays), "0", *[S.scene_file(n) for n in names]],
-                       capture_output=True, text=True, env=env, timeout=900)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    got = {}
-    for line in r.stdout.splitlines():
-        f = line.split()
-        got[f[0]] = {k: int(v) for k, v in (x.split("=") for x in f[1:])}
-    return got
+    exe = H.program(source + ".cpp", [*H.COMPILER, *flags], H.COMPILER_SOURCES)
+    return H.parse(H.run(exe, [str(tmp_path), "1", str(rays), "0", *[S.scene_file(n) for n in names]], 900,
+                         drop=["RT2_FLAT_BVH"]))
 
 
 @pytest.mark.parametrize("flags,rays", [([], 60000), (SAN, 6000)], ids=["plain", "asan_ubsan"])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from adaptive_ref import AdaptiveSim, margin, pixel_noise
+from bits import f32_bits, refused
 from conftest import ROOT, scene_path
 from helpers import SEED
 
@@ -71,10 +72,6 @@ def _preconditions(name, window):
     assert min(h["margin"] for h in hist) >= 1e-9
 
 
-def _bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
 def _tracer(name, *, adaptive=True, ray_counts=False):
     import raytrace2_amd as R
     sc = R.Scene(scene_path(name), SEED)
@@ -92,8 +89,8 @@ def _tracer(name, *, adaptive=True, ray_counts=False):
 
 def _assert_state(tr, sim, what=""):
     assert np.array_equal(tr.sample_counts(), sim.n), f"sample counts differ {what}"
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(sim.a)), f"accumulation differs {what}"
-    assert np.array_equal(_bits(tr.moments()), _bits(sim.q)), f"moments differ {what}"
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(sim.a)), f"accumulation differs {what}"
+    assert np.array_equal(f32_bits(tr.moments()), f32_bits(sim.q)), f"moments differ {what}"
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -182,7 +179,7 @@ def test_partition(have_gpu):
     full, _ = _reference(name)
     sim, ref = _reference(name, THR, 1, rows)
     # the window runs along the row: a partition decides as the full image does
-    assert np.array_equal(sim.n, full.n[list(rows)]) and np.array_equal(_bits(sim.a), _bits(full.a[list(rows)]))
+    assert np.array_equal(sim.n, full.n[list(rows)]) and np.array_equal(f32_bits(sim.a), f32_bits(full.a[list(rows)]))
     assert 0 < ref["active"] < len(rows) * W
     sc, tr = _tracer(name)
     tr.set_partition(2, 1, 3)
@@ -214,11 +211,11 @@ def test_readbacks_use_each_pixels_count(have_gpu):
     sc, tr = _tracer(name)
     tr.render_adaptive(THR, MAXF, check_every=STEP)
     mean = sim.a / sim.n.astype(np.float32)[..., None]
-    assert np.array_equal(_bits(tr.NonConvertedPixels()), _bits(mean))
+    assert np.array_equal(f32_bits(tr.NonConvertedPixels()), f32_bits(mean))
     px = tr.Pixels()
     expect = np.floor(np.clip(mean, 0, 1).astype(np.float64) * 255.999).astype(np.uint8)
     assert np.array_equal(px[..., :3], expect) and np.all(px[..., 3] == 255)
-    assert np.array_equal(_bits(tr.standard_error()), _bits(sem))
+    assert np.array_equal(f32_bits(tr.standard_error()), f32_bits(sem))
     # (every pixel of this scene has retired, so all are below THR: count against a lower threshold)
     thr = float(np.float32(0.02))
     below = int((err[finite] <= np.float64(np.float32(thr))).sum())
@@ -240,7 +237,8 @@ def test_edges(have_gpu):
     acc, mom, cnt, launches = tr.Accumulation(), tr.moments(), tr.sample_counts(), tr.stats()["launches"]
     tr.Render(16)  # nothing to trace: the frame index advances, nothing else moves
     assert tr.FrameIdx() == 2 * STEP
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(acc)) and np.array_equal(_bits(tr.moments()), _bits(mom))
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(acc))
+    assert np.array_equal(f32_bits(tr.moments()), f32_bits(mom))
     assert np.array_equal(tr.sample_counts(), cnt) and (cnt == STEP).all()
     assert tr.stats()["launches"] == launches
     # threshold 0: only pixels whose estimate is exactly 0, with such neighbours, retire
@@ -280,21 +278,15 @@ def test_off_path_is_untouched(have_gpu):
     tr.enable_adaptive(False)
     assert tr.FrameIdx() == 0
     tr.Render(13)
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(o_acc))
-    assert np.array_equal(_bits(tr.NonConvertedPixels()), _bits(o_acc / np.float32(13)))
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(o_acc))
+    assert np.array_equal(f32_bits(tr.NonConvertedPixels()), f32_bits(o_acc / np.float32(13)))
     tr.close()
 
 
 def test_refusals(have_gpu):
     import raytrace2_amd as R
-    from raytrace2_amd import Rt2Error
     name = "cornell_box_original"
     s, _ = _frames(name)
-
-    def refused(call):
-        with pytest.raises(Rt2Error) as e:
-            call()
-        assert e.value.code == -1
 
     sc = R.Scene(scene_path(name), SEED)
     tr = R.RayTracer(sc, 0)
@@ -325,7 +317,7 @@ def test_refusals(have_gpu):
     a = np.zeros((H, W, 3), np.float32)
     for f in range(13):
         a = a + s[f]
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(a)) and (tr.sample_counts() == 13).all()
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(a)) and (tr.sample_counts() == 13).all()
     tr.close()
 
 
@@ -347,13 +339,6 @@ def _sum13(rows=None):
     return a if rows is None else a[rows]
 
 
-def _refused(call):
-    from raytrace2_amd import Rt2Error
-    with pytest.raises(Rt2Error) as e:
-        call()
-    assert e.value.code == -1
-
-
 def test_joined_tracer_is_refused_and_adaptive_tracer_cannot_join(have_gpu):
     """One process per GPU (rt2_tracer_join), world 1 on this GPU: a joined tracer refuses enable_adaptive, an
     adaptive tracer refuses join; both still render afterwards."""
@@ -362,17 +347,17 @@ def test_joined_tracer_is_refused_and_adaptive_tracer_cannot_join(have_gpu):
     sc, tr = _plain_tracer()
     tr.join(R.comm_unique_id(), 1, 0, 16)
     tr.enable_moments()
-    _refused(tr.enable_adaptive)
-    _refused(tr.sample_counts)  # adaptive stayed off
+    refused(tr.enable_adaptive)
+    refused(tr.sample_counts)  # adaptive stayed off
     tr.Render(13)
-    assert tr.FrameIdx() == 13 and np.array_equal(_bits(tr.Accumulation()), _bits(_sum13(local_rows(H, 16, 0, 1))))
+    assert tr.FrameIdx() == 13 and np.array_equal(f32_bits(tr.Accumulation()), f32_bits(_sum13(local_rows(H, 16, 0, 1))))
     tr.close()
     sc, tr = _plain_tracer()
     tr.enable_moments()
     tr.enable_adaptive()
-    _refused(lambda: tr.join(R.comm_unique_id(), 1, 0, 16))
+    refused(lambda: tr.join(R.comm_unique_id(), 1, 0, 16))
     tr.Render(13)  # still adaptive, unpartitioned, every pixel active
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(_sum13())) and (tr.sample_counts() == 13).all()
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(_sum13())) and (tr.sample_counts() == 13).all()
     assert tr.adaptive_check(THR, 1)["pixels"] == NPIX
     tr.close()
 
@@ -384,10 +369,10 @@ def test_tracer_without_the_threaded_traversal_is_refused(have_gpu, monkeypatch)
     sc, tr = _plain_tracer()
     monkeypatch.delenv("RT2_NO_LINEAR")
     tr.enable_moments()
-    _refused(tr.enable_adaptive)
+    refused(tr.enable_adaptive)
     tr.enable_adaptive(False)  # switching it off is always allowed
     tr.Render(13)
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(_sum13()))
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(_sum13()))
     assert tr.noise()["frames"] == 13
     tr.close()
 

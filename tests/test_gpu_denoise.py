@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import refused, same_bits
 from conftest import ROOT, scene_path
 from denoise_ref import denoise_ref, features_ref, synthetic_case, variance_of_sem
 from helpers import SEED
@@ -20,14 +21,6 @@ W, H, SPP, FRAMES = 70, 37, 16, 16
 F32 = np.float32
 SCENES = ["cornell_box_original", "final_render_book_1", "cornell_box_volume"]
 APP = os.path.join(ROOT, "raytrace2_amd", "lib", "rt2_headless")
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
 
 
 def _tracer(name, *, moments=False, **kw):
@@ -61,9 +54,9 @@ def _assert_features(got, ref, flagged, what):
     hit = ref[..., 0] == 1
     assert np.array_equal(got[..., 0], ref[..., 0]), f"hit flags differ {what}"
     assert hit.any()
-    assert _same(got[hit][:, 0:10], ref[hit][:, 0:10]), f"hit records differ {what}"
-    assert _same(got[..., 13], ref[..., 13]), f"dist differs {what}"
-    assert _same(got[~flagged][:, 10:13], ref[~flagged][:, 10:13]), f"albedo differs {what}"
+    assert same_bits(got[hit][:, 0:10], ref[hit][:, 0:10]), f"hit records differ {what}"
+    assert same_bits(got[..., 13], ref[..., 13]), f"dist differs {what}"
+    assert same_bits(got[~flagged][:, 10:13], ref[~flagged][:, 10:13]), f"albedo differs {what}"
     assert (got[~hit][:, 1:10] == 0).all() and (got[..., 14:16] == 0).all()
 
 
@@ -74,19 +67,19 @@ def test_features_match_the_oracle(have_gpu, name):
     ref, flagged = _features_ref(name)
     sc, tr = _tracer(name)
     ocp = _oracle(name).camera_params(W, H, SPP)
-    assert _same(sc.camera_params(W, H, SPP), ocp)  # the rays are built from camera_params' words
+    assert same_bits(sc.camera_params(W, H, SPP), ocp)  # the rays are built from camera_params' words
     if name == "final_render_book_1":
         assert ocp[18] > 0  # defocus_angle
     got = tr.features()
     assert got.shape == (H, W, 16)
     _assert_features(got, ref, flagged, name)
     assert not flagged.any() and (ref[..., 0] == 0).any()
-    assert _same(tr.features(), got)  # the cached buffer
+    assert same_bits(tr.features(), got)  # the cached buffer
     assert tr.denoise_times()["features_ms"] > 0
     # the tracer still renders what it rendered
     tr.Render(3)
     acc, _, _ = _oracle(name).render(W, H, SPP, 3, forward=True)
-    assert _same(tr.Accumulation(), acc)
+    assert same_bits(tr.Accumulation(), acc)
     tr.close()
 
 
@@ -115,7 +108,7 @@ def test_features_under_a_partition(have_gpu):
     tr.set_partition(2, 1, 3)
     part = tr.features()
     assert part.shape == (len(rows), W, 16)
-    assert _same(part, full[rows])
+    assert same_bits(part, full[rows])
     _assert_features(part, ref[rows], flagged[rows], "partition")
     tr.close()
 
@@ -129,7 +122,7 @@ def test_features_follow_the_camera(have_gpu):
     cam.vfov = cam.vfov + 5.0
     tr.set_camera(cam)
     after = tr.features()
-    assert not _same(before, after)
+    assert not same_bits(before, after)
     from oracle.oracle import OracleScene
     o = OracleScene(scene_path(name), SEED)
     o.set_camera(cam.center, cam.look_at, cam.view_up, cam.vfov, cam.defocus_angle, cam.focus_distance)
@@ -137,7 +130,7 @@ def test_features_follow_the_camera(have_gpu):
     _assert_features(after, ref, flagged, "moved camera")
     # a new seed keys the medium's stream: the buffer is traced again (same records in a scene without media)
     tr.set_seed(SEED + 7)
-    assert _same(tr.features(), after)
+    assert same_bits(tr.features(), after)
     tr.close()
 
 
@@ -150,10 +143,10 @@ def test_denoise_buffers_match_numpy_bit_for_bit(have_gpu, size):
     for it in (1, 3, 5, 8):
         rc, rv = denoise_ref(c, v, f, iterations=it)
         gc, gv = R.denoise_buffers(c, v, f, iterations=it)
-        assert _same(gc, rc), (size, it, "colour")
-        assert _same(gv, rv), (size, it, "variance")
+        assert same_bits(gc, rc), (size, it, "colour")
+        assert same_bits(gv, rv), (size, it, "variance")
     gc2, gv2 = R.denoise_buffers(c, v, f, iterations=8)
-    assert _same(gc2, gc) and _same(gv2, gv)  # the same call twice: the same bytes
+    assert same_bits(gc2, gc) and same_bits(gv2, gv)  # the same call twice: the same bytes
 
 
 def test_denoise_buffers_lds_and_direct_paths_agree(have_gpu, monkeypatch):
@@ -166,7 +159,7 @@ def test_denoise_buffers_lds_and_direct_paths_agree(have_gpu, monkeypatch):
     for lds in ("1", "0"):
         monkeypatch.setenv("RT2_DENOISE_LDS", lds)
         gc, gv = R.denoise_buffers(c, v, f, **kw)
-        assert _same(gc, rc) and _same(gv, rv), f"RT2_DENOISE_LDS={lds}"
+        assert same_bits(gc, rc) and same_bits(gv, rv), f"RT2_DENOISE_LDS={lds}"
 
 
 # ---- tracer.denoise() ----------------------------------------------------------------------------------------
@@ -194,19 +187,20 @@ def test_tracer_denoise_matches_numpy_on_the_oracle_sums(have_gpu):
     tr.Render(FRAMES)
     state = (tr.Accumulation(), tr.moments(), tr.FrameIdx())
     gc, gv = tr.denoise(variance=True)
-    assert _same(gc, rc) and _same(gv, rv)
-    assert _same(tr.denoise(), rc)
+    assert same_bits(gc, rc) and same_bits(gv, rv)
+    assert same_bits(tr.denoise(), rc)
     bc, bv = R.denoise_buffers(tr.NonConvertedPixels(), variance_of_sem(tr.standard_error()), tr.features())
-    assert _same(bc, gc) and _same(bv, gv)
+    assert same_bits(bc, gc) and same_bits(bv, gv)
     assert tr.denoise_times()["denoise_ms"] > 0
     # other parameters reach the kernel
     kw = dict(iterations=2, sigma_l=3.0)
-    assert _same(tr.denoise(**kw), denoise_ref(a / F32(FRAMES), variance_of_sem(sem), feat, **kw)[0])
+    assert same_bits(tr.denoise(**kw), denoise_ref(a / F32(FRAMES), variance_of_sem(sem), feat, **kw)[0])
     # the call changed nothing: the sums, the frame index, and what rendering on gives
-    assert _same(tr.Accumulation(), state[0]) and _same(tr.moments(), state[1]) and tr.FrameIdx() == state[2] == FRAMES
+    assert same_bits(tr.Accumulation(), state[0]) and same_bits(tr.moments(), state[1])
+    assert tr.FrameIdx() == state[2] == FRAMES
     tr.Render(5)
     acc, _, _ = _oracle(name).render(W, H, SPP, FRAMES + 5, forward=True)
-    assert _same(tr.Accumulation(), acc)
+    assert same_bits(tr.Accumulation(), acc)
     tr.close()
 
 
@@ -222,33 +216,26 @@ def test_tracer_denoise_with_adaptive_sampling(have_gpu):
     assert len(np.unique(n)) > 1 and out["frames"] == 48
     state = (tr.Accumulation(), tr.moments(), n, tr.FrameIdx())
     c = tr.NonConvertedPixels()
-    assert _same(c, state[0] / n[..., None].astype(F32))
+    assert same_bits(c, state[0] / n[..., None].astype(F32))
     v = variance_of_sem(tr.standard_error())
     feat, _ = _features_ref(name)
     rc, rv = denoise_ref(c, v, feat)
     gc, gv = tr.denoise(variance=True)
-    assert _same(gc, rc) and _same(gv, rv)
+    assert same_bits(gc, rc) and same_bits(gv, rv)
     bc, bv = R.denoise_buffers(c, v, tr.features())
-    assert _same(bc, gc) and _same(bv, gv)
-    assert _same(tr.Accumulation(), state[0]) and _same(tr.moments(), state[1])
+    assert same_bits(bc, gc) and same_bits(bv, gv)
+    assert same_bits(tr.Accumulation(), state[0]) and same_bits(tr.moments(), state[1])
     assert np.array_equal(tr.sample_counts(), state[2]) and tr.FrameIdx() == state[3]
     tr.close()
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------
-def _refused(call):
-    from raytrace2_amd import Rt2Error
-    with pytest.raises(Rt2Error) as e:
-        call()
-    assert e.value.code == -1
-
-
 def _renders(tr, frames, rows=None):
     """The tracer still renders: `frames` frames from a reset give the oracle's sums."""
     tr.Reset()
     tr.Render(frames)
     acc, _, _ = _oracle("cornell_box_original").render(W, H, SPP, frames, forward=True)
-    assert _same(tr.Accumulation(), acc if rows is None else acc[rows])
+    assert same_bits(tr.Accumulation(), acc if rows is None else acc[rows])
 
 
 def test_refusals(have_gpu):
@@ -259,18 +246,18 @@ def test_refusals(have_gpu):
     # moments off
     sc, tr = _tracer(name)
     tr.Render(4)
-    _refused(tr.denoise)
+    refused(tr.denoise)
     _renders(tr, 3)
     # fewer than 2 frames
     tr.enable_moments()
-    _refused(tr.denoise)
+    refused(tr.denoise)
     tr.Render(1)
-    _refused(tr.denoise)
+    refused(tr.denoise)
     # bad parameters, NULL outputs
     tr.Render(3)
     for kw in (dict(iterations=0), dict(iterations=9), dict(normal_power_log2=-1), dict(normal_power_log2=9),
                dict(sigma_l=0.0), dict(sigma_p=float("nan")), dict(sigma_a=float("inf")), dict(eps_l=-1.0)):
-        _refused(lambda: tr.denoise(**kw))
+        refused(lambda: tr.denoise(**kw))
     assert R.lib.rt2_tracer_denoise(tr._h, None, None, None) == -1
     assert R.lib.rt2_tracer_features(tr._h, None) == -1
     buf = (ctypes.c_float * 16)()
@@ -280,7 +267,7 @@ def test_refusals(have_gpu):
     # a partitioned tracer: features work, denoise does not
     tr.set_partition(2, 1, 3)
     tr.Render(4)
-    _refused(tr.denoise)
+    refused(tr.denoise)
     rows = local_rows(H, 2, 1, 3)
     assert tr.features().shape == (len(rows), W, 16)
     _renders(tr, 3, rows)
@@ -288,8 +275,8 @@ def test_refusals(have_gpu):
     # a multi tracer over one GPU twice
     sc, multi = _tracer(name, moments=True, devices=[0, 0], band_h=2)
     multi.Render(4)
-    _refused(multi.denoise)
-    _refused(multi.features)
+    refused(multi.denoise)
+    refused(multi.features)
     _renders(multi, 3)
     multi.close()
     # a joined world-1 tracer
@@ -297,8 +284,8 @@ def test_refusals(have_gpu):
     tr.join(R.comm_unique_id(), 1, 0, 16)
     tr.enable_moments()
     tr.Render(4)
-    _refused(tr.denoise)
-    _refused(tr.features)
+    refused(tr.denoise)
+    refused(tr.features)
     _renders(tr, 3)
     tr.close()
 

@@ -13,10 +13,11 @@ import numpy as np
 import pytest
 
 import edge_rays as E
+from bits import f32_bits
 from conftest import ROOT
 from helpers import SEED
 from test_gpu_parity import MODES
-from test_gpu_query import _assert_records, _bits, _expect, _tracer
+from test_gpu_query import _assert_records, _expect, _tracer
 
 pytestmark = pytest.mark.gpu
 REF = os.path.join(ROOT, "tests", "golden", "ref")
@@ -49,7 +50,7 @@ def _describe(name, what, b, got, exp, bad):
 
 
 def _check(name, what, b, got, exp):
-    bad = np.flatnonzero((_bits(got) != _bits(exp)).any(-1))
+    bad = np.flatnonzero((f32_bits(got) != f32_bits(exp)).any(-1))
     if bad.size:
         pytest.fail(_describe(name, what, b, got, exp, bad))
     _assert_records(got, exp, f"{name} {what}")
@@ -94,7 +95,7 @@ def test_against_the_reference(have_gpu, monkeypatch, name, mode):
     sc, tr = _tracer(E.scene_file(name))
     got = tr.intersect(rays)[:, :10]
     tr.close()
-    bad = np.flatnonzero((_bits(got) != _bits(ref)).any(-1))
+    bad = np.flatnonzero((f32_bits(got) != f32_bits(ref)).any(-1))
     assert bad.size == 0, (f"{name} {mode}: {bad.size} of {len(fx)} records differ from the reference; first: ray "
                            f"{bad[0]} {rays[bad[0]].tolist()}\n  kernel    {got[bad[0]].tolist()}\n  reference {ref[bad[0]].tolist()}")
 

@@ -9,10 +9,10 @@ RT2_FLAT_BVH=2 and the number of hits: neither the oracle nor the counting kerne
 takes them from the flat kernel's own count of the hits its falling-back wave-bounces end with (all hits
 under RT2_FLAT_BVH=2, counted from the final hit flags after the second trace) and bounds them from
 outside: a path casts at most one ray that misses, so rays - paths <= hits <= rays."""
-import numpy as np
 import pytest
 
 import raytrace2_amd as R
+from bits import same_bits
 from conftest import scene_path
 from helpers import SEED, oracle_render
 
@@ -33,10 +33,6 @@ def render(path, w, h, spp, frames, *, stats=False):
     variant = tr.last_launch()["variant"]
     tr.close()
     return sc.info(), acc, st, variant
-
-
-def same_bits(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 _oracle = {}

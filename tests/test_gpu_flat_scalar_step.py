@@ -11,10 +11,10 @@ The number of hits under RT2_FLAT_BVH=2: neither the oracle nor the counting ker
 test_gpu_flat_bvh.py, it is the flat kernel's own count of the hits its falling-back wave-bounces end with
 (every wave-bounce with a hit, when nothing is certified), bounded from outside by rays - paths <= hits <=
 rays (a path casts at most one ray that misses)."""
-import numpy as np
 import pytest
 
 import raytrace2_amd as R
+from bits import same_bits
 from conftest import scene_path
 from helpers import SEED, oracle_render
 from raytrace2_amd.tracer import local_rows
@@ -40,10 +40,6 @@ def render(name, w, h, spp, frames, *, max_depth=50, partition=None):
     variant = tr.last_launch()["variant"]
     tr.close()
     return sc.info(), acc, st, variant
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 @pytest.mark.parametrize("max_depth", [50, 2])

@@ -11,16 +11,13 @@ oracle(frames k..n | start = GPU(frames 0..k)) must equal GPU(frames 0..n) bit f
 import numpy as np
 import pytest
 
+from bits import same_bits
 from conftest import scene_path
 from helpers import SEED, gpu_render, oracle_render
 
 pytestmark = pytest.mark.gpu
 
 THREADS = 16  # the GPU box's CPU share
-
-
-def _same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def _check(name, w, h, spp, frames, **kw):
@@ -47,7 +44,7 @@ def _check_continuation(name, w, h, spp, k, n, launch=None, **part):
     o_rc = np.zeros_like(rc_k)
     o.render(w, h, spp, n - k, frame_begin=k, accum=o_acc, ray_counts=o_rc, forward=True, threads=THREADS, **part)
     np.testing.assert_array_equal(rc_n - rc_k, o_rc)
-    assert _same(a_n, o_acc)
+    assert same_bits(a_n, o_acc)
     return st_n
 
 
@@ -135,7 +132,7 @@ def test_spp20_sq2_below_spp_frames_wrap(split):
     acc, rc = _check("cornell_box_original", 72, 40, 20, 40, work_split=split)
     if split:
         acc0, _, _, _ = gpu_render("cornell_box_original", 72, 40, 20, 40, work_split=0)
-        assert _same(acc, acc0)
+        assert same_bits(acc, acc0)
 
 
 def test_frames_beyond_sq2_in_several_launches():

@@ -9,10 +9,10 @@ transforms. A metal or dielectric material, a checker or noise texture, a sphere
 another kernel variant (rt2_layout.h Feature), none of which reads the table, so those kinds cannot
 reach this path; the kinds that can (lambertian, diffuse light and texture materials over solid
 textures, under a transform or not, QUADAA and general quads) are all in the authored scenes below."""
-import numpy as np
 import pytest
 
 import raytrace2_amd as R
+from bits import same_bits
 from conftest import scene_path
 from helpers import SEED, oracle_render
 from raytrace2_amd import authoring as A
@@ -35,10 +35,6 @@ def render(path, w, h, spp, frames, *, stats=False):
     variant = tr.last_launch()["variant"]
     tr.close()
     return sc.info(), acc, st, variant
-
-
-def same_bits(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def test_cornell_box_from_the_table_changes_no_bit(have_gpu, monkeypatch):

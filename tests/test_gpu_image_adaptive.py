@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import refused, same_bits
 from conftest import ROOT, scene_path
 from denoise_ref import variance_of_sem
 from helpers import SEED
@@ -26,21 +27,6 @@ NAME = "cornell_box_original"
 F32 = np.float32
 APP = os.path.join(ROOT, "raytrace2_amd", "lib", "rt2_headless")
 FIELDS = ("pixels", "active", "retired", "samples", "nonfinite")
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _refused(call):
-    from raytrace2_amd import Rt2Error
-    with pytest.raises(Rt2Error) as e:
-        call()
-    assert e.value.code == -1
 
 
 def _tracer(name=NAME, *, moments=True, **kw):
@@ -100,9 +86,9 @@ def _plain13():
 
 def _assert_gathered(tr, ref, what=""):
     """The gathered image's readbacks against the plain tracer's state."""
-    assert _same(tr.image_accumulation(), ref["acc"]), f"image_accumulation {what}"
+    assert same_bits(tr.image_accumulation(), ref["acc"]), f"image_accumulation {what}"
     assert np.array_equal(tr.image_sample_counts(), ref["n"]), f"image_sample_counts {what}"
-    assert _same(tr.image_non_converted_pixels(), ref["nc"]), f"image_non_converted_pixels {what}"
+    assert same_bits(tr.image_non_converted_pixels(), ref["nc"]), f"image_non_converted_pixels {what}"
     assert np.array_equal(tr.image_pixels(), ref["px"]), f"image_pixels {what}"
 
 
@@ -115,11 +101,11 @@ def _whole_run(name, n, band_h):
     tr.gather()
     _assert_gathered(tr, ref, (name, n, band_h))
     # the multi tracer's own readbacks
-    assert _same(tr.Accumulation(), ref["acc"])
-    assert _same(tr.NonConvertedPixels(), ref["nc"])
+    assert same_bits(tr.Accumulation(), ref["acc"])
+    assert same_bits(tr.NonConvertedPixels(), ref["nc"])
     assert np.array_equal(tr.Pixels(), ref["px"])
-    assert _same(tr.moments(), ref["mom"])
-    assert _same(tr.standard_error(), ref["sem"])
+    assert same_bits(tr.moments(), ref["mom"])
+    assert same_bits(tr.standard_error(), ref["sem"])
     tr.close()
 
 
@@ -145,7 +131,7 @@ def test_check_sums_the_parts_and_waits_once_per_part(have_gpu):
     for t in (tr, plain):
         t.Render(STEP)
     tr.flush()
-    _refused(lambda: tr.image_part_adaptive(0))  # no check yet
+    refused(lambda: tr.image_part_adaptive(0))  # no check yet
     w0 = tr.stats()["host_waits"]
     out = tr.image_adaptive_check(THR, 1)
     w1 = tr.stats()["host_waits"]
@@ -156,8 +142,8 @@ def test_check_sums_the_parts_and_waits_once_per_part(have_gpu):
     for f in FIELDS:
         assert sum(p[f] for p in parts) == out[f], f
     assert all(p["frames"] == STEP for p in parts) and [p["pixels"] for p in parts] == [W * 8] * n
-    _refused(lambda: tr.image_part_adaptive(n))
-    _refused(lambda: tr.image_part_adaptive(-1))
+    refused(lambda: tr.image_part_adaptive(n))
+    refused(lambda: tr.image_part_adaptive(-1))
     tr.close()
     plain.close()
 
@@ -179,11 +165,11 @@ def test_estimate_and_reconstruction(have_gpu):
     assert multi.image_render_adaptive(THR, 48, check_every=STEP) == ref_out
     assert 0 < ref_out["active"] < NPIX and plain.noise()["nonfinite"] == 0
     multi.gather_estimate()
-    assert _same(multi.image_variance(), variance_of_sem(plain.standard_error()))
+    assert same_bits(multi.image_variance(), variance_of_sem(plain.standard_error()))
     _assert_gathered(multi, _state(plain), "estimate")
     dn = plain.denoise(variance=True)
     got = multi.image_resolve(temporal=0, variance=True)
-    assert _same(got[0], dn[0]) and _same(got[1], dn[1])
+    assert same_bits(got[0], dn[0]) and same_bits(got[1], dn[1])
     assert np.array_equal(multi.image_present(temporal=0, denoise=0), plain.Pixels())
     # the blend's length is each pixel's own count
     c, v, ln = multi.image_resolve(temporal=1, denoise=0, variance=True, length=True)
@@ -212,13 +198,13 @@ def test_joined_world_1(have_gpu):
     assert out == ref["out"] and tr.image_part_adaptive(0) == out
     tr.gather_estimate()
     _assert_gathered(tr, ref, "joined")
-    assert _same(tr.image_variance(), variance_of_sem(ref["sem"]))
-    assert _same(tr.Accumulation(), ref["acc"]) and _same(tr.NonConvertedPixels(), ref["nc"])
+    assert same_bits(tr.image_variance(), variance_of_sem(ref["sem"]))
+    assert same_bits(tr.Accumulation(), ref["acc"]) and same_bits(tr.NonConvertedPixels(), ref["nc"])
     assert np.array_equal(tr.image_present(temporal=0, denoise=0), ref["px"])
     # the section above keeps its refusals on a joined tracer
-    _refused(tr.sample_counts)
-    _refused(lambda: tr.adaptive_check(THR))
-    _refused(lambda: tr.render_adaptive(THR, MAXF))
+    refused(tr.sample_counts)
+    refused(lambda: tr.adaptive_check(THR))
+    refused(lambda: tr.render_adaptive(THR, MAXF))
     tr.close()
 
 
@@ -235,8 +221,8 @@ def test_everything_retired(have_gpu):
     tr.Render(16)  # nothing to trace: the frame index advances
     assert tr.FrameIdx() == 2 * STEP and tr.stats()["launches"] == launches
     tr.gather()  # a new gather, at frame index 32: the means are still sums / 16
-    assert _same(tr.image_non_converted_pixels(), nc16) and (tr.image_sample_counts() == STEP).all()
-    assert _same(tr.NonConvertedPixels(), nc16)
+    assert same_bits(tr.image_non_converted_pixels(), nc16) and (tr.image_sample_counts() == STEP).all()
+    assert same_bits(tr.NonConvertedPixels(), nc16)
     tr.close()
 
 
@@ -249,7 +235,7 @@ def test_reset_reactivates_and_reproduces(have_gpu):
     _assert_gathered(tr, ref, "first run")
     tr.Reset()
     assert tr.FrameIdx() == 0
-    _refused(tr.image_sample_counts)  # the reset dropped the gathered image
+    refused(tr.image_sample_counts)  # the reset dropped the gathered image
     tr.Render(2)
     assert tr.image_adaptive_check(0.0, 64)["pixels"] == NPIX
     tr.gather()
@@ -259,7 +245,7 @@ def test_reset_reactivates_and_reproduces(have_gpu):
     assert first == second == ref["out"]
     tr.gather()
     _assert_gathered(tr, ref, "second run")
-    assert _same(tr.moments(), ref["mom"])
+    assert same_bits(tr.moments(), ref["mom"])
     tr.close()
 
 
@@ -272,10 +258,10 @@ def test_switching_it_off(have_gpu):
     assert tr.FrameIdx() == 0
     tr.Render(13)
     tr.gather()
-    assert _same(tr.image_accumulation(), acc)
-    assert _same(tr.image_non_converted_pixels(), acc / F32(13)) and _same(tr.NonConvertedPixels(), acc / F32(13))
-    _refused(tr.image_sample_counts)
-    _refused(lambda: tr.image_adaptive_check(THR))
+    assert same_bits(tr.image_accumulation(), acc)
+    assert same_bits(tr.image_non_converted_pixels(), acc / F32(13)) and same_bits(tr.NonConvertedPixels(), acc / F32(13))
+    refused(tr.image_sample_counts)
+    refused(lambda: tr.image_adaptive_check(THR))
     tr.close()
 
 
@@ -286,25 +272,25 @@ def test_refusals(have_gpu):
     from raytrace2_amd._native import Adaptive
     lib = R.lib
     sc, tr = _tracer(moments=False, devices=[0, 0, 0], band_h=2)
-    _refused(tr.image_enable_adaptive)  # moments off
+    refused(tr.image_enable_adaptive)  # moments off
     tr.enable_moments()
     tr.Render(2)
     for call in (lambda: tr.image_adaptive_check(THR), lambda: tr.image_render_adaptive(THR, 16), tr.image_sample_counts,
                  lambda: tr.image_part_adaptive(0)):
-        _refused(call)  # not switched on
+        refused(call)  # not switched on
     assert tr.FrameIdx() == 2
     tr.image_enable_adaptive()
-    _refused(tr.image_sample_counts)  # before a gather
+    refused(tr.image_sample_counts)  # before a gather
     tr.Render(1)
-    _refused(lambda: tr.image_adaptive_check(THR))  # one frame
+    refused(lambda: tr.image_adaptive_check(THR))  # one frame
     assert tr.FrameIdx() == 1
     tr.Render(1)
     for window in (-1, 65):
-        _refused(lambda: tr.image_adaptive_check(THR, window))
-        _refused(lambda: tr.image_render_adaptive(THR, 16, window=window))
+        refused(lambda: tr.image_adaptive_check(THR, window))
+        refused(lambda: tr.image_render_adaptive(THR, 16, window=window))
     for thr in (-1.0, float("nan")):
-        _refused(lambda: tr.image_adaptive_check(thr))
-        _refused(lambda: tr.image_render_adaptive(thr, 16))
+        refused(lambda: tr.image_adaptive_check(thr))
+        refused(lambda: tr.image_render_adaptive(thr, 16))
     a = Adaptive()
     assert lib.rt2_tracer_image_adaptive_check(tr._h, THR, 1, None) == -1
     assert lib.rt2_tracer_image_render_adaptive(tr._h, THR, 1, 0, 16, 0, None) == -1
@@ -315,36 +301,36 @@ def test_refusals(have_gpu):
     assert tr.FrameIdx() == 2
     tr.Render(11)
     tr.gather()
-    assert _same(tr.image_accumulation(), _plain13()) and (tr.image_sample_counts() == 13).all()
+    assert same_bits(tr.image_accumulation(), _plain13()) and (tr.image_sample_counts() == 13).all()
     tr.close()
     # a partition that is not joined has no communicator to gather over
     sc, tr = _tracer()
     tr.set_partition(2, 1, 3)
-    _refused(tr.image_enable_adaptive)
-    _refused(lambda: tr.image_adaptive_check(THR))
+    refused(tr.image_enable_adaptive)
+    refused(lambda: tr.image_adaptive_check(THR))
     tr.Render(13)
-    assert _same(tr.Accumulation(), _plain13()[R.local_rows(H, 2, 1, 3)])
+    assert same_bits(tr.Accumulation(), _plain13()[R.local_rows(H, 2, 1, 3)])
     tr.close()
 
 
 # ---- 10. the refusals other files pin, restated ----------------------------------------------------------------------
 def test_the_old_calls_keep_their_refusals(have_gpu):
     sc, multi = _tracer(devices=[0, 0], band_h=2)
-    _refused(multi.enable_adaptive)
+    refused(multi.enable_adaptive)
     multi.image_enable_adaptive()
-    _refused(multi.enable_adaptive)
-    _refused(multi.sample_counts)
-    _refused(lambda: multi.adaptive_check(THR))
-    _refused(lambda: multi.render_adaptive(THR, 16))
+    refused(multi.enable_adaptive)
+    refused(multi.sample_counts)
+    refused(lambda: multi.adaptive_check(THR))
+    refused(lambda: multi.render_adaptive(THR, 16))
     multi.close()
     sc, tr = _tracer()
     tr.enable_adaptive()  # the old call: no counts in the gather
     tr.Render(4)
-    _refused(tr.gather_estimate)
-    _refused(tr.image_resolve)
-    _refused(tr.image_present)
-    _refused(lambda: tr.image_move_camera(tr.get_camera()))
-    _refused(lambda: tr.image_adaptive_check(THR))
+    refused(tr.gather_estimate)
+    refused(tr.image_resolve)
+    refused(tr.image_present)
+    refused(lambda: tr.image_move_camera(tr.get_camera()))
+    refused(lambda: tr.image_adaptive_check(THR))
     assert tr.FrameIdx() == 4 and (tr.sample_counts() == 4).all()
     # the new call on the same plain tracer: its gathers carry the counts, and the old family still works
     tr.image_enable_adaptive()
@@ -356,7 +342,7 @@ def test_the_old_calls_keep_their_refusals(have_gpu):
     # and the old call again takes the counts out of the gather
     tr.enable_adaptive()
     tr.Render(4)
-    _refused(tr.gather_estimate)
+    refused(tr.gather_estimate)
     tr.close()
 
 

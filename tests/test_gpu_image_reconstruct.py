@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import refused, same_bits
 from conftest import ROOT, scene_path
 from denoise_ref import variance_of_sem
 from helpers import SEED
@@ -25,16 +26,8 @@ APP = os.path.join(ROOT, "raytrace2_amd", "lib", "rt2_headless")
 DN3 = dict(iterations=3, sigma_l=2.0)  # a filter off its defaults
 
 
-def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
 def _all_same(got, ref):
-    return len(got) == len(ref) and all(_same(g, r) for g, r in zip(got, ref))
+    return len(got) == len(ref) and all(same_bits(g, r) for g, r in zip(got, ref))
 
 
 def _tracer(name=NAME, size=(W, H), *, moments=True, **kw):
@@ -74,13 +67,6 @@ def _plain(size=(W, H)):
     return ref
 
 
-def _refused(call):
-    from raytrace2_amd import Rt2Error
-    with pytest.raises(Rt2Error) as e:
-        call()
-    assert e.value.code == -1
-
-
 def _renders(tr, frames, ref_rows=None):
     """The tracer still renders: `frames` frames from a reset give the plain tracer's sums."""
     sc, plain = _tracer(moments=False)
@@ -89,7 +75,7 @@ def _renders(tr, frames, ref_rows=None):
     plain.close()
     tr.Reset()
     tr.Render(frames)
-    assert _same(tr.Accumulation(), acc if ref_rows is None else acc[ref_rows])
+    assert same_bits(tr.Accumulation(), acc if ref_rows is None else acc[ref_rows])
 
 
 # ---- 3. the gather's kernel: image, means, pixels and variance over the band layouts ------------------------------
@@ -102,15 +88,15 @@ def test_gather_estimate_matches_one_gpu(have_gpu, n, band_h, size):
     sc, tr = _tracer(size=size, devices=[0] * n, band_h=band_h)
     tr.Render(FRAMES)
     tr.gather_estimate()
-    assert _same(tr.image_accumulation(), ref["acc"])
-    assert _same(tr.image_non_converted_pixels(), ref["nc"])
+    assert same_bits(tr.image_accumulation(), ref["acc"])
+    assert same_bits(tr.image_non_converted_pixels(), ref["nc"])
     assert np.array_equal(tr.image_pixels(), ref["px"])
     var = tr.image_variance()
-    assert var.shape == (size[1], size[0]) and _same(var, ref["var"])
+    assert var.shape == (size[1], size[0]) and same_bits(var, ref["var"])
     assert (var > 0).any()
     # a plain gather afterwards leaves the same image, and the estimate stays readable
     tr.gather()
-    assert _same(tr.image_non_converted_pixels(), ref["nc"]) and _same(tr.image_variance(), ref["var"])
+    assert same_bits(tr.image_non_converted_pixels(), ref["nc"]) and same_bits(tr.image_variance(), ref["var"])
     tr.close()
 
 
@@ -119,7 +105,7 @@ def test_gather_estimate_on_a_plain_tracer(have_gpu):
     sc, tr = _tracer()
     tr.Render(FRAMES)
     tr.gather_estimate()
-    assert _same(tr.image_accumulation(), ref["acc"]) and _same(tr.image_variance(), ref["var"])
+    assert same_bits(tr.image_accumulation(), ref["acc"]) and same_bits(tr.image_variance(), ref["var"])
     assert np.array_equal(tr.image_pixels(), ref["px"])
     tr.close()
 
@@ -135,12 +121,12 @@ def test_image_features_match_one_gpu(have_gpu, name):
         for t in (plain, multi):
             t.set_camera(_moved(cam, step))
         got, ref = multi.image_features(), plain.features()
-        assert got.shape == (H, W, 16) and _same(got, ref), (name, step)
+        assert got.shape == (H, W, 16) and same_bits(got, ref), (name, step)
         assert (ref[..., 0] == 1).any()
         if step == 0:
             first = ref
-            assert _same(multi.image_features(), ref)  # the cached records
-    assert not _same(first, ref), "the move changes the records"
+            assert same_bits(multi.image_features(), ref)  # the cached records
+    assert not same_bits(first, ref), "the move changes the records"
     plain.close()
     multi.close()
 
@@ -154,15 +140,15 @@ def test_image_resolve_is_denoise(have_gpu, n):
     # no gather_estimate before: all ranks are in this process, the call gathers
     assert _all_same(tr.image_resolve(temporal=0, denoise=1, variance=True), ref["dn"])
     assert _all_same(tr.image_resolve(temporal=0, denoise=1, variance=True, dp=DN3), ref["dn3"])
-    assert not _same(ref["dn"][0], ref["dn3"][0])
+    assert not same_bits(ref["dn"][0], ref["dn3"][0])
     assert _all_same(tr.image_resolve(temporal=0, denoise=0, variance=True), (ref["nc"], ref["var"]))
     # length is left untouched with temporal off; with it on and no history the current estimate comes back
     c, v, ln = tr.image_resolve(temporal=0, denoise=0, variance=True, length=True)
     assert (ln == 0).all()
     c, v, ln = tr.image_resolve(temporal=1, denoise=0, variance=True, length=True)
-    assert _same(c, ref["nc"]) and _same(v, ref["var"]) and (ln == FRAMES).all()
+    assert same_bits(c, ref["nc"]) and same_bits(v, ref["var"]) and (ln == FRAMES).all()
     assert _all_same(tr.image_resolve(variance=True), ref["dn"])  # the defaults: both on, no history held
-    assert tr.FrameIdx() == FRAMES and _same(tr.Accumulation(), ref["acc"])
+    assert tr.FrameIdx() == FRAMES and same_bits(tr.Accumulation(), ref["acc"])
     tr.close()
 
 
@@ -196,7 +182,7 @@ def test_image_move_camera_carries_the_history(have_gpu):
     got = same_after(8, True)
     assert (got[2] > 8 + 8).any(), "lengths past both renders since the first move: the first history is carried"
     # invalid temporal parameters: refused, nothing moves
-    _refused(lambda: multi.image_move_camera(cam, max_history=0.0))
+    refused(lambda: multi.image_move_camera(cam, max_history=0.0))
     assert multi.FrameIdx() == 8
     # a resize drops the history
     multi.OnResize((W, H))
@@ -216,7 +202,7 @@ def test_image_move_camera_carries_the_history(have_gpu):
     plain.Reset()
     for t in (plain, multi):
         t.Render(3)
-    assert multi.FrameIdx() == 3 and _same(multi.Accumulation(), plain.Accumulation())
+    assert multi.FrameIdx() == 3 and same_bits(multi.Accumulation(), plain.Accumulation())
     plain.close()
     multi.close()
 
@@ -300,18 +286,18 @@ def test_joined_tracer_needs_its_gather_estimate(have_gpu):
     tr.join(R.comm_unique_id(), 1, 0, 16)  # bands of 16 rows at height 37: the stacks carry padding rows
     tr.enable_moments()
     tr.Render(FRAMES)
-    _refused(tr.image_resolve)  # no estimate yet
-    _refused(tr.image_present)
-    _refused(tr.image_variance)
+    refused(tr.image_resolve)  # no estimate yet
+    refused(tr.image_present)
+    refused(tr.image_variance)
     tr.gather_estimate()
-    assert _same(tr.image_variance(), ref["var"])
+    assert same_bits(tr.image_variance(), ref["var"])
     assert _all_same(tr.image_resolve(temporal=0, denoise=1, variance=True), ref["dn"])
     assert _all_same(tr.image_resolve(variance=True), ref["dn"])
     for key, px in ref["present"].items():
         assert np.array_equal(tr.image_present(temporal=key[0], denoise=key[1]), px), key
     tr.Render(4)
-    _refused(tr.image_resolve)  # stale: frames since the gather
-    _refused(tr.image_present)
+    refused(tr.image_resolve)  # stale: frames since the gather
+    refused(tr.image_present)
     assert tr.FrameIdx() == FRAMES + 4
     tr.gather_estimate()
     assert tr.image_resolve().shape == (H, W, 3)
@@ -340,17 +326,17 @@ def test_refusals(have_gpu):
     u8 = ctypes.POINTER(ctypes.c_uint8)
 
     def estimate_refused(tr):
-        _refused(tr.gather_estimate)
-        _refused(tr.image_resolve)
-        _refused(tr.image_present)
-        _refused(lambda: tr.image_present_async(buf.array))
+        refused(tr.gather_estimate)
+        refused(tr.image_resolve)
+        refused(tr.image_present)
+        refused(lambda: tr.image_present_async(buf.array))
 
     # moments off
     sc, multi = _tracer(moments=False, devices=[0, 0], band_h=2)
     cam = multi.get_camera()
     multi.Render(4)
     estimate_refused(multi)
-    _refused(multi.image_variance)
+    refused(multi.image_variance)
     assert multi.image_features().shape == (H, W, 16)  # needs neither moments nor a gather
     _renders(multi, 3)
     # fewer than 2 frames
@@ -371,24 +357,24 @@ def test_refusals(have_gpu):
     assert lib.rt2_tracer_image_move_camera(multi._h, None, None) == -1
     for kw in (dict(dp=dict(iterations=0)), dict(dp=dict(sigma_l=0.0)), dict(tp=dict(max_history=0.0)),
                dict(tp=dict(min_normal_dot=float("nan")))):
-        _refused(lambda: multi.image_resolve(**kw))
-        _refused(lambda: multi.image_present(**kw))
-        _refused(lambda: multi.image_present_async(buf.array, **kw))
-    _refused(lambda: multi.image_move_camera(cam, sigma_p=-1.0))
-    assert multi.FrameIdx() == 4 and _same(multi.Accumulation(), acc)
+        refused(lambda: multi.image_resolve(**kw))
+        refused(lambda: multi.image_present(**kw))
+        refused(lambda: multi.image_present_async(buf.array, **kw))
+    refused(lambda: multi.image_move_camera(cam, sigma_p=-1.0))
+    assert multi.FrameIdx() == 4 and same_bits(multi.Accumulation(), acc)
     assert np.array_equal(multi.image_present(denoise=0, dp=dict(iterations=0)), multi.image_present(denoise=0))
-    assert _same(multi.image_resolve(temporal=0, tp=dict(max_history=0.0)), multi.image_resolve(temporal=0))
+    assert same_bits(multi.image_resolve(temporal=0, tp=dict(max_history=0.0)), multi.image_resolve(temporal=0))
     with pytest.raises(TypeError):
         multi.image_resolve(iterations=3)
     # the existing calls keep their refusals on the same tracer
-    _refused(multi.denoise)
-    _refused(multi.features)
-    _refused(multi.temporal_resolve)
-    _refused(multi.temporal_push)
-    _refused(multi.present)
-    _refused(multi.present_time)
-    _refused(lambda: multi.move_camera(cam))
-    _refused(multi.enable_adaptive)
+    refused(multi.denoise)
+    refused(multi.features)
+    refused(multi.temporal_resolve)
+    refused(multi.temporal_push)
+    refused(multi.present)
+    refused(multi.present_time)
+    refused(lambda: multi.move_camera(cam))
+    refused(multi.enable_adaptive)
     _renders(multi, 3)
     multi.close()
     # a joined tracer keeps them too
@@ -396,10 +382,10 @@ def test_refusals(have_gpu):
     tr.join(R.comm_unique_id(), 1, 0, 16)
     tr.enable_moments()
     tr.Render(4)
-    _refused(tr.denoise)
-    _refused(tr.present)
-    _refused(lambda: tr.move_camera(cam))
-    _refused(tr.enable_adaptive)
+    refused(tr.denoise)
+    refused(tr.present)
+    refused(lambda: tr.move_camera(cam))
+    refused(tr.enable_adaptive)
     _renders(tr, 3)
     tr.close()
     # a plain tracer with adaptive sampling on
@@ -407,7 +393,7 @@ def test_refusals(have_gpu):
     tr.enable_adaptive()
     tr.Render(4)
     estimate_refused(tr)
-    _refused(lambda: tr.image_move_camera(cam))
+    refused(lambda: tr.image_move_camera(cam))
     assert tr.FrameIdx() == 4
     assert tr.present().shape == (H, W, 4)  # its own chain works as before
     tr.enable_adaptive(False)
@@ -415,11 +401,11 @@ def test_refusals(have_gpu):
     # a partition that is not joined: as gather refuses it; rank 1 holds no image either
     tr.set_partition(2, 1, 3)
     tr.Render(4)
-    _refused(tr.gather)
+    refused(tr.gather)
     estimate_refused(tr)
-    _refused(tr.image_features)
-    _refused(tr.image_present_time)
-    _refused(lambda: tr.image_move_camera(cam))
+    refused(tr.image_features)
+    refused(tr.image_present_time)
+    refused(lambda: tr.image_move_camera(cam))
     assert lib.rt2_tracer_image_present_async(tr._h, None, buf.array.ctypes.data_as(u8)) == -1
     assert tr.FrameIdx() == 4
     _renders(tr, 3, local_rows(H, 2, 1, 3))

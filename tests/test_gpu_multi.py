@@ -13,6 +13,7 @@ by tests/test_dist.py.
 import numpy as np
 import pytest
 
+from bits import same_bits
 from conftest import scene_path
 from helpers import SEED
 
@@ -59,18 +60,14 @@ def _multi(name, w, h, spp, frames, *, devices, band_h=8, counts=True, updates=F
     return acc, px, rc, st, ncp
 
 
-def _same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def test_one_gpu_through_rccl_is_bit_identical():
     """A communicator of size 1: ncclGather + de-interleave reproduce the plain render bit for bit."""
     w, h, spp, frames = 61, 47, 16, 6
     acc, px, rc, st = _plain("cornell_box_volume", w, h, spp, frames)
     macc, mpx, mrc, mst, ncp = _multi("cornell_box_volume", w, h, spp, frames, devices=[0], band_h=16)
-    assert _same(macc, acc) and np.array_equal(mpx, px) and np.array_equal(mrc, rc)
+    assert same_bits(macc, acc) and np.array_equal(mpx, px) and np.array_equal(mrc, rc)
     assert mst["rays"] == st["rays"] and mst["gathers"] >= 1 and mst["gather_ms"] > 0
-    assert _same(ncp, acc / np.float32(frames))
+    assert same_bits(ncp, acc / np.float32(frames))
 
 
 @pytest.mark.parametrize("n,band_h", [(2, 8), (3, 8), (8, 4), (8, 16), (4, 1), (5, 2), (3, 5)])
@@ -80,7 +77,7 @@ def test_partitions_on_one_gpu_reassemble(n, band_h):
     acc, px, rc, st = _plain("cornell_box_original", w, h, spp, frames)
     macc, mpx, mrc, mst, _ = _multi("cornell_box_original", w, h, spp, frames, devices=[0] * n, band_h=band_h,
                                     updates=(n == 3))
-    assert _same(macc, acc)
+    assert same_bits(macc, acc)
     assert np.array_equal(mpx, px)
     assert np.array_equal(mrc, rc)
     assert mst["rays"] == st["rays"] and mst["paths"] == st["paths"]
@@ -91,7 +88,7 @@ def test_more_partitions_than_bands():
     w, h = 33, 10
     acc, px, rc, _ = _plain("cornell_box_original", w, h, 16, 3)
     macc, mpx, mrc, _, _ = _multi("cornell_box_original", w, h, 16, 3, devices=[0] * 4, band_h=8)
-    assert _same(macc, acc) and np.array_equal(mpx, px) and np.array_equal(mrc, rc)
+    assert same_bits(macc, acc) and np.array_equal(mpx, px) and np.array_equal(mrc, rc)
 
 
 def test_multi_reset_resize_and_explicit_gather():
@@ -109,7 +106,7 @@ def test_multi_reset_resize_and_explicit_gather():
     img = tr.image_accumulation()
     assert img.shape == (24, 40, 3)
     acc, px, _, _ = _plain("cornell_box_original", 40, 24, 16, 3, counts=False)
-    assert _same(img, acc) and np.array_equal(tr.image_pixels(), px)
+    assert same_bits(img, acc) and np.array_equal(tr.image_pixels(), px)
     with pytest.raises(R.Rt2Error):
         tr.set_partition(8, 0, 2)  # a multi tracer partitions itself
     tr.close()
@@ -132,9 +129,9 @@ def test_join_world_one(h):
     with pytest.raises(R.Rt2Error):
         tr.image_accumulation()  # nothing gathered yet
     tr.gather()
-    assert _same(tr.image_accumulation(), acc)
+    assert same_bits(tr.image_accumulation(), acc)
     assert np.array_equal(tr.image_pixels(), px)
-    assert _same(tr.image_non_converted_pixels(), acc / np.float32(frames))
+    assert same_bits(tr.image_non_converted_pixels(), acc / np.float32(frames))
     tr.close()
 
 
@@ -172,7 +169,7 @@ def test_camera_moved_between_updates_matches_oracle():
         o.render(w, h, spp, n, frame_begin=f, accum=o_acc, ray_counts=o_rc, forward=True)
         f += n
     np.testing.assert_array_equal(rc, o_rc)
-    assert _same(acc, o_acc)
+    assert same_bits(acc, o_acc)
 
 
 def test_camera_setter_on_multi_tracer():
@@ -191,7 +188,7 @@ def test_camera_setter_on_multi_tracer():
         outs.append(tr.Accumulation())
         assert tr.get_camera() == cam_b
         tr.close()
-    assert _same(outs[0], outs[1])
+    assert same_bits(outs[0], outs[1])
 
 
 def test_partitions_with_frame_tiles(monkeypatch):
@@ -201,7 +198,7 @@ def test_partitions_with_frame_tiles(monkeypatch):
     w, h, spp, frames = 50, 45, 16, 70
     acc, px, rc, st = _plain("cornell_box_original", w, h, spp, frames)
     macc, mpx, mrc, mst, _ = _multi("cornell_box_original", w, h, spp, frames, devices=[0] * 3, band_h=2)
-    assert _same(macc, acc) and np.array_equal(mpx, px) and np.array_equal(mrc, rc)
+    assert same_bits(macc, acc) and np.array_equal(mpx, px) and np.array_equal(mrc, rc)
     assert mst["rays"] == st["rays"]
 
 
@@ -245,6 +242,6 @@ def test_multi_launch_render_does_not_block_the_host():
     # it is reported, not asserted)
     print(f"flush() host time {host_s * 1e3:.2f} ms for {mst['kernel_ms']:.1f} ms of GPU work, busy after "
           f"flush: {busy_after_flush} (informational)")
-    assert _same(tr.Accumulation(), acc) and np.array_equal(tr.Pixels(), px)
+    assert same_bits(tr.Accumulation(), acc) and np.array_equal(tr.Pixels(), px)
     assert mst["rays"] == st["rays"]
     tr.close()

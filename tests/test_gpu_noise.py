@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import f32_bits
 from conftest import ROOT, scene_path
 from helpers import SEED
 from noise_ref import noise_ref, scalars_ref, ss_unclamped
@@ -53,10 +54,6 @@ def _sums(name, frames):
     a.setflags(write=False)
     q.setflags(write=False)
     return a, q
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
 
 
 def _tracer(name, *, moments=True, devices=None, band_h=0):
@@ -122,9 +119,9 @@ def test_moments_are_bit_exact(have_gpu, name, pattern):
         tr.close()
     (acc_on, mom), (acc_off, _) = out
     assert acc_on.shape == (len(rows), W, 3)
-    assert np.array_equal(_bits(mom), _bits(q[rows])), "moment2 differs from the oracle's frame-order sum"
-    assert np.array_equal(_bits(acc_on), _bits(a[rows]))
-    assert np.array_equal(_bits(acc_on), _bits(acc_off)), "moments changed the accumulation"
+    assert np.array_equal(f32_bits(mom), f32_bits(q[rows])), "moment2 differs from the oracle's frame-order sum"
+    assert np.array_equal(f32_bits(acc_on), f32_bits(a[rows]))
+    assert np.array_equal(f32_bits(acc_on), f32_bits(acc_off)), "moments changed the accumulation"
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -141,8 +138,8 @@ def test_standard_error_is_bit_exact(have_gpu, name):
     got = tr.standard_error()
     again = tr.standard_error()
     tr.close()
-    assert np.array_equal(_bits(got), _bits(sem))
-    assert np.array_equal(_bits(got), _bits(again))
+    assert np.array_equal(f32_bits(got), f32_bits(sem))
+    assert np.array_equal(f32_bits(got), f32_bits(again))
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -193,7 +190,7 @@ def test_noise_errors(have_gpu):
     assert tr.moments().shape == (H, W, 3)
     tr.Render(FRAMES - 1)  # the tracer still renders
     assert tr.FrameIdx() == FRAMES
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(a))
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(a))
     assert tr.noise()["frames"] == FRAMES
     tr.enable_moments(False)
     assert tr.FrameIdx() == 0
@@ -224,7 +221,7 @@ def test_render_until_stops_at_the_target(have_gpu):
     out = tr.render_until(target, 80)  # check_every 0: one sweep of the 4 x 4 strata = 16 frames
     print("render_until:", out)
     assert tr.FrameIdx() == 48 and out["frames"] == 48
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(a48))
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(a48))
     assert out["nonfinite"] == 0 and out["pixels"] == NPIX
     assert _within(out["sum_sq"], rms[48]["sum_sq"]) and _rms_ok(out["rms"], rms[48]["sum_sq"], NPIX)
     # an accumulation already begun is continued: the next sweep is checked at 64 frames, still converged
@@ -241,8 +238,8 @@ def test_render_until_target_zero_runs_to_max_frames(have_gpu, max_frames):
     sc, tr = _tracer("cornell_box_original")
     out = tr.render_until(0.0, max_frames)
     assert tr.FrameIdx() == max_frames and out["frames"] == max_frames  # 70: a shortened last step
-    assert np.array_equal(_bits(tr.Accumulation()), _bits(a))
-    assert np.array_equal(_bits(tr.moments()), _bits(q))
+    assert np.array_equal(f32_bits(tr.Accumulation()), f32_bits(a))
+    assert np.array_equal(f32_bits(tr.moments()), f32_bits(q))
     assert _within(out["sum_sq"], ref["sum_sq"]) and out["rms"] > 0
     # min_frames above max_frames: no check on the way, the estimate of the final image
     tr.Reset()
@@ -287,9 +284,10 @@ def test_multi_gpu_noise(have_gpu):
     mom, se, nz = tr.moments(), tr.standard_error(), tr.noise(thr)
     acc = tr.Accumulation()
     tr.close()
-    assert mom.shape == (H, W, 3) and np.array_equal(_bits(mom), _bits(one_mom)) and np.array_equal(_bits(mom), _bits(q))
-    assert np.array_equal(_bits(se), _bits(one_sem)) and np.array_equal(_bits(se), _bits(sem))
-    assert np.array_equal(_bits(acc), _bits(a))
+    assert mom.shape == (H, W, 3) and np.array_equal(f32_bits(mom), f32_bits(one_mom))
+    assert np.array_equal(f32_bits(mom), f32_bits(q))
+    assert np.array_equal(f32_bits(se), f32_bits(one_sem)) and np.array_equal(f32_bits(se), f32_bits(sem))
+    assert np.array_equal(f32_bits(acc), f32_bits(a))
     for k in ("frames", "pixels", "below", "nonfinite", "max_err"):
         assert nz[k] == one_nz[k], k
     assert (nz["pixels"], nz["below"], nz["nonfinite"]) == (ref["pixels"], ref["below"], ref["nonfinite"])

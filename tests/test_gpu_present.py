@@ -9,6 +9,7 @@ import dataclasses
 import numpy as np
 import pytest
 
+from bits import refused, same_bits
 from conftest import scene_path
 from helpers import SEED
 from present_ref import EDGE_BYTES, edge_cases, edge_image, present
@@ -20,14 +21,6 @@ NAME = "cornell_box_original"
 F32 = np.float32
 # adaptive sampling's threshold in the tests: loose enough that a check after a few frames retires pixels
 ADAPTIVE_THRESHOLD = 0.5
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
 
 
 def _tracer(*, moments=True, adaptive=False, **kw):
@@ -95,7 +88,7 @@ def _state(tr):
 
 
 def _untouched(tr, state):
-    return _same(tr.Accumulation(), state[0]) and _same(tr.moments(), state[1]) and tr.FrameIdx() == state[2]
+    return same_bits(tr.Accumulation(), state[0]) and same_bits(tr.moments(), state[1]) and tr.FrameIdx() == state[2]
 
 
 def _blocking(tr, temporal, denoise):
@@ -176,7 +169,7 @@ def test_present_async_launches_the_queued_frames(have_gpu):
     assert waits == _waits_across(twin, queued_then_flush)
     assert tr.FrameIdx() == twin.FrameIdx() == AFTER + 3
     assert np.array_equal(buf.array, twin.present())
-    assert _same(tr.Accumulation(), twin.Accumulation())
+    assert same_bits(tr.Accumulation(), twin.Accumulation())
     buf.close()
     tr.close()
     twin.close()
@@ -221,8 +214,8 @@ def test_move_camera_is_push_set_camera_reset_without_a_wait(have_gpu):
         for dn in (False, True):
             got = tr.temporal_resolve(denoise=dn, variance=True, length=True)
             ref = twin.temporal_resolve(denoise=dn, variance=True, length=True)
-            assert all(_same(g, r) for g, r in zip(got, ref)), dn
-        assert _same(tr.Accumulation(), twin.Accumulation()) and _same(tr.moments(), twin.moments())
+            assert all(same_bits(g, r) for g, r in zip(got, ref)), dn
+        assert same_bits(tr.Accumulation(), twin.Accumulation()) and same_bits(tr.moments(), twin.moments())
         assert bool((got[2] > tr.FrameIdx()).any()) == history
         assert np.array_equal(tr.present(), twin.present())
 
@@ -256,7 +249,7 @@ def test_move_camera_is_push_set_camera_reset_without_a_wait(have_gpu):
     twin.Reset()
     for t in (tr, twin):
         t.Render(3)
-    assert tr.FrameIdx() == 3 and _same(tr.Accumulation(), twin.Accumulation())
+    assert tr.FrameIdx() == 3 and same_bits(tr.Accumulation(), twin.Accumulation())
     tr.close()
     twin.close()
 
@@ -288,20 +281,13 @@ def test_present_time_polls_and_never_waits(have_gpu):
 
 
 # ---- 8. refusals ----------------------------------------------------------------------------------------------------------
-def _refused(call):
-    from raytrace2_amd import Rt2Error
-    with pytest.raises(Rt2Error) as e:
-        call()
-    assert e.value.code == -1
-
-
 def _renders(tr, frames, rows=None):
     """The tracer still renders: `frames` frames from a reset give the oracle's sums."""
     from oracle.oracle import OracleScene
     tr.Reset()
     tr.Render(frames)
     acc, _, _ = OracleScene(scene_path(NAME), SEED).render(W, H, SPP, frames, forward=True)
-    assert _same(tr.Accumulation(), acc if rows is None else acc[rows])
+    assert same_bits(tr.Accumulation(), acc if rows is None else acc[rows])
 
 
 def test_refusals(have_gpu):
@@ -311,8 +297,8 @@ def test_refusals(have_gpu):
     buf = PinnedBuffer((H, W, 4))
 
     def both_refused(tr):
-        _refused(tr.present)
-        _refused(lambda: tr.present_async(buf.array))
+        refused(tr.present)
+        refused(lambda: tr.present_async(buf.array))
 
     # moments off
     sc, tr = _tracer(moments=False)
@@ -332,9 +318,9 @@ def test_refusals(have_gpu):
     assert R.lib.rt2_tracer_present(tr._h, None, None) == -1
     assert R.lib.rt2_tracer_present_async(tr._h, None, None) == -1
     assert R.lib.rt2_tracer_move_camera(tr._h, None, None) == -1
-    _refused(lambda: tr.present(dp=dict(iterations=0)))
-    _refused(lambda: tr.present_async(buf.array, dp=dict(iterations=0)))
-    _refused(lambda: tr.present(tp=dict(max_history=0.0)))
+    refused(lambda: tr.present(dp=dict(iterations=0)))
+    refused(lambda: tr.present_async(buf.array, dp=dict(iterations=0)))
+    refused(lambda: tr.present(tp=dict(max_history=0.0)))
     assert _untouched(tr, state)
     assert np.array_equal(tr.present(denoise=0, dp=dict(iterations=0)), tr.present(denoise=0))
     assert np.array_equal(tr.present(temporal=0, tp=dict(max_history=0.0)), tr.present(temporal=0))
@@ -344,9 +330,9 @@ def test_refusals(have_gpu):
     # a partitioned tracer: move_camera is set_camera + reset there
     tr.set_partition(2, 1, 3)
     tr.Render(4)
-    _refused(tr.present)
+    refused(tr.present)
     assert R.lib.rt2_tracer_present_async(tr._h, None, buf.array.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))) == -1
-    _refused(tr.present_time)
+    refused(tr.present_time)
     tr.move_camera(_moved(cam, 1))
     assert tr.FrameIdx() == 0
     tr.move_camera(cam)
@@ -356,8 +342,8 @@ def test_refusals(have_gpu):
     sc, multi = _tracer(devices=[0, 0], band_h=2)
     multi.Render(4)
     both_refused(multi)
-    _refused(multi.present_time)
-    _refused(lambda: multi.move_camera(cam))
+    refused(multi.present_time)
+    refused(lambda: multi.move_camera(cam))
     _renders(multi, 3)
     multi.close()
     # a joined world-1 tracer
@@ -366,8 +352,8 @@ def test_refusals(have_gpu):
     tr.enable_moments()
     tr.Render(4)
     both_refused(tr)
-    _refused(tr.present_time)
-    _refused(lambda: tr.move_camera(cam))
+    refused(tr.present_time)
+    refused(lambda: tr.move_camera(cam))
     _renders(tr, 3)
     tr.close()
     buf.close()
@@ -391,7 +377,7 @@ def test_progressive_loop_shows_the_reconstruction(have_gpu):
     _, twin = _tracer()
     twin.set_camera(cam)
     twin.Render(24)
-    assert _same(tr.Accumulation(), twin.Accumulation()) and _same(tr.moments(), twin.moments())
+    assert same_bits(tr.Accumulation(), twin.Accumulation()) and same_bits(tr.moments(), twin.moments())
     # a move restarts the count; the ticks after it blend with the history
     loop.move(_moved(cam, 1))
     assert loop.frames_done == 0 and not loop.done() and not loop.converged and loop.n == 1 and tr.FrameIdx() == 0

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from bits import f32_bits, same_bits
 from conftest import ROOT, scene_path
 from denoise_ref import feature_rays
 from helpers import SEED
@@ -23,14 +24,6 @@ SCENES = [c[0] for c in CASES]
 MEDIA = ("cornell_box_volume", "book2_final_scene_10000_samples")
 SPP = 16
 APP = os.path.join(ROOT, "raytrace2_amd", "lib", "rt2_headless")
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 def _rays(o, d, tmax=FLT_MAX, time=0.0):
@@ -187,7 +180,7 @@ def _tracer(name, size=None):
 def _assert_records(got, exp, what):
     assert got.shape == exp.shape
     assert np.array_equal(got[:, 0], exp[:, 0]), f"flags differ {what}: {np.flatnonzero(got[:, 0] != exp[:, 0])[:8]}"
-    bad = np.flatnonzero((_bits(got) != _bits(exp)).any(-1))
+    bad = np.flatnonzero((f32_bits(got) != f32_bits(exp)).any(-1))
     assert bad.size == 0, f"{bad.size} records differ {what}; first {bad[0]}: {got[bad[0]]} vs {exp[bad[0]]}"
 
 
@@ -230,7 +223,7 @@ def test_against_the_oracle(have_gpu, monkeypatch, name, mode):
         seed2 = SEED + 7
         got2 = tr.intersect(rays, seed=seed2)
         _assert_records(got2, _expect(name, rays, seed2), f"{name} {mode} seed 2")
-        assert not _same(got, got2), "the seed does not reach the media"
+        assert not same_bits(got, got2), "the seed does not reach the media"
     assert tr.stats()["overflow"] == 0
     tr.close()
 
@@ -259,11 +252,11 @@ def test_wave_and_chunk_edges(have_gpu, monkeypatch):
     full = tr.intersect(rays)
     _assert_records(full, exp, "full")
     for n in (1, 63, 64, 65, 1000):
-        assert _same(tr.intersect(rays[:n]), full[:n]), n
+        assert same_bits(tr.intersect(rays[:n]), full[:n]), n
     monkeypatch.setenv("RT2_QUERY_CHUNK", "128")
-    assert _same(tr.intersect(rays[:1000]), full[:1000])
+    assert same_bits(tr.intersect(rays[:1000]), full[:1000])
     monkeypatch.setenv("RT2_QUERY_CHUNK", "100")  # rounded up to 128
-    assert _same(tr.intersect(rays[:257]), full[:257])
+    assert same_bits(tr.intersect(rays[:257]), full[:257])
     monkeypatch.delenv("RT2_QUERY_CHUNK")
     empty = tr.intersect(np.zeros((0, 8), F32))
     assert empty.shape == (0, 16)
@@ -306,8 +299,8 @@ def test_invalid_rays_stay_out(have_gpu, name):
     got = tr.intersect(mixed)
     alone = tr.intersect(good)
     _assert_records(alone, exp, "valid alone")
-    assert _same(got[~is_bad], alone)
-    assert (got[is_bad, 0] == -1).all() and (_bits(got[is_bad, 1:]) == 0).all()
+    assert same_bits(got[~is_bad], alone)
+    assert (got[is_bad, 0] == -1).all() and (f32_bits(got[is_bad, 1:]) == 0).all()
     assert np.array_equal(R.ray_valid(mixed), ~is_bad)
     assert tr.stats()["overflow"] == 0
     tr.close()
@@ -321,7 +314,7 @@ def test_device_entry(have_gpu):
     host = tr.intersect(rays)
     d_rays = torch.from_numpy(np.array(rays)).cuda()
     d_out = tr.intersect(d_rays)
-    assert d_out.is_cuda and _same(d_out.cpu().numpy(), host)
+    assert d_out.is_cuda and same_bits(d_out.cpu().numpy(), host)
     assert tr.intersect_time() > 0
     # the entry itself blocks nowhere: host_waits moves only by what stats() itself adds
     out2 = torch.empty((len(rays), 16), dtype=torch.float32, device="cuda")
@@ -334,7 +327,7 @@ def test_device_entry(have_gpu):
     w2 = tr.stats()["host_waits"]
     assert w2 - w1 == w1 - w0
     tr.synchronize()
-    assert _same(out2.cpu().numpy(), host) and tr.intersect_time() > 0
+    assert same_bits(out2.cpu().numpy(), host) and tr.intersect_time() > 0
     tr.close()
 
 
@@ -357,14 +350,14 @@ def test_no_disturbance(have_gpu):
     for _ in range(4):
         tr.Update(sc)
     assert tr.FrameIdx() == ref_idx == 8
-    assert _same(tr.Accumulation(), ref)
-    assert _same(tr.features(), f0)
+    assert same_bits(tr.Accumulation(), ref)
+    assert same_bits(tr.features(), f0)
     _assert_records(got, exp[:500], "between updates")
     tr.set_partition(8, 1, 2)
-    assert _same(tr.intersect(rays[:500]), got)
+    assert same_bits(tr.intersect(rays[:500]), got)
     tr.close()
     sc, tr = _tracer("cornell_box_original")  # no OnResize
-    assert _same(tr.intersect(rays[:500]), got)
+    assert same_bits(tr.intersect(rays[:500]), got)
     tr.close()
     multi = R.RayTracer(sc, devices=[0, 0], band_h=8)
     with pytest.raises(R.Rt2Error) as e:
@@ -380,5 +373,5 @@ def test_headless_pick(have_gpu):
     doc = json.loads(r.stdout.strip().splitlines()[-1])
     sc, tr = _tracer("cornell_box_original", (32, 18))
     assert doc["pick"] == [16, 9] and doc["size"] == [32, 18]
-    assert _same(np.array(doc["record"], F32), tr.features()[9, 16])
+    assert same_bits(np.array(doc["record"], F32), tr.features()[9, 16])
     tr.close()

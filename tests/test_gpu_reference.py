@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from bits import f32_bits
 from conftest import ROOT, scene_path
 from helpers import SEED, gpu_render
 from test_gpu_parity import CASES, MODES
@@ -18,10 +19,6 @@ W, H = 32, 18
 SPP = {c[0]: c[3] for c in CASES}
 HIT_SCENES = sorted(f[:-len("_hits.npy")] for f in os.listdir(REF) if f.endswith("_hits.npy"))
 DEPTH1_SCENES = sorted(f[:-len("_depth1.npy")] for f in os.listdir(REF) if f.endswith("_depth1.npy"))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_the_fixtures_cover_the_cases():
@@ -44,14 +41,14 @@ def test_first_hits_match_the_reference(have_gpu, name):
     tr.set_seed(SEED)
     tr.SetSamplesPerPixel(SPP[name])
     tr.OnResize((W, H))
-    assert np.array_equal(_bits(sc.camera_params(W, H, SPP[name])), _bits(cam))
+    assert np.array_equal(f32_bits(sc.camera_params(W, H, SPP[name])), f32_bits(cam))
     got = tr.features()
     tr.close()
     assert got.shape == (H, W, 16)
     assert np.array_equal(got[..., 0], ref[..., 0]), "hit flags differ"
     hit = ref[..., 0] == 1
     assert hit.any()
-    words = _bits(got[hit][:, 1:10]) != _bits(ref[hit][:, 1:10])
+    words = f32_bits(got[hit][:, 1:10]) != f32_bits(ref[hit][:, 1:10])
     assert not words.any(), f"{np.count_nonzero(words)} words differ, first at pixel {np.argwhere(hit)[np.argwhere(words)[0][0]]}"
 
 
@@ -64,7 +61,7 @@ def test_depth1_matches_the_reference(have_gpu, monkeypatch, name, mode):
         monkeypatch.setenv(k, v)
     ref = np.load(os.path.join(REF, name + "_depth1.npy"))
     acc, _, st, _ = gpu_render(name, W, H, 4, 6, max_depth=1)
-    assert np.array_equal(_bits(acc), _bits(ref)), f"{np.count_nonzero(_bits(acc) != _bits(ref))} words differ"
+    assert np.array_equal(f32_bits(acc), f32_bits(ref)), f"{np.count_nonzero(f32_bits(acc) != f32_bits(ref))} words differ"
     assert st["rays"] == W * H * 6
 
 
@@ -72,5 +69,5 @@ def test_depth1_cornell_without_the_flat_walk(have_gpu, monkeypatch):
     monkeypatch.setenv("RT2_FLAT_BVH", "0")  # read at scene load
     ref = np.load(os.path.join(REF, "cornell_box_original_depth1.npy"))
     acc, _, st, _ = gpu_render("cornell_box_original", W, H, 4, 6, max_depth=1)
-    assert np.array_equal(_bits(acc), _bits(ref))
+    assert np.array_equal(f32_bits(acc), f32_bits(ref))
     assert st["rays"] == W * H * 6

@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from bits import refused, same_bits
 from conftest import scene_path
 from denoise_ref import denoise_ref, variance_of_sem
 from helpers import SEED
@@ -19,16 +20,8 @@ SCENES = ["cornell_box_original", "final_render_book_1", "cornell_box_volume"]
 OTHER = dict(max_history=48.0, max_history_specular=6.0, min_normal_dot=0.5, sigma_p=0.25, sigma_a=2.0)
 
 
-def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
 def _same3(got, ref):
-    return all(_same(g, r) for g, r in zip(got, ref))
+    return all(same_bits(g, r) for g, r in zip(got, ref))
 
 
 # ---- temporal_buffers against the numpy statement --------------------------------------------------------------
@@ -43,7 +36,7 @@ def test_temporal_buffers_match_numpy_bit_for_bit(have_gpu, size):
             ref = temporal_ref(*args, materials=mats, **kw)
             got = R.temporal_buffers(*args, materials=mats, **kw)
             for g, r, what in zip(got, ref, ("colour", "variance", "length")):
-                assert _same(g, r), (size, mats is None, kw, what)
+                assert same_bits(g, r), (size, mats is None, kw, what)
     again = R.temporal_buffers(*args, materials=mats, **kw)
     assert _same3(again, got)  # the same call twice: the same bytes
 
@@ -88,7 +81,7 @@ def _no_history(cur):
 
 
 def _untouched(tr, state):
-    return _same(tr.Accumulation(), state[0]) and _same(tr.moments(), state[1]) and tr.FrameIdx() == state[2]
+    return same_bits(tr.Accumulation(), state[0]) and same_bits(tr.moments(), state[1]) and tr.FrameIdx() == state[2]
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -121,10 +114,10 @@ def test_tracer_chain_matches_numpy_on_its_own_readbacks(have_gpu, name):
     assert trace["has"].mean() > 0.2 and (refB[2] == 20).any(), "the move leaves history to find"
     gotB = tr.temporal_resolve(variance=True, length=True)
     for g, r, what in zip(gotB, refB, ("colour", "variance", "length")):
-        assert _same(g, r), (name, "B", what)
+        assert same_bits(g, r), (name, "B", what)
     assert tr.temporal_time() > 0
     assert _same3(tr.temporal_resolve(variance=True, length=True), gotB)  # twice: the same bytes
-    assert _same(tr.temporal_resolve(), gotB[0])
+    assert same_bits(tr.temporal_resolve(), gotB[0])
     assert _untouched(tr, state)
     if name == "final_render_book_1":
         types = mats[curB[3][..., 9].astype(int), 0][curB[3][..., 0] != 0]
@@ -147,14 +140,14 @@ def test_tracer_chain_matches_numpy_on_its_own_readbacks(have_gpu, name):
         assert trace["has"][trace["specular"]].any(), "a positive specular cap lets metal and glass reuse"
     gotC = tr.temporal_resolve(variance=True, length=True, **kw)
     for g, r, what in zip(gotC, refC, ("colour", "variance", "length")):
-        assert _same(g, r), (name, "C", what)
+        assert same_bits(g, r), (name, "C", what)
     # the tracer still renders what it rendered
     tr.Render(3)
     from oracle.oracle import OracleScene
     o = OracleScene(scene_path(name), SEED)
     o.set_camera(camC.center, camC.look_at, camC.view_up, camC.vfov, camC.defocus_angle, camC.focus_distance)
     acc, _, _ = o.render(W, H, SPP, 7, forward=True)
-    assert _same(tr.Accumulation(), acc)
+    assert same_bits(tr.Accumulation(), acc)
     tr.close()
 
 
@@ -177,7 +170,7 @@ def test_resolve_with_the_filter(have_gpu):
     for dn, kw in ((True, {}), (dict(iterations=2, sigma_l=3.0), dict(iterations=2, sigma_l=3.0))):
         rc, rv = denoise_ref(bc, bv, cur[3], **kw)
         gc, gv, gn = tr.temporal_resolve(denoise=dn, variance=True, length=True)
-        assert _same(gc, rc) and _same(gv, rv) and _same(gn, bn), kw
+        assert same_bits(gc, rc) and same_bits(gv, rv) and same_bits(gn, bn), kw
     assert _same3(tr.temporal_resolve(variance=True, length=True), (bc, bv, bn))  # the filter left no trace
     tr.close()
 
@@ -218,7 +211,7 @@ def test_history_lifetime(have_gpu):
         """Whether a resolve returns the current estimate with length == n."""
         tr.Render(4)
         c, v, n = tr.temporal_resolve(variance=True, length=True)
-        fresh_c, fresh_n = _same(c, tr.NonConvertedPixels()), bool((n == tr.FrameIdx()).all())
+        fresh_c, fresh_n = same_bits(c, tr.NonConvertedPixels()), bool((n == tr.FrameIdx()).all())
         assert fresh_c == fresh_n
         return fresh_n
 
@@ -236,7 +229,7 @@ def test_history_lifetime(have_gpu):
     tr.enable_moments()
     tr.Render(4)
     c, n = tr.temporal_resolve(length=True)
-    assert c.shape == (H + 2, W + 3, 3) and _same(c, tr.NonConvertedPixels()) and (n == 4).all(), "a resize drops it"
+    assert c.shape == (H + 2, W + 3, 3) and same_bits(c, tr.NonConvertedPixels()) and (n == 4).all(), "a resize drops it"
     tr.OnResize((W, H))
     tr.Reset()
     assert fresh()
@@ -271,20 +264,13 @@ def test_history_counts_as_device_bytes(have_gpu):
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------
-def _refused(call):
-    from raytrace2_amd import Rt2Error
-    with pytest.raises(Rt2Error) as e:
-        call()
-    assert e.value.code == -1
-
-
 def _renders(tr, frames, rows=None):
     """The tracer still renders: `frames` frames from a reset give the oracle's sums."""
     from oracle.oracle import OracleScene
     tr.Reset()
     tr.Render(frames)
     acc, _, _ = OracleScene(scene_path("cornell_box_original"), SEED).render(W, H, SPP, frames, forward=True)
-    assert _same(tr.Accumulation(), acc if rows is None else acc[rows])
+    assert same_bits(tr.Accumulation(), acc if rows is None else acc[rows])
 
 
 def test_refusals(have_gpu):
@@ -294,23 +280,23 @@ def test_refusals(have_gpu):
     # moments off
     sc, tr = _tracer(name, moments=False)
     tr.Render(4)
-    _refused(tr.temporal_resolve)
-    _refused(tr.temporal_push)
+    refused(tr.temporal_resolve)
+    refused(tr.temporal_push)
     _renders(tr, 3)
     # fewer than 2 frames
     tr.enable_moments()
-    _refused(tr.temporal_resolve)
+    refused(tr.temporal_resolve)
     tr.Render(1)
-    _refused(tr.temporal_resolve)
-    _refused(tr.temporal_push)
+    refused(tr.temporal_resolve)
+    refused(tr.temporal_push)
     # each invalid parameter, a NULL output, invalid filter parameters
     tr.Render(3)
     for kw in (dict(max_history=0.0), dict(max_history=float("inf")), dict(max_history_specular=-1.0),
                dict(max_history_specular=float("nan")), dict(min_normal_dot=float("nan")), dict(sigma_p=0.0),
                dict(sigma_p=float("inf")), dict(sigma_a=-1.0), dict(sigma_a=float("nan"))):
-        _refused(lambda: tr.temporal_resolve(**kw))
-        _refused(lambda: tr.temporal_push(**kw))
-    _refused(lambda: tr.temporal_resolve(denoise=dict(iterations=0)))
+        refused(lambda: tr.temporal_resolve(**kw))
+        refused(lambda: tr.temporal_push(**kw))
+    refused(lambda: tr.temporal_resolve(denoise=dict(iterations=0)))
     assert R.lib.rt2_tracer_temporal_resolve(tr._h, None, 0, None, None, None, None) == -1
     buf = (ctypes.c_float * 32)()
     assert R.lib.rt2_temporal_buffers(0, 1, 1, *([buf] * 9), None, 0, None, None, None, None) == -1
@@ -319,18 +305,18 @@ def test_refusals(have_gpu):
     # a partitioned tracer
     tr.set_partition(2, 1, 3)
     tr.Render(4)
-    _refused(tr.temporal_resolve)
-    _refused(tr.temporal_push)
-    _refused(tr.temporal_clear)
+    refused(tr.temporal_resolve)
+    refused(tr.temporal_push)
+    refused(tr.temporal_clear)
     _renders(tr, 3, local_rows(H, 2, 1, 3))
     tr.close()
     # a multi tracer over one GPU twice
     sc, multi = _tracer(name, devices=[0, 0], band_h=2)
     multi.Render(4)
-    _refused(multi.temporal_resolve)
-    _refused(multi.temporal_push)
-    _refused(multi.temporal_clear)
-    _refused(multi.temporal_time)
+    refused(multi.temporal_resolve)
+    refused(multi.temporal_push)
+    refused(multi.temporal_clear)
+    refused(multi.temporal_time)
     _renders(multi, 3)
     multi.close()
     # a joined world-1 tracer
@@ -338,8 +324,8 @@ def test_refusals(have_gpu):
     tr.join(R.comm_unique_id(), 1, 0, 16)
     tr.enable_moments()
     tr.Render(4)
-    _refused(tr.temporal_resolve)
-    _refused(tr.temporal_push)
-    _refused(tr.temporal_clear)
+    refused(tr.temporal_resolve)
+    refused(tr.temporal_push)
+    refused(tr.temporal_clear)
     _renders(tr, 3)
     tr.close()

@@ -2,14 +2,13 @@
 rt2_deinterleave_estimate_host, the CPU statement of gather_estimate()'s kernel, against rt2_deinterleave_host and
 the noise estimate's numpy formulas bit for bit, its argument checks, and the C++ mirror's new members. No GPU."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build as H
 import raytrace2_amd as R
-from conftest import ROOT
+from bits import f32_bits
 from denoise_ref import variance_of_sem
 from noise_ref import noise_ref
 from raytrace2_amd.dist import band_rows_max, deinterleave, deinterleave_estimate, source_rows
@@ -19,10 +18,6 @@ FRAMES = 16
 # (width, height, world, band_h): 33x10 over 4 ranks in bands of 8 leaves ranks 2 and 3 without a row and rank 1
 # with padding rows; 1x45 is one pixel per row
 LAYOUTS = [(50, 45, 2, 8), (50, 45, 3, 5), (50, 45, 4, 1), (50, 45, 8, 16), (33, 10, 4, 8), (1, 45, 3, 5)]
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
 
 
 def _stacks(w, h, world, band_h, seed):
@@ -54,11 +49,11 @@ def test_deinterleave_estimate_host_matches_numpy(w, h, world, band_h):
     image, mean, var = deinterleave_estimate(acc, sq, h, band_h, FRAMES)
     assert image.shape == mean.shape == (h, w, 3) and var.shape == (h, w)
     ref_a, ref_q = deinterleave(acc, h, band_h), deinterleave(sq, h, band_h)
-    assert np.array_equal(_bits(image), _bits(ref_a))
+    assert np.array_equal(f32_bits(image), f32_bits(ref_a))
     with np.errstate(all="ignore"):
-        assert np.array_equal(_bits(mean), _bits(ref_a / F32(FRAMES)))
+        assert np.array_equal(f32_bits(mean), f32_bits(ref_a / F32(FRAMES)))
     sem, _, finite = noise_ref(ref_a, ref_q, FRAMES)
-    assert np.array_equal(_bits(var), _bits(variance_of_sem(sem)))
+    assert np.array_equal(f32_bits(var), f32_bits(variance_of_sem(sem)))
     # the data reaches the cases it is meant to: non-finite pixels (variance +inf), clamped and ordinary ones
     if w * h >= 330:
         assert (~finite).any() and np.isinf(var[~finite]).all() and np.isfinite(var[finite]).all()
@@ -97,6 +92,4 @@ def test_new_entry_points_refuse_null_tracers():
 def test_cpp_mirror_image_reconstruct_members_compile():
     """include/rt2/RayTracer.hpp: GatherEstimate, ImageVariance, ImageFeatures, ImageResolve, ImagePresentAsync,
     ImagePresent, ImageMoveCamera, ImagePresentTime."""
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only",
-                        os.path.join(ROOT, "tests", "cpp", "mirror_image_reconstruct.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.syntax_only("mirror_image_reconstruct.cpp")

@@ -8,21 +8,17 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build as H
 import raytrace2_amd as R
 from conftest import ROOT
 from noise_ref import noise_ref, ss_unclamped
 from raytrace2_amd._native import Noise
 from raytrace2_amd.dist import combine_noise
 
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
 
 
-def _build(tmp_path, name, extra=()):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra, "-I", CSRC,
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "noise_host.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+def _build(sanitize):
+    return H.program("noise_host.cpp", [*H.HOST, *(H.HOST_SAN if sanitize else ())])
 
 
 def _run(exe, tmp_path, a, q, n):
@@ -81,8 +77,7 @@ def _cases():
 @pytest.mark.parametrize("sanitize", [False, True])
 def test_pixel_noise_matches_the_formulas_bit_for_bit(tmp_path, sanitize):
     """tests/cpp/noise_host.cpp over noise.h, plain and with the host sanitizers (a stand-alone program)."""
-    exe = _build(tmp_path, "noise_host_san" if sanitize else "noise_host",
-                 ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g") if sanitize else ())
+    exe = _build(sanitize)
     a, q, n = _cases()
     sem, err, fin = _run(exe, tmp_path, a, q, n)
     ref = [noise_ref(a[i], q[i], n[i]) for i in range(len(a))]
@@ -122,9 +117,7 @@ def test_null_arguments_return_invalid():
 
 def test_cpp_mirror_noise_members_compile():
     """include/rt2/RayTracer.hpp: EnableMoments, Moments, StandardError, Noise, RenderUntil."""
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only",
-                        os.path.join(ROOT, "tests", "cpp", "mirror_noise.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.syntax_only("mirror_noise.cpp")
 
 
 def test_noise_struct_matches_the_header(tmp_path):

@@ -6,6 +6,7 @@ import subprocess
 
 import numpy as np
 
+import host_build as H
 from conftest import ROOT
 
 F32 = np.float32
@@ -69,13 +70,8 @@ def test_refusals_on_a_tracer_handle_need_no_launch():
     L.rt2_tracer_destroy(h)
 
 
-def test_cpp_mirror_occlusion_members_compile_and_link(tmp_path):
+def test_cpp_mirror_occlusion_members_compile_and_link():
     """include/rt2/RayTracer.hpp: Occluded, OccludedDevice, against the built library."""
-    lib_dir = os.path.join(ROOT, "raytrace2_amd", "lib")
-    exe = str(tmp_path / "mirror_occlusion")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", exe,
-                        os.path.join(ROOT, "tests", "cpp", "mirror_occlusion.cpp"), "-L", lib_dir, "-lrt2",
-                        f"-Wl,-rpath,{lib_dir}"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = H.program("mirror_occlusion.cpp", H.MIRROR, link=H.LIBRT2)
     r = subprocess.run([exe], capture_output=True, text=True)  # no arguments: it touches no device
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]

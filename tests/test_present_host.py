@@ -3,7 +3,6 @@ built into the stand-alone tests/cpp/present_host.cpp, also under the address an
 sanitizers) against its numpy statement (tests/present_ref.py) byte for byte, the edge values the header names,
 and the new entry points' argument checks, defaults and struct layout. No GPU."""
 import ctypes
-import functools
 import os
 import struct
 import subprocess
@@ -11,29 +10,18 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build as H
 import raytrace2_amd as R
 from conftest import ROOT
 from present_ref import EDGE_BYTES, EDGE_VALUES, edge_cases, edge_image, present
 from raytrace2_amd._native import CameraDesc, DenoiseParams, PresentParams, TemporalParams
 
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
 F32 = np.float32
 SIZES = [(1, 1), (1, 9), (33, 9), (70, 37)]
 
 
-@functools.lru_cache(maxsize=None)
-def _exe(tmp, sanitize):
-    exe = os.path.join(tmp, "present_host_san" if sanitize else "present_host")
-    extra = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g") if sanitize else ()
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra, "-I", CSRC,
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "present_host.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def build_dir(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("present_host"))
+def _exe(sanitize):
+    return H.program("present_host.cpp", [*H.HOST, *(H.HOST_SAN if sanitize else ())])
 
 
 def _run(exe, tmp_path, c):
@@ -64,10 +52,10 @@ def test_numpy_statement_on_the_edge_values():
 
 
 @pytest.mark.parametrize("sanitize", [False, True])
-def test_host_program_matches_numpy_byte_for_byte(build_dir, tmp_path, sanitize):
+def test_host_program_matches_numpy_byte_for_byte(tmp_path, sanitize):
     """Every size of the issue on random values in [-0.5, 1.5] (the two larger ones with the edge values in), and
     each edge value in every channel; the sanitized build is its own program."""
-    exe = _exe(build_dir, sanitize)
+    exe = _exe(sanitize)
     for (w, h) in SIZES:
         c = edge_image(w, h)
         assert c.shape == (h, w, 3)
@@ -135,6 +123,4 @@ def test_params_struct_matches_the_header(tmp_path):
 
 def test_cpp_mirror_present_members_compile():
     """include/rt2/RayTracer.hpp: PresentDefaults, Present, PresentAsync, MoveCamera, PresentTime, Query."""
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only",
-                        os.path.join(ROOT, "tests", "cpp", "mirror_present.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.syntax_only("mirror_present.cpp")

@@ -6,6 +6,7 @@ import subprocess
 
 import numpy as np
 
+import host_build as H
 from conftest import ROOT
 
 F32 = np.float32
@@ -126,13 +127,8 @@ def test_ray_valid_agrees_with_numpy():
     assert got[len(mixed):].any() and not got[len(mixed):].all()
 
 
-def test_cpp_mirror_intersect_members_compile_and_link(tmp_path):
+def test_cpp_mirror_intersect_members_compile_and_link():
     """include/rt2/RayTracer.hpp: Intersect, IntersectDevice, IntersectTime, RayValid, against the built library."""
-    lib_dir = os.path.join(ROOT, "raytrace2_amd", "lib")
-    exe = str(tmp_path / "mirror_intersect")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", exe,
-                        os.path.join(ROOT, "tests", "cpp", "mirror_intersect.cpp"), "-L", lib_dir, "-lrt2",
-                        f"-Wl,-rpath,{lib_dir}"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = H.program("mirror_intersect.cpp", H.MIRROR, link=H.LIBRT2)
     r = subprocess.run([exe], capture_output=True, text=True)  # no arguments: it touches no device
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]

@@ -4,11 +4,9 @@ Quad.cpp:19-43), over special values (signed zeros, denormals, infinities, NaNs,
 and random floats of every exponent."""
 import numpy as np
 
+from bits import f32_bits
+
 F32 = np.float32
-
-
-def _bits(x):
-    return np.asarray(x, dtype=F32).view(np.uint32)
 
 
 def _specials():
@@ -30,14 +28,14 @@ def _randoms(n, rng):
 def unit_pair(a, b):
     """render.hip unit_pair: max(bits(a + 0), bits(b + 0)) <= bits(1.0f)."""
     with np.errstate(invalid="ignore"):
-        ka = _bits(a + F32(0.0))
-        kb = _bits(b + F32(0.0))
+        ka = f32_bits(a + F32(0.0))
+        kb = f32_bits(b + F32(0.0))
     return np.maximum(ka, kb) <= np.uint32(0x3F800000)
 
 
 def in_interval(t, lo, hi):
     """render.hip in_interval: bits(t) - bits(lo) <= bits(hi) - bits(lo), unsigned, wrapping."""
-    return (_bits(t) - _bits(lo)) <= (_bits(hi) - _bits(lo))
+    return (f32_bits(t) - f32_bits(lo)) <= (f32_bits(hi) - f32_bits(lo))
 
 
 def test_unit_pair_matches_ieee_compares():

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import edge_rays as E
+from bits import f32_bits, same_bits
 from conftest import ROOT, scene_path
 from denoise_ref import feature_rays
 from helpers import SEED
@@ -40,14 +41,6 @@ if not R.available() and not R.checkout_present():
 # a checkout without the library is a build failure: every test below then fails on loading the library
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
 def _pair(name, mask=O.CTL_REF_MATH):
     """The oracle's scene, loaded and used under `mask`, and the reference's."""
     with O.controls(mask):
@@ -64,7 +57,7 @@ KEYS = [(SEED, 0, 0), (SEED, 1, 0), (SEED, 431, 5), (0x0123456789ABCDEF, 24 * 18
 def test_streams(seed, pixel, frame):
     """The driver's Philox stream, read through the reference's RandReal() hook, is oracle.uniforms."""
     a, b = R.uniforms(seed, pixel, frame, 64), O.uniforms(seed, pixel, frame, 64)
-    assert _same(a, b)
+    assert same_bits(a, b)
     assert len(np.unique(a)) > 60 and (a >= 0).all() and (a < 1).all()
 
 
@@ -74,7 +67,7 @@ def test_camera(name):
     o, r = _pair(name)
     for w, h in ((33, 18), (64, 64)):
         for spp in (4, SPP[name]):
-            assert _same(r.camera_params(w, h, spp), o.camera_params(w, h, spp)), (w, h, spp)
+            assert same_bits(r.camera_params(w, h, spp), o.camera_params(w, h, spp)), (w, h, spp)
 
 
 def test_camera_moved_and_defocus():
@@ -85,10 +78,10 @@ def test_camera_moved_and_defocus():
     for w, h in ((33, 18), (64, 64)):
         for spp in (4, 16):
             a, b = r.camera_params(w, h, spp), o.camera_params(w, h, spp)
-            assert _same(a, b) and a[9] == np.float32(250.5)
+            assert same_bits(a, b) and a[9] == np.float32(250.5)
     o, r = _pair("final_render_book_1")
     a, b = r.camera_params(33, 18, 500), o.camera_params(33, 18, 500)
-    assert _same(a, b) and a[18] > 0 and np.abs(a[12:18]).max() > 0  # a defocus disk
+    assert same_bits(a, b) and a[18] > 0 and np.abs(a[12:18]).max() > 0  # a defocus disk
 
 
 # ---- hits -------------------------------------------------------------------------------------------------
@@ -219,7 +212,7 @@ def test_hits(name):
     flags_differ = np.flatnonzero(a[:, 0] != b[:, 0])
     assert len(flags_differ) == 0, f"hit flag differs on rays {flags_differ[:5]}"
     hit = a[:, 0] == 1
-    words = _bits(a[hit]) != _bits(b[hit][:, :10])
+    words = f32_bits(a[hit]) != f32_bits(b[hit][:, :10])
     assert not words.any(), f"{np.count_nonzero(words)} words differ, first ray {np.flatnonzero(hit)[np.argwhere(words)[0][0]]}"
     assert np.count_nonzero(hit) >= 200 and np.count_nonzero(~hit) >= 20, (np.count_nonzero(hit), np.count_nonzero(~hit))
     _, kinds = _kinds_by_material(name)
@@ -246,12 +239,12 @@ def test_edge_batches(name):
     flags_differ = np.flatnonzero(a[:, 0] != b[:, 0])
     assert len(flags_differ) == 0, f"hit flag differs on rays {flags_differ[:5]} ({batch.cls[flags_differ[:5]]})"
     hit = a[:, 0] == 1
-    words = _bits(a[hit]) != _bits(b[hit][:, :10])
+    words = f32_bits(a[hit]) != f32_bits(b[hit][:, :10])
     assert not words.any(), f"{np.count_nonzero(words)} words differ, first ray {np.flatnonzero(hit)[np.argwhere(words)[0][0]]}"
     assert np.count_nonzero(hit) >= 0.1 * len(a) and np.count_nonzero(~hit) >= 0.1 * len(a)
     if name not in E.MEDIA:
         mine = E.answers(name)
-        assert np.array_equal(mine[:, 0], a[:, 0]) and _same(mine[hit], a[hit])
+        assert np.array_equal(mine[:, 0], a[:, 0]) and same_bits(mine[hit], a[hit])
 
 
 # ---- whole paths ------------------------------------------------------------------------------------------
@@ -265,7 +258,7 @@ def _paths_differ(name, spp, frames, mask=O.CTL_REF_MATH, **kw):
     with O.controls(mask):
         oa, _, cnt = o.render(PW, PH, spp, frames, forward=False, threads=1, **kw)
     ra, draws = r.render(PW, PH, spp, frames, **kw)
-    return int(np.count_nonzero(_bits(oa) != _bits(ra))), cnt["rng_draws"], draws, ra
+    return int(np.count_nonzero(f32_bits(oa) != f32_bits(ra))), cnt["rng_draws"], draws, ra
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -304,7 +297,7 @@ def test_perlin(name):
         with O.controls(O.CTL_REF_MATH):
             a = o.texture_value(tex, pts)
         b = r.perlin_probe(tex, pts)
-        assert _same(a, b), f"texture {tex}: {np.count_nonzero(_bits(a) != _bits(b))} words differ"
+        assert same_bits(a, b), f"texture {tex}: {np.count_nonzero(f32_bits(a) != f32_bits(b))} words differ"
         assert len(np.unique(b)) > 200
 
 

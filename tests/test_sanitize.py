@@ -12,12 +12,11 @@ sanitizer report aborts the run. CPU only; the GPU code is not built here (no de
 pool)."""
 import glob
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
+import host_build as H
+from host_build import ROOT
 
 BAD_DOCS = [
     '{"materials": [{"type": "plastic"}], "camera": {}}',
@@ -40,16 +39,8 @@ BAD_DOCS = [
 
 
 @pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("asan") / "sanitize_host")
-    flags = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-omit-frame-pointer",
-             "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all", "-pthread"]
-    srcs = [os.path.join(ROOT, "tests", "cpp", "sanitize_host.cpp"), os.path.join(ROOT, "oracle", "rt_oracle.cpp")]
-    srcs += [os.path.join(CSRC, f) for f in ("json.cpp", "scene.cpp", "compile.cpp", "image.cpp")]
-    r = subprocess.run(["g++", *flags, "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", CSRC, "-o", exe, *srcs],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+def sanitized():
+    return H.program("sanitize_host.cpp", H.SANITIZE, ("oracle/rt_oracle.cpp", *H.COMPILER_SOURCES, "image.cpp"))
 
 
 def test_host_code_is_clean_under_asan_and_ubsan(sanitized, tmp_path):
@@ -62,11 +53,7 @@ def test_host_code_is_clean_under_asan_and_ubsan(sanitized, tmp_path):
         p.write_text(doc)
         bad.append(str(p))
     cams = [os.path.join(ROOT, "scenes", "cam1.json"), os.path.join(ROOT, "scenes", "scene2_cam.json")]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([sanitized, "--out", str(tmp_path), "--good", *scenes, "--bad", *bad, "--camera", *cams],
-                       capture_output=True, text=True, env=env, timeout=1200)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-6000:]
-    assert r.stdout.startswith("documents=")
-    assert int(r.stdout.split()[0].split("=")[1]) > 5000  # (every scene, its prefixes and corruptions)
+    out = H.run(sanitized, ["--out", str(tmp_path), "--good", *scenes, "--bad", *bad, "--camera", *cams], 1200,
+                env=H.SANITIZE_ENV)
+    assert out.startswith("documents=")
+    assert int(out.split()[0].split("=")[1]) > 5000  # (every scene, its prefixes and corruptions)

@@ -12,7 +12,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build as H
 import raytrace2_amd as R
+from bits import same_bits
 from conftest import ROOT, scene_path
 from denoise_ref import features_ref, variance_of_sem
 from helpers import SEED, rmse
@@ -20,25 +22,13 @@ from noise_ref import noise_ref
 from raytrace2_amd._native import TemporalParams
 from temporal_ref import DEFAULTS, FEATURE_FLOATS, case_args, params, project, synthetic_case, temporal_ref
 
-CSRC = os.path.join(ROOT, "raytrace2_amd", "csrc")
 F32 = np.float32
 SIZES = [(1, 1), (1, 9), (9, 1), (33, 9), (70, 37)]
 OTHER = dict(max_history=48.0, max_history_specular=6.0, min_normal_dot=0.5, sigma_p=0.25, sigma_a=2.0)
 
 
-@functools.lru_cache(maxsize=None)
-def _exe(tmp, sanitize):
-    exe = os.path.join(tmp, "temporal_host_san" if sanitize else "temporal_host")
-    extra = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g") if sanitize else ()
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra, "-I", CSRC,
-                        "-o", exe, os.path.join(ROOT, "tests", "cpp", "temporal_host.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def build_dir(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("temporal_host"))
+def _exe(sanitize):
+    return H.program("temporal_host.cpp", [*H.HOST, *(H.HOST_SAN if sanitize else ())])
 
 
 def _run(exe, tmp_path, args, materials=None, **kw):
@@ -61,23 +51,15 @@ def _run(exe, tmp_path, args, materials=None, **kw):
     return out[:3 * n].reshape(h, w, 3), out[3 * n:4 * n].reshape(h, w), out[4 * n:].reshape(h, w)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
-
-
 def _same3(got, ref):
-    return all(_same(g, r) for g, r in zip(got, ref))
+    return all(same_bits(g, r) for g, r in zip(got, ref))
 
 
 @pytest.mark.parametrize("sanitize", [False, True])
-def test_host_program_matches_numpy_bit_for_bit(build_dir, tmp_path, sanitize):
+def test_host_program_matches_numpy_bit_for_bit(tmp_path, sanitize):
     """Every size of the GPU test, with and without the material table, at the defaults and at other parameters;
     the sanitized build is its own program."""
-    exe = _exe(build_dir, sanitize)
+    exe = _exe(sanitize)
     for (w, h) in SIZES:
         case = synthetic_case(w, h)
         args = case_args(case)
@@ -120,17 +102,17 @@ def test_synthetic_case_reaches_the_branches():
         assert metal.any() and glass.any(), "a metal and a dielectric current hit"
         if spec_cap == 0:
             assert tr["cap_zero"][metal].any() and tr["cap_zero"][glass].any() and not tr["has"][tr["specular"]].any()
-            assert _same(on[tr["specular"]], n[tr["specular"]])
+            assert same_bits(on[tr["specular"]], n[tr["specular"]])
         else:
             assert tr["has"][metal].any() and tr["has"][glass].any()
             assert (on[tr["has"] & tr["specular"]] == F32(spec_cap) + F32(4)).all()
         fin = tr["finite"]
         # no finite input gives a NaN or an inf; the others pass through bit for bit with length 0
         assert np.isfinite(oc[fin]).all() and np.isfinite(ov[fin]).all() and np.isfinite(on).all()
-        assert _same(oc[~fin], c[~fin]) and _same(ov[~fin], v[~fin]) and (on[~fin] == 0).all()
+        assert same_bits(oc[~fin], c[~fin]) and same_bits(ov[~fin], v[~fin]) and (on[~fin] == 0).all()
         # no history: the current pixel bit for bit
         no = fin & ~tr["has"]
-        assert no.any() and _same(oc[no], c[no]) and _same(ov[no], v[no]) and _same(on[no], n[no])
+        assert no.any() and same_bits(oc[no], c[no]) and same_bits(ov[no], v[no]) and same_bits(on[no], n[no])
         assert (oc[tr["has"]] != c[tr["has"]]).any()
 
 
@@ -155,8 +137,8 @@ def _flat(w, h):
                 materials=None)
 
 
-def test_degenerate_cases(build_dir, tmp_path):
-    exe = _exe(build_dir, False)
+def test_degenerate_cases(tmp_path):
+    exe = _exe(False)
 
     def both(case, **kw):
         ref = temporal_ref(*case_args(case), materials=case["materials"], **kw)
@@ -172,15 +154,15 @@ def test_degenerate_cases(build_dir, tmp_path):
     assert ok.all() and (fx == xx).all() and (fy == yy).all()
     ref = both(case)
     a = F32(4) / (F32(64) + F32(4))
-    assert _same(ref[2], np.full((5, 6), 68, F32))
-    assert _same(ref[0], case["hist_color"] + a * (case["color"] - case["hist_color"]))
+    assert same_bits(ref[2], np.full((5, 6), 68, F32))
+    assert same_bits(ref[0], case["hist_color"] + a * (case["color"] - case["hist_color"]))
     poisoned = dict(case)
     poisoned["hist_color"] = case["hist_color"].copy()
     poisoned["hist_color"][2, 3] = np.nan
     ref2 = both(poisoned)
     changed = np.zeros((5, 6), bool)
     changed[2, 3] = True
-    assert _same(ref2[0][~changed], ref[0][~changed]) and _same(ref2[0][2, 3], case["color"][2, 3])
+    assert same_bits(ref2[0][~changed], ref[0][~changed]) and same_bits(ref2[0][2, 3], case["color"][2, 3])
     assert ref2[2][2, 3] == 4
     # a 1 x 1 image
     one = _flat(1, 1)
@@ -230,7 +212,7 @@ def test_derivable_properties():
     a0 = list(args)
     a0[6] = np.zeros_like(args[6])
     oc, ov, on = temporal_ref(*a0, materials=case["materials"])
-    assert _same(oc, c) and _same(ov, v) and _same(on[fin], n[fin]) and (on[~fin] == 0).all()
+    assert same_bits(oc, c) and same_bits(ov, v) and same_bits(on[fin], n[fin]) and (on[~fin] == 0).all()
     # the history camera turned to face away: the same
     a1 = list(args)
     cam = args[8].copy()
@@ -239,7 +221,7 @@ def test_derivable_properties():
     tr = {}
     oc, ov, on = temporal_ref(*a1, materials=case["materials"], trace=tr)
     assert not tr["has"].any() and tr["hit"].any()
-    assert _same(oc, c) and _same(ov, v) and _same(on[fin], n[fin])
+    assert same_bits(oc, c) and same_bits(ov, v) and same_bits(on[fin], n[fin])
     # identical camera and features, a constant history length: n_out within 8 ulp of min(nh, cap) + n (four
     # products, three sums and one division, each within half an ulp)
     for nh, cap in ((64.0, 1024.0), (2000.0, 1024.0), (37.3, 1024.0), (37.3, 18.0)):
@@ -387,9 +369,7 @@ def test_argument_checks_return_invalid():
 
 def test_cpp_mirror_temporal_members_compile():
     """include/rt2/RayTracer.hpp: TemporalDefaults, TemporalResolve, TemporalPush, TemporalClear."""
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only",
-                        os.path.join(ROOT, "tests", "cpp", "mirror_temporal.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    H.syntax_only("mirror_temporal.cpp")
 
 
 def test_params_struct_matches_the_header(tmp_path):
