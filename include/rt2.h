@@ -704,6 +704,56 @@ RT2_API int rt2_tracer_occluded(rt2_tracer* tr, int64_t n, const float* rays, ui
 RT2_API int rt2_tracer_occluded_device(rt2_tracer* tr, int64_t n, const float* d_rays, uint64_t seed, int8_t* d_out);
 RT2_API int rt2_tracer_intersect_time(rt2_tracer* tr, double* ms);
 
+/* ---- Ambient occlusion ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before.
+ * Per point the number of `samples` cosine-weighted occlusion rays that are blocked, one uint32_t per point, drawn
+ * and traced on the GPU (raytrace2_amd/csrc/ambient.h holds the rule; the kernel, rt2_ambient_direction and the host
+ * test evaluate that one text).
+ * A point, 8 floats, the ray record's shape: px py pz tmax | nx ny nz time. It is valid iff rt2_query_ray_valid
+ *   holds for these eight words, the normal standing in for the direction. An invalid point answers 0xFFFFFFFF.
+ * Sample s of the point with stream index i, every float operation rounded on its own: u = the first RandUnitVec3
+ *   draw of the path stream (seed, pixel word i, frame word 0x80000000 + s), above every render frame index; v = n +
+ *   u; v = n where every |component of v| <= 1e-8 (Lambertian scatter's guard); d = v * (1 / sqrt((vx vx + vy vy) +
+ *   vz vz)). The ray (p, tmax | d, time) is traced exactly as rt2_tracer_occluded traces that record: interval
+ *   (0.001, tmax), media drawing from the stream (seed, 0xFFFFFFF0, 0). A built ray that fails rt2_query_ray_valid
+ *   is not traced and counts as clear. The count is the number of s in [0, samples) whose answer is 1.
+ * ambient_direction: d of the rule from a normal and a unit-vector draw (3 floats each), on the host.
+ * ambient (image mode): the points are the tracer's cached feature records (rt2_tracer_features): point = slots 2-4,
+ *   normal = slots 5-7, time 0, tmax = radius (FLT_MAX: unbounded); i is the global pixel index y * width + x, so a
+ *   set_partition tracer answers what the whole image answers on its rows; a pixel whose ray missed answers
+ *   0xFFFFFFFF. One word per local pixel into a host buffer, in rt2_tracer_accumulation's row order. It behaves as a
+ *   readback: it launches queued frames, runs the feature pass under `seed` if the cache is stale (the cache is
+ *   keyed by camera, size, partition and seed: a seed other than the tracer's makes the next rt2_tracer_features
+ *   trace again), and waits once.
+ * ambient_device: the same into device memory on the tracer's device, exactly `local pixels` words. It only
+ *   enqueues on the tracer's stream, adds nothing to rt2_stats.host_waits and is complete when rt2_tracer_query
+ *   returns 1.
+ * ambient_points, ambient_points_device (point mode): n caller records, i = the record's index. The host entry goes
+ *   in chunks of RT2_QUERY_CHUNK points through the tracer's two query buffers, as occluded does; the device entry
+ *   only enqueues and writes exactly n words. They work before on_resize and on set_partition and joined tracers.
+ * A launch takes as many samples of every point as keep points x samples below 2^31 and a larger call is split by
+ *   sample ranges; counts are integer sums, so the bytes are the same on every run and under every split.
+ * ambient_time: GPU time (HIP events) of the last ambient call's kernels in ms (a stale cache's feature pass not
+ *   included); -1 while that call has not finished, or when there was none. It polls and never waits.
+ * Quirks, the reference's and this rule's: a transformed child compares its model-space t with tmax (occluded's
+ *   quirk). Every ray of a call shares the one medium stream, so in a scene wrapped in a medium (book 2's mist) an
+ *   image's counts are all 0 or all `samples` around one radius, and the camera's first hits there lie in the mist.
+ *   dot(d, n) can be slightly negative where a record's normal is not unit.
+ * A call changes no render state: accumulation, moments, counts, FrameIdx() and history are unchanged, and a second
+ *   call returns the same bytes. n == 0 is RT2_OK and does nothing.
+ * RT2_ERR_INVALID: a NULL tracer or pointer; samples outside [1, 65535]; a radius that is NaN, infinite or <= 0.001;
+ *   n < 0 or n >= 2^31; image mode on a tracer without an image (rt2_tracer_create gives every tracer the scene's
+ *   default one, as on_resize would) or on a joined tracer; a create_multi tracer; what features
+ *   (image mode) and occluded refuse for the scene's stack depth. A refused call changes nothing. */
+RT2_API int rt2_ambient_direction(const float* n3, const float* u3, float* d3);
+RT2_API int rt2_tracer_ambient(rt2_tracer* tr, int samples, float radius, uint64_t seed, uint32_t* out);
+RT2_API int rt2_tracer_ambient_device(rt2_tracer* tr, int samples, float radius, uint64_t seed, uint32_t* d_out);
+RT2_API int rt2_tracer_ambient_points(rt2_tracer* tr, int64_t n, const float* points, int samples, uint64_t seed,
+                                      uint32_t* out);
+RT2_API int rt2_tracer_ambient_points_device(rt2_tracer* tr, int64_t n, const float* d_points, int samples,
+                                             uint64_t seed, uint32_t* d_out);
+RT2_API int rt2_tracer_ambient_time(rt2_tracer* tr, double* ms);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

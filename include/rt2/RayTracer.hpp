@@ -454,6 +454,30 @@ class RayTracer {
     Check(rt2_tracer_intersect_time(t_.get(), &ms));
     return ms;
   }
+  // Ambient occlusion (rt2.h "Ambient occlusion"): per point the number of `samples` cosine-weighted occlusion
+  // rays that are blocked, one uint32_t each, 0xFFFFFFFF for a miss pixel or an invalid point. Ambient: the image's
+  // first hits (the cached feature records) within `radius` (FLT_MAX: unbounded), one word per local pixel into a
+  // host buffer; a readback. AmbientPoints: n caller records, 8 floats each (px py pz tmax nx ny nz time). The
+  // Device forms take device pointers, only enqueue and are complete when Query() returns true. AmbientTime: GPU ms
+  // of the last call's kernels (-1: not finished, or none); never waits.
+  void Ambient(int samples, float radius, uint32_t* out, uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_ambient(t_.get(), samples, radius, seed, out));
+  }
+  void AmbientDevice(int samples, float radius, uint32_t* d_out, uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_ambient_device(t_.get(), samples, radius, seed, d_out));
+  }
+  void AmbientPoints(const float* points, int64_t n, int samples, uint32_t* out, uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_ambient_points(t_.get(), n, points, samples, seed, out));
+  }
+  void AmbientPointsDevice(const float* d_points, int64_t n, int samples, uint32_t* d_out,
+                           uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_ambient_points_device(t_.get(), n, d_points, samples, seed, d_out));
+  }
+  [[nodiscard]] double AmbientTime() {
+    double ms = -1.0;
+    Check(rt2_tracer_ambient_time(t_.get(), &ms));
+    return ms;
+  }
   [[nodiscard]] bool Query() {
     const int q = rt2_tracer_query(t_.get());
     Check(q);

@@ -274,6 +274,12 @@ def _load():
         "rt2_tracer_intersect_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
         "rt2_tracer_occluded": (i32, [vp, i64, fp, u64, ctypes.POINTER(ctypes.c_int8)]),
         "rt2_tracer_occluded_device": (i32, [vp, i64, vp, u64, vp]),
+        "rt2_ambient_direction": (i32, [fp, fp, fp]),
+        "rt2_tracer_ambient": (i32, [vp, i32, f32, u64, ctypes.POINTER(ctypes.c_uint32)]),
+        "rt2_tracer_ambient_device": (i32, [vp, i32, f32, u64, vp]),
+        "rt2_tracer_ambient_points": (i32, [vp, i64, fp, i32, u64, ctypes.POINTER(ctypes.c_uint32)]),
+        "rt2_tracer_ambient_points_device": (i32, [vp, i64, vp, i32, u64, vp]),
+        "rt2_tracer_ambient_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

@@ -538,6 +538,8 @@ rt2_tracer::~rt2_tracer() {
   image_recon.DestroyEvents();
   if (query_e0) (void)hipEventDestroy(query_e0);
   if (query_e1) (void)hipEventDestroy(query_e1);
+  if (ambient_e0) (void)hipEventDestroy(ambient_e0);
+  if (ambient_e1) (void)hipEventDestroy(ambient_e1);
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
   if (h_check) (void)hipHostFree(h_check);

@@ -125,16 +125,17 @@ struct Partition {
 
 // The feature records of `part` of the tracer's image in rc, on the tracer's device, traced again when the camera
 // or the seed have changed since (a change of size or partition drops the buffer: Realloc, FreeImage).
-// alloc_pixels: the records the buffer is allocated for. ev: events recorded around the pass, or null; launched
-// (or null): whether a pass ran. Enqueued on the tracer's stream; the host does not wait.
-static int EnsureFeatures(rt2_tracer* t, Recon& rc, const Partition& part, size_t alloc_pixels, const EventPair* ev,
-                          bool* launched) {
+// alloc_pixels: the records the buffer is allocated for. seed: the pass's (the tracer's, or an ambient call's). ev:
+// events recorded around the pass, or null; launched (or null): whether a pass ran. Enqueued on the tracer's stream;
+// the host does not wait.
+static int EnsureFeatures(rt2_tracer* t, Recon& rc, const Partition& part, size_t alloc_pixels, uint64_t seed,
+                          const EventPair* ev, bool* launched) {
   if (launched) *launched = false;
   if (!t->stack_ok) return StackRefusal(t);
   const size_t n = (size_t)t->width * (size_t)part.local_rows;
   const CameraParams cam = t->camera.Params();
   if (n == 0) return RT2_OK;
-  if (rc.d_features && rc.features_valid && rc.features_seed == t->seed && memcmp(&rc.features_cam, &cam, sizeof(cam)) == 0)
+  if (rc.d_features && rc.features_valid && rc.features_seed == seed && memcmp(&rc.features_cam, &cam, sizeof(cam)) == 0)
     return RT2_OK;
   HIP_TRY(hipSetDevice(t->device));
   if (!rc.d_features) {
@@ -148,27 +149,43 @@ static int EnsureFeatures(rt2_tracer* t, Recon& rc, const Partition& part, size_
   p.rank = part.rank;
   p.world = part.world;
   p.local_pixels = (uint32_t)n;
+  p.seed_lo = (uint32_t)seed;  // (BaseParams took the tracer's)
+  p.seed_hi = (uint32_t)(seed >> 32);
+  for (uint32_t r = 0; r < 10; r++) {
+    p.philox_keys[2 * r] = p.seed_lo + r * 0x9E3779B9u;
+    p.philox_keys[2 * r + 1] = p.seed_hi + r * 0xBB67AE85u;
+  }
   if (ev) HIP_TRY(hipEventRecord(ev->e0, t->stream));
   HIP_TRY(LaunchFeatures(p, rc.d_features.get<float>(), t->stream));
   if (ev) HIP_TRY(hipEventRecord(ev->e1, t->stream));
   rc.features_valid = true;
   rc.features_cam = cam;
-  rc.features_seed = t->seed;
+  rc.features_seed = seed;
   if (launched) *launched = true;
   return RT2_OK;
 }
 
 // The tracer's own band, as BaseParams describes it; the buffer is as tall as the accumulation.
-static int LocalFeatures(rt2_tracer* t, const EventPair* ev, bool* launched) {
+static int LocalFeatures(rt2_tracer* t, uint64_t seed, const EventPair* ev, bool* launched) {
   const Partition own{t->local_rows, t->band_h > 0 ? t->band_h : t->height, t->rank, t->world};
-  return EnsureFeatures(t, t->recon, own, (size_t)t->width * (size_t)AllocRows(t), ev, launched);
+  return EnsureFeatures(t, t->recon, own, (size_t)t->width * (size_t)AllocRows(t), seed, ev, launched);
+}
+static int LocalFeatures(rt2_tracer* t, const EventPair* ev, bool* launched) {
+  return LocalFeatures(t, t->seed, ev, launched);
+}
+
+// (tracer.h) For rt2_tracer_ambient: the local records as traced under `seed`, no events and no wait.
+int rt2::detail::FeaturesForSeed(rt2_tracer* t, uint64_t seed, const float** d_features) {
+  int rc = LocalFeatures(t, seed, nullptr, nullptr);
+  if (rc == RT2_OK) *d_features = t->recon.d_features.get<float>();
+  return rc;
 }
 
 // The whole image on the root of a gathered image. The root traces every pixel itself: with world 1, rank 0 and
 // one band of the image's height, features_kernel's map from local to image rows is the identity.
 static int ImageFeatures(rt2_tracer* r) {
   const Partition whole{r->height, r->height, 0, 1};
-  return EnsureFeatures(r, r->image_recon, whole, (size_t)r->width * (size_t)r->height, nullptr, nullptr);
+  return EnsureFeatures(r, r->image_recon, whole, (size_t)r->width * (size_t)r->height, r->seed, nullptr, nullptr);
 }
 
 static int FeaturesTimed(rt2_tracer* t) {

@@ -1,6 +1,7 @@
 // capi_query.cpp — the ray queries of include/rt2.h ("Ray queries"): the scene's closest Hit for rays the caller
 // owns, over render.hip's query kernel, and whether anything is in their way, over its occlusion kernel. Planned by launch_plan.h PlanQuery; the layouts and the validity rule are
-// query.h's.
+// query.h's. And "Ambient occlusion": blocked-sample counts per pixel or caller point over render.hip's ambient
+// kernel, through the same buffers and chunks; planned by PlanAmbient, the rule is ambient.h's.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -8,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "ambient.h"
+#include "kernels.h"
 #include "launch_plan.h"
 #include "query.h"
 #include "tracer.h"
@@ -164,9 +167,226 @@ int DeviceQuery(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, vo
   return RT2_OK;
 }
 
+// ---- ambient occlusion (rt2.h "Ambient occlusion", ambient.h) ----
+
+// (the arguments first, as CheckCall: samples, then n and the pointers, then the tracer)
+int CheckAmbient(const rt2_tracer* t, int samples, int64_t n, const void* points, const void* out, const char* call) {
+  if (samples < 1 || samples > kAmbientMaxSamples)
+    return Fail(RT2_ERR_INVALID, std::string(call) + ": need 1 <= samples <= 65535");
+  return CheckCall(t, n, points, out, call);
+}
+
+// What an image call checks before it touches the device.
+int CheckAmbientImage(const rt2_tracer* t, int samples, float radius, const void* out, const char* call) {
+  if (!(radius > kQueryTmin) || !QueryFinite(radius))
+    return Fail(RT2_ERR_INVALID, std::string(call) + ": need a finite radius above 0.001 (FLT_MAX: unbounded)");
+  int rc = CheckAmbient(t, samples, 0, out, out, call);  // (no caller records: n and its pointer pass)
+  if (rc != RT2_OK) return rc;
+  if (t->comm) return Fail(RT2_ERR_INVALID, std::string(call) + ": not on a joined tracer (a set_partition tracer works)");
+  if (t->width <= 0 || t->height <= 0) return Fail(RT2_ERR_INVALID, std::string(call) + ": no image yet (on_resize first)");
+  return RT2_OK;
+}
+
+// Zeroes n words of d_counts and adds the samples' hits of n points of src into them: the plan's launches over
+// consecutive sample ranges, all on the tracer's stream.
+hipError_t EnqueueAmbient(const rt2_tracer* t, const RenderParams& p, const AmbientSource& src, uint32_t n, int samples,
+                          uint32_t* d_counts) {
+  const int variant = RenderVariant(t->features);
+  const AmbientPlan a = PlanAmbient(p.lin_len, variant, RenderVariantFeatures(variant), p.stack_depth, n,
+                                    (uint32_t)samples, RenderBlockSize());
+  hipError_t e = hipMemsetAsync(d_counts, 0, (size_t)n * sizeof(uint32_t), t->stream);
+  for (uint32_t l = 0; l < a.launches && e == hipSuccess; l++) {
+    const uint32_t k = l + 1u == a.launches ? a.last : a.per_launch;
+    e = LaunchAmbient(p, a.q.variant, src, n, l * a.per_launch, k, MakeMagic(k), d_counts, t->stream);
+  }
+  return e;
+}
+
+// The events of the device entries' last call (created at the first one), recorded around its kernels.
+int AmbientEvents(rt2_tracer* t) {
+  if (!t->ambient_e0 && hipEventCreate(&t->ambient_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  if (!t->ambient_e1 && hipEventCreate(&t->ambient_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  t->ambient_pending = false;
+  t->ambient_ms = -1.0;
+  return RT2_OK;
+}
+
+// A device entry's body: the events around the kernels over n points of src into d_out, no wait.
+int DeviceAmbient(rt2_tracer* t, const RenderParams& p, const AmbientSource& src, uint32_t n, int samples,
+                  uint32_t* d_out) {
+  int rc = AmbientEvents(t);
+  if (rc != RT2_OK) return rc;
+  HIP_TRY(hipEventRecord(t->ambient_e0, t->stream));
+  HIP_TRY(EnqueueAmbient(t, p, src, n, samples, d_out));
+  HIP_TRY(hipEventRecord(t->ambient_e1, t->stream));
+  t->ambient_pending = true;
+  return RT2_OK;
+}
+
+// The image calls' points: the tracer's feature records under `seed`, traced on the stream if the cache is stale.
+int ImageSource(rt2_tracer* t, float radius, uint64_t seed, AmbientSource* src) {
+  const float* d_features = nullptr;
+  int rc = FeaturesForSeed(t, seed, &d_features);
+  if (rc != RT2_OK) return rc;
+  *src = AmbientFeatureSource(d_features, radius, (uint32_t)t->width);
+  return RT2_OK;
+}
+
+// The image's launch parameters: QueryParams and the tracer's partition (BaseParams has it), which the kernel's
+// map from a local pixel to its global index reads.
+int ImageParams(const rt2_tracer* t, uint64_t seed, const char* call, RenderParams* p) {
+  QueryPlan q;
+  return QueryParams(t, seed, 1u, call, p, &q);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rt2_ambient_direction(const float* n3, const float* u3, float* d3) {
+  if (!n3 || !u3 || !d3) return Fail(RT2_ERR_INVALID, "ambient_direction: null pointer");
+  AmbientDirection(n3, u3, d3);
+  return RT2_OK;
+}
+
+int rt2_tracer_ambient(rt2_tracer* t, int samples, float radius, uint64_t seed, uint32_t* out) {
+  const char* call = "ambient";
+  int rc = CheckAmbientImage(t, samples, radius, out, call);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  RenderParams p;
+  if ((rc = ImageParams(t, seed, call, &p)) != RT2_OK) return rc;
+  if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
+  HIP_TRY(hipSetDevice(t->device));
+  AmbientSource src;
+  if ((rc = ImageSource(t, radius, seed, &src)) != RT2_OK) return rc;
+  if (n * sizeof(uint32_t) > t->d_query_hits.bytes()) {
+    HIP_TRY(t->d_query_hits.Grow(n * sizeof(uint32_t)));
+    NoteDeviceBytes(t);
+  }
+  EventPair ev(t);
+  if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
+  uint32_t* d_counts = t->d_query_hits.get<uint32_t>();
+  hipError_t e = hipEventRecord(ev.e0, t->stream);
+  if (e == hipSuccess) e = EnqueueAmbient(t, p, src, (uint32_t)n, samples, d_counts);
+  if (e == hipSuccess) e = hipEventRecord(ev.e1, t->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, call);
+  float f = -1.0f;
+  if (hipEventElapsedTime(&f, ev.e0, ev.e1) != hipSuccess) f = -1.0f;
+  t->ambient_pending = false;
+  t->ambient_ms = (double)f;
+  return RT2_OK;
+}
+
+int rt2_tracer_ambient_device(rt2_tracer* t, int samples, float radius, uint64_t seed, uint32_t* d_out) {
+  const char* call = "ambient_device";
+  int rc = CheckAmbientImage(t, samples, radius, d_out, call);
+  if (rc != RT2_OK) return rc;
+  const size_t n = (size_t)t->width * (size_t)t->local_rows;
+  if (n == 0) return RT2_OK;
+  RenderParams p;
+  if ((rc = ImageParams(t, seed, call, &p)) != RT2_OK) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  AmbientSource src;
+  if ((rc = ImageSource(t, radius, seed, &src)) != RT2_OK) return rc;
+  return DeviceAmbient(t, p, src, (uint32_t)n, samples, d_out);
+}
+
+int rt2_tracer_ambient_points(rt2_tracer* t, int64_t n, const float* points, int samples, uint64_t seed, uint32_t* out) {
+  const char* call = "ambient_points";
+  int rc = CheckAmbient(t, samples, n, points, out, call);
+  if (rc != RT2_OK) return rc;
+  if (n == 0) return RT2_OK;
+  const int64_t chunk = std::min(QueryChunk(), (n + 63) / 64 * 64);
+  RenderParams p;
+  QueryPlan q;
+  if ((rc = QueryParams(t, seed, 1u, call, &p, &q)) != RT2_OK) return rc;
+  if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
+  HIP_TRY(hipSetDevice(t->device));
+  const size_t in_bytes = (size_t)chunk * kQueryRayFloats * sizeof(float);
+  const size_t out_bytes = (size_t)chunk * sizeof(uint32_t);
+  if (in_bytes > t->d_query_rays.bytes() || out_bytes > t->d_query_hits.bytes()) {
+    HIP_TRY(t->d_query_rays.Grow(in_bytes));
+    HIP_TRY(t->d_query_hits.Grow(out_bytes));
+    NoteDeviceBytes(t);
+  }
+  std::vector<hipEvent_t> ev;  // one pair per chunk, back to the tracer's pool on every way out
+  struct Return {
+    rt2_tracer* t;
+    std::vector<hipEvent_t>& ev;
+    ~Return() {
+      for (hipEvent_t e : ev) t->event_pool.push_back(e);
+    }
+  } give_back{t, ev};
+  uint32_t* d_counts = t->d_query_hits.get<uint32_t>();
+  hipError_t e = hipSuccess;
+  for (int64_t at = 0; at < n && e == hipSuccess; at += chunk) {
+    const uint32_t m = (uint32_t)std::min(chunk, n - at);
+    hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
+    if (e0) ev.push_back(e0);
+    if (e1) ev.push_back(e1);
+    if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
+    e = hipMemcpyAsync(t->d_query_rays.get<float>(), points + (size_t)at * kQueryRayFloats,
+                       (size_t)m * kQueryRayFloats * sizeof(float), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipEventRecord(e0, t->stream);
+    if (e == hipSuccess)
+      e = EnqueueAmbient(t, p, AmbientRecordSource(t->d_query_rays.get<float>(), (uint32_t)at), m, samples, d_counts);
+    if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(out + at, d_counts, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, call);
+  double ms = 0.0;
+  for (size_t k = 0; k + 1 < ev.size(); k += 2) {
+    float f = 0.0f;
+    if (hipEventElapsedTime(&f, ev[k], ev[k + 1]) != hipSuccess) {
+      ms = -1.0;
+      break;
+    }
+    ms += (double)f;
+  }
+  t->ambient_pending = false;
+  t->ambient_ms = ms;
+  return RT2_OK;
+}
+
+int rt2_tracer_ambient_points_device(rt2_tracer* t, int64_t n, const float* d_points, int samples, uint64_t seed,
+                                     uint32_t* d_out) {
+  const char* call = "ambient_points_device";
+  int rc = CheckAmbient(t, samples, n, d_points, d_out, call);
+  if (rc != RT2_OK) return rc;
+  if (n == 0) return RT2_OK;
+  RenderParams p;
+  QueryPlan q;
+  if ((rc = QueryParams(t, seed, 1u, call, &p, &q)) != RT2_OK) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  return DeviceAmbient(t, p, AmbientRecordSource(d_points, 0u), (uint32_t)n, samples, d_out);
+}
+
+int rt2_tracer_ambient_time(rt2_tracer* t, double* ms) {
+  if (!t || !ms) return Fail(RT2_ERR_INVALID, "ambient_time: null argument");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "ambient_time: not on a create_multi tracer");
+  if (t->ambient_pending) {
+    HIP_TRY(hipSetDevice(t->device));
+    const hipError_t q = hipEventQuery(t->ambient_e1);
+    if (q == hipSuccess) {
+      float f = -1.0f;
+      if (hipEventElapsedTime(&f, t->ambient_e0, t->ambient_e1) != hipSuccess) f = -1.0f;
+      t->ambient_ms = (double)f;
+      t->ambient_pending = false;
+    } else if (q != hipErrorNotReady) {
+      return HipFail(q, "ambient_time");
+    }
+  }
+  *ms = t->ambient_pending ? -1.0 : t->ambient_ms;
+  return RT2_OK;
+}
 
 int rt2_query_ray_valid(const float* ray8) { return ray8 && QueryRayValid(ray8) ? 1 : 0; }
 

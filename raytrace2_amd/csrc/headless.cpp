@@ -11,6 +11,11 @@
 // --pick X Y renders nothing and writes no image: it prints the hit record (rt2.h "Ray queries": 16 floats, the
 // feature record's layout) of the ray through the centre of pixel (X, Y) of a W x H image (default: the
 // scene's dims, else 1600x900) as one JSON line: the record RayTracer::Features holds for that pixel.
+//
+//   rt2_headless <scene.json> <out.png> --ao SAMPLES [--ao-radius R] [--size WxH]
+// --ao SAMPLES renders nothing: it writes the ambient-occlusion visibility of the image's first hits (rt2.h "Ambient
+// occlusion": RayTracer::Ambient with SAMPLES samples within R, default unbounded) as a grey image, 1 - count /
+// SAMPLES in float per pixel and 1 where the pixel's ray missed, through WriteImage as every other image.
 // Without --settings the reference's Settings.hpp defaults apply (num_samples 1, max_depth 50);
 // --samples / --size override num_samples and the output dims (App.cpp:115-124: scene dims, else
 // 1600x900). --gpus N renders on GPUs 0..N-1 (row bands + RCCL gather, rt2_tracer_create_multi).
@@ -34,6 +39,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include <rt2/RayTracer.hpp>
 
@@ -42,9 +48,9 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "usage: %s <scene.json> <out.png> [--settings f] [--samples N] [--size WxH] [--gpus N] "
                          "[--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]] "
                          "[--denoise [--denoise-iterations N]] (--denoise with --gpus N filters the gathered image)\n"
+                         "       %s <scene.json> <out.png> --ao SAMPLES [--ao-radius R] [--size WxH]\n"
                          "       %s <scene.json> --pick X Y [--size W H]\n",
-                 argv[0],
-                 argv[0]);
+                 argv[0], argv[0], argv[0]);
     return 2;
   }
   // (--pick: no output image, the options start right after the scene)
@@ -62,6 +68,8 @@ int main(int argc, char** argv) {
   int denoise_iterations = 0;  // 0: the default
   bool pick = false;
   rt2::ivec2 pick_at{0, 0};
+  int ao_samples = 0;  // > 0: write the ambient-occlusion visibility instead of a render
+  float ao_radius = FLT_MAX;
   try {
     for (int i = no_image ? 2 : 3; i < argc; i += 2) {
       if (!std::strcmp(argv[i], "--denoise")) {  // a flag: no value follows
@@ -98,6 +106,18 @@ int main(int argc, char** argv) {
         window = (int)v;
       } else if (!std::strcmp(argv[i], "--max-samples")) {
         max_samples = std::atol(argv[i + 1]);
+      } else if (!std::strcmp(argv[i], "--ao")) {
+        ao_samples = std::atoi(argv[i + 1]);
+        if (ao_samples < 1 || ao_samples > 65535) {
+          std::fprintf(stderr, "--ao needs an integer in [1, 65535]\n");
+          return 2;
+        }
+      } else if (!std::strcmp(argv[i], "--ao-radius")) {
+        ao_radius = std::strtof(argv[i + 1], nullptr);
+        if (!(ao_radius > 0.001f) || std::isinf(ao_radius)) {
+          std::fprintf(stderr, "--ao-radius needs a finite number above 0.001\n");
+          return 2;
+        }
       } else if (!std::strcmp(argv[i], "--pick")) {  // two values follow
         if (i + 2 >= argc || std::sscanf(argv[i + 1], "%d", &pick_at.x) != 1 || std::sscanf(argv[i + 2], "%d", &pick_at.y) != 1)
           return 2;
@@ -162,6 +182,32 @@ int main(int argc, char** argv) {
         std::printf("%s%s%s", k ? ", " : "", num, integral ? ".0" : "");
       }
       std::printf("]}\n");
+      return 0;
+    }
+
+    if (ao_samples > 0) {
+      if (no_image || gpus > 0) {
+        std::fprintf(stderr, "--ao writes an image from one GPU\n");
+        return 2;
+      }
+      rt2::RayTracer ao(scene, 0);
+      scene.cam.SetSamplesPerPixel((int)settings.num_samples);
+      ao.camera = &scene.cam;
+      ao.OnResize(dims);
+      std::vector<uint32_t> counts((size_t)dims.x * (size_t)dims.y);
+      ao.Ambient(ao_samples, ao_radius, counts.data());
+      std::vector<rt2::vec3> grey(counts.size());
+      unsigned long long blocked = 0, hit_pixels = 0;
+      for (size_t k = 0; k < counts.size(); k++) {
+        const bool miss = counts[k] == 0xFFFFFFFFu;
+        const float v = miss ? 1.0f : 1.0f - (float)counts[k] / (float)ao_samples;
+        grey[k] = rt2::vec3{v, v, v};
+        if (!miss) blocked += counts[k], hit_pixels++;
+      }
+      rt2::util::WriteImage(grey, dims.x, dims.y, out_path);
+      std::printf("{\"ao_samples\": %d, \"width\": %d, \"height\": %d, \"hit_pixels\": %llu, \"blocked\": %llu, "
+                  "\"kernel_ms\": %.3f}\n",
+                  ao_samples, dims.x, dims.y, hit_pixels, blocked, ao.AmbientTime());
       return 0;
     }
 

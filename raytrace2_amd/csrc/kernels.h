@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "adaptive.h"
+#include "ambient.h"
 #include "denoise.h"
 #include "noise.h"
 #include "rt2_layout.h"
@@ -27,6 +28,8 @@ hipError_t LaunchFeatures(const RenderParams& p, float* out, hipStream_t stream)
 hipError_t LaunchQuery(const RenderParams& p, int variant, const float* rays, float* out, uint32_t n, hipStream_t stream);
 hipError_t LaunchOcclusion(const RenderParams& p, int variant, const float* rays, int8_t* out, uint32_t n,
                            hipStream_t stream);
+hipError_t LaunchAmbient(const RenderParams& p, int variant, const AmbientSource& src, uint32_t n_points, uint32_t s0,
+                         uint32_t k, Magic k_div, uint32_t* counts, hipStream_t stream);
 size_t QueryLdsBytes(const RenderParams& p);
 int RenderMode(const RenderParams& p);
 int RenderBlockSize();

@@ -159,4 +159,23 @@ inline QueryPlan PlanQuery(uint32_t lin_len, int variant, uint32_t variant_featu
   return q;
 }
 
+// An ambient-occlusion call (rt2.h "Ambient occlusion"; render.hip ambient_kernel) over `points` points, 0 <
+// points < 2^31, of `samples` samples each, 1 <= samples <= 65535. Work items are (point, sample): a launch takes
+// per_launch consecutive samples of every point, as many as keep points x per_launch below 2^31, and the call is
+// `launches` launches over consecutive sample ranges (the last one takes last samples). The counts are integer
+// sums, so the split does not show in the result. The walk, variant and LDS: as PlanQuery over one launch's items.
+struct AmbientPlan {
+  QueryPlan q;  // of a launch of per_launch samples
+  uint32_t per_launch, launches, last;
+};
+inline AmbientPlan PlanAmbient(uint32_t lin_len, int variant, uint32_t variant_features, int stack_depth,
+                               uint32_t points, uint32_t samples, int block) {
+  AmbientPlan a;
+  a.per_launch = std::min<uint32_t>(samples, 0x7FFFFFFFu / points);
+  a.launches = (samples + a.per_launch - 1u) / a.per_launch;
+  a.last = samples - (a.launches - 1u) * a.per_launch;
+  a.q = PlanQuery(lin_len, variant, variant_features, stack_depth, points * a.per_launch, block);
+  return a;
+}
+
 }  // namespace rt2

@@ -3369,6 +3369,111 @@ OcclusionFn OcclusionKernel(int v, bool threaded) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Ambient occlusion (rt2.h "Ambient occlusion", ambient.h): per point the number of its k_launch
+// samples [s0, s0 + k_launch) whose occlusion ray is blocked, added into counts[point] (zeroed on the stream
+// before the first launch of a call). A work item is (point, sample), the sample index fastest, so the lanes of a
+// wave share a point or a few neighbouring ones and the record loads are broadcasts. A point is `stride` words
+// at recs: its position at off_p, its normal at off_n; feature records (stride 16, a miss where slot 0 is 0) take
+// tmax = radius and time 0, caller records (stride 8) carry both in words 3 and 7. The stream index of a point is
+// index0 + its index, or with width != 0 the global pixel index of local pixel `point` (features_kernel's row map). The
+// sample's direction is ambient.h's, its unit vector the first draw of the path stream (seed, index,
+// kAmbientFrame0 + s); the ray is traced as occlusion_kernel traces a caller's (same masking, whole-wave skip,
+// medium stream and choice of walk). Counts: the wave's ballot of hits, popcounted over the lanes that share a
+// point by that point's first lane in the wave, one integer atomic add per (wave, point) and none for a zero.
+// An invalid point gets kAmbientInvalid from the lane of its sample 0 (nothing is ever added to it).
+template <uint32_t F, int kMode>
+__global__ __launch_bounds__(kBlock) void ambient_kernel(const RenderParams P, const float* __restrict__ recs,
+                                                         uint32_t stride, uint32_t off_p, uint32_t off_n, float radius,
+                                                         uint32_t width, uint32_t index0, uint32_t n_points, uint32_t s0,
+                                                         uint32_t k_launch, Magic k_div,
+                                                         uint32_t* __restrict__ counts) {
+  static_assert(kMode == kModeLinear || kMode == kModeStackGlobal, "threaded program or global-memory stack walk");
+  const uint32_t w = blockIdx.x * (uint32_t)kBlock + threadIdx.x;  // n_points * k_launch < 2^31 (PlanAmbient)
+  const bool in = w < n_points * k_launch;
+  const uint32_t pt = in ? udiv(w, k_div) : 0u;
+  const uint32_t ls = w - pt * k_launch;  // the sample within this launch
+  float r[kQueryRayFloats] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool point_ok = false, valid = false;
+  if (in) {
+    const float* rec = recs + (size_t)pt * stride;
+    const bool image = stride == kAmbientFeatureStride;
+    float pr[kQueryRayFloats];
+    pr[kQrOx] = rec[off_p], pr[kQrOy] = rec[off_p + 1u], pr[kQrOz] = rec[off_p + 2u];
+    pr[kQrTmax] = image ? radius : rec[kQrTmax];
+    pr[kQrDx] = rec[off_n], pr[kQrDy] = rec[off_n + 1u], pr[kQrDz] = rec[off_n + 2u];
+    pr[kQrTime] = image ? 0.0f : rec[kQrTime];
+    point_ok = QueryRayValid(pr) && !(image && rec[0] == 0.0f);
+    if (point_ok) {
+      uint32_t gi = index0 + pt;
+      if (width != 0u) {  // local row -> global row, as features_kernel
+        const uint32_t lr = pt / width, x = pt - lr * width;
+        const uint32_t bh = (uint32_t)P.band_h, world = (uint32_t)P.world;
+        const uint32_t period = lr / bh;
+        const uint32_t phase = ((uint32_t)P.rank + world - period % world) % world;
+        gi = ((period * world + phase) * bh + lr % bh) * width + x;
+      }
+      PathT<false> draw;
+      draw.rb = nullptr;
+      draw.pix = gi;
+      draw.sij = 0;
+      draw.r0 = draw.r1 = draw.r2 = draw.r3 = 0;
+      draw.start(kAmbientFrame0 + s0 + ls);
+      const f3 u = rand_unit_vec3(draw);
+      const float uu[3] = {u.x, u.y, u.z};
+      AmbientRay(pr, uu, r);
+      valid = QueryRayValid(r);
+    }
+  }
+  const f3 ro = mk(r[kQrOx], r[kQrOy], r[kQrOz]), rd = mk(r[kQrDx], r[kQrDy], r[kQrDz]);
+  const float time = r[kQrTime];
+  lds_u32* cand = nullptr;  // the wave's box-boundary candidate planes, as the query kernel's
+  if constexpr (BoxPair<F, kMode>()) {
+    __shared__ uint32_t s_cand[(kBlock / 64) * kBoundaryAAMax * 64];
+    cand = wave_planes((lds_u32*)(s_cand), kBoundaryAAMax);
+  }
+  bool hit = false;
+  if (__ballot(valid) != 0ull) {
+    if (valid) {
+      PathT<false> path = probe_path();
+      Counters cnt = {};
+      HitRef h{0.0f, kRefNone, kRefNone};  // (not read: the trace's flag is the answer)
+      if constexpr (kMode == kModeLinear) {
+        hit = trace_linear<F, false, false, true, true>(P, RegRay{ro, rd}, time, path, h, cand, nullptr, cnt, false,
+                                                        nullptr, r[kQrTmax]);
+      } else {
+        uint32_t* stk = reinterpret_cast<uint32_t*>(s_dyn) + threadIdx.x;
+        const Nodes<kModeStackGlobal> N{reinterpret_cast<const float4*>(P.nodes), 0u};
+        bool overflow = false;  // (the launcher refuses a scene whose stack is deeper than the kernel's)
+        hit = trace_stack<F, kModeStackGlobal, false, true, true>(P, N, ro, rd, time, path, h, stk, cnt, overflow,
+                                                                  r[kQrTmax]);
+      }
+    }
+  }
+  const unsigned long long hits = __ballot(hit);
+  if (!in) return;
+  if (!point_ok) {
+    if (s0 + ls == 0u) counts[pt] = kAmbientInvalid;
+    return;
+  }
+  // the point's first lane in this wave adds the hits of the point's lanes: [lane, lane + len)
+  const uint32_t lane = threadIdx.x & 63u;
+  if (lane != 0u && ls != 0u) return;
+  const uint32_t left = k_launch - ls, room = 64u - lane;
+  const uint32_t len = left < room ? left : room;
+  const unsigned long long mask = (len == 64u ? ~0ull : ((1ull << len) - 1ull)) << lane;
+  const uint32_t c = (uint32_t)__popcll(hits & mask);
+  if (c != 0u) atomicAdd(counts + pt, c);
+}
+
+using AmbientFn = void (*)(RenderParams, const float*, uint32_t, uint32_t, uint32_t, float, uint32_t, uint32_t, uint32_t,
+                           uint32_t, uint32_t, Magic, uint32_t*);
+// chosen as OcclusionKernel chooses
+AmbientFn AmbientKernel(int v, bool threaded) {
+  if (!threaded) return &ambient_kernel<kFeatAll, kModeStackGlobal>;
+  return WithVariant(v, [](auto V) -> AmbientFn { return &ambient_kernel<kVariants[V], kModeLinear>; });
+}
+
+// ------------------------------------------------------------------------------------------
 // Self-tests of the kernel's exact shortcuts on random inputs (rt2_selftest):
 //   which 0: div_by_inv(a, b, fl(1/b)) == a / b for |b| > 1e-8, |a / b| >= 1e-3 (accepted quad t)
 //   which 3: the same for any quotient with 2^-100 <= |a| < 2^21 (medium box boundaries, any t)
@@ -3672,6 +3777,20 @@ hipError_t LaunchQuery(const RenderParams& p, int variant, const float* rays, fl
 hipError_t LaunchOcclusion(const RenderParams& p, int variant, const float* rays, int8_t* out, uint32_t n,
                            hipStream_t stream) {
   return LaunchProbe(dev::OcclusionKernel(variant, p.lin_len != 0), p, rays, out, n, stream);
+}
+
+// The ambient kernel over the samples [s0, s0 + k) of n_points points of src, added into counts (n_points words,
+// zeroed on the stream before a call's first launch). n_points * k < 2^31 (launch_plan.h PlanAmbient); k_div:
+// MakeMagic(k). p and the choice of walk: as LaunchQuery.
+hipError_t LaunchAmbient(const RenderParams& p, int variant, const AmbientSource& src, uint32_t n_points, uint32_t s0,
+                         uint32_t k, Magic k_div, uint32_t* counts, hipStream_t stream) {
+  if (n_points == 0 || k == 0) return hipSuccess;
+  const dev::AmbientFn fn = dev::AmbientKernel(variant, p.lin_len != 0);
+  if (!fn || (uint64_t)n_points * k > 0x7FFFFFFFull || (!p.lin_len && p.stack_depth > kTraversalStack))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fn, dim3(QueryGrid(n_points * k, (uint32_t)dev::kBlock)), dim3(dev::kBlock), QueryLdsBytes(p), stream,
+                     p, src.recs, src.stride, src.off_p, src.off_n, src.radius, src.width, src.index0, n_points, s0, k, k_div, counts);
+  return hipGetLastError();
 }
 
 hipError_t LaunchSelftest(int which, unsigned long long n, uint32_t seed, unsigned long long* d_out, hipStream_t stream) {

@@ -257,6 +257,11 @@ struct rt2_tracer {
   hipEvent_t query_e0 = nullptr, query_e1 = nullptr;
   bool query_pending = false;
   double query_ms = -1.0;
+  // ambient occlusion (rt2.h "Ambient occlusion"): the same for its calls (rt2_tracer_ambient_time); the counts and
+  // the host entry's points go through the two query buffers above
+  hipEvent_t ambient_e0 = nullptr, ambient_e1 = nullptr;
+  bool ambient_pending = false;
+  double ambient_ms = -1.0;
   rt2::DeviceBuffer d_work;  // one work counter per launch slot (words 0 and 16)
   rt2::DeviceBuffer d_stats;
   bool stats_on = false;
@@ -399,6 +404,9 @@ int EnqueueAdaptiveCheck(rt2_tracer* t, float threshold, int window, rt2::Adapti
                          rt2::AdaptiveTotals** d_totals);
 int FinishAdaptiveCheck(rt2_tracer* t, const rt2::AdaptiveTotals& h, rt2_adaptive* out);
 int SampleCountsLocal(rt2_tracer* t, uint32_t* out);  // n_p per local pixel of an adaptive one-GPU tracer (blocks)
+// capi_filter.cpp: the cached feature records of a one-GPU tracer's local rows as traced under `seed` (the cache
+// is keyed by camera, size, partition and seed), traced again on the tracer's stream where stale; no host wait.
+int FeaturesForSeed(rt2_tracer* t, uint64_t seed, const float** d_features);
 // capi_multi.cpp
 int GatherMulti(rt2_tracer* t);
 int GatherEstimate(rt2_tracer* t);  // rt2_tracer_gather_estimate: the gather with the sums of squares

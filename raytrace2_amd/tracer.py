@@ -21,6 +21,8 @@ from ._native import (UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Nois
                       TemporalParams, check, lib)
 
 DEFAULT_SEED = 0x5EED2024
+FLT_MAX = float(np.finfo(np.float32).max)
+AMBIENT_INVALID = np.uint32(0xFFFFFFFF)  # ambient_counts / ambient_points: a miss pixel, an invalid point
 
 
 def _fp(a: np.ndarray):
@@ -712,6 +714,64 @@ class RayTracer:
         waits."""
         ms = ctypes.c_double(-1.0)
         check(lib.rt2_tracer_intersect_time(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    # -- ambient occlusion (rt2.h "Ambient occlusion") ---------------------------------------------
+    def ambient_counts(self, samples: int, radius: float = FLT_MAX, seed: Optional[int] = None) -> np.ndarray:
+        """Per local pixel the number of `samples` cosine-weighted occlusion rays from its first hit (features())
+        that are blocked within `radius`: (rows, W) uint32, 0xFFFFFFFF where the pixel's ray missed. Drawn and
+        traced on the GPU by the rule of rt2.h "Ambient occlusion"; seed (default: the tracer's) keys the samples,
+        a ConstantMedium's draws and the feature pass. A readback: queued frames are launched first."""
+        self._push_camera()
+        seed = self._seed if seed is None else int(seed)
+        w, _ = self.Dims()
+        out = np.zeros((max(self.local_rows(), 0), w), np.uint32)
+        check(lib.rt2_tracer_ambient(self._h, int(samples), float(radius), seed,
+                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def ambient(self, samples: int, radius: float = FLT_MAX, seed: Optional[int] = None) -> np.ndarray:
+        """The visibility 1 - count / samples of ambient_counts() in float32, (rows, W); 1.0 where the pixel's
+        ray missed."""
+        c = self.ambient_counts(samples, radius, seed)
+        vis = np.float32(1) - c.astype(np.float32) / np.float32(samples)
+        return np.where(c == AMBIENT_INVALID, np.float32(1), vis).astype(np.float32)
+
+    def ambient_points(self, points, samples: int, seed: Optional[int] = None):
+        """The blocked-sample counts of caller points: points (n, 8) float32, px py pz tmax nx ny nz time ->
+        (n,) uint32, 0xFFFFFFFF for a point outside ray_valid's domain (the normal as the direction). The stream
+        index of a point is its row. A numpy array goes through the host entry and a numpy array comes back; a CUDA
+        torch tensor on the tracer's device goes through the device entry into a new int32 tensor holding the
+        uint32 words, complete on return."""
+        seed = self._seed if seed is None else int(seed)
+        if not isinstance(points, np.ndarray) and hasattr(points, "is_cuda"):
+            import torch
+            if not points.is_cuda or points.device.index != self.device:
+                raise ValueError(f"ambient_points: need a tensor on cuda:{self.device}")
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 8:
+                raise ValueError("ambient_points: need points (n, 8) float32")
+            points = points.contiguous()
+            out = torch.empty((points.shape[0],), dtype=torch.int32, device=points.device)
+            if points.shape[0] == 0:
+                return out
+            torch.cuda.current_stream(points.device).synchronize()  # the points are written; `out` is allocated
+            check(lib.rt2_tracer_ambient_points_device(self._h, points.shape[0], ctypes.c_void_p(points.data_ptr()),
+                                                       int(samples), seed, ctypes.c_void_p(out.data_ptr())))
+            self.synchronize()
+            return out
+        points = np.ascontiguousarray(points, np.float32)
+        if points.ndim != 2 or points.shape[1] != 8:
+            raise ValueError("ambient_points: need points (n, 8) float32")
+        out = np.zeros((points.shape[0],), np.uint32)
+        if points.shape[0]:
+            check(lib.rt2_tracer_ambient_points(self._h, points.shape[0], _fp(points), int(samples), seed,
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def ambient_time(self) -> float:
+        """GPU ms of the last ambient call's kernels (-1: not finished yet, or none). Never waits."""
+        ms = ctypes.c_double(-1.0)
+        check(lib.rt2_tracer_ambient_time(self._h, ctypes.byref(ms)))
         return ms.value
 
     # -- temporal reuse (rt2.h "Temporal reuse") ------------------------------------------------
