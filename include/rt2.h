@@ -754,6 +754,57 @@ RT2_API int rt2_tracer_ambient_points_device(rt2_tracer* tr, int64_t n, const fl
                                              uint64_t seed, uint32_t* d_out);
 RT2_API int rt2_tracer_ambient_time(rt2_tracer* tr, double* ms);
 
+/* ---- Radiance queries ----
+ * Opt-in: a tracer that never calls these allocates nothing new and launches what it launched before.
+ * The radiance RayColor returns along rays the caller owns, path-traced on the GPU (raytrace2_amd/csrc/radiance.h
+ * holds the rule; the kernels and the host test evaluate that one text).
+ * A ray, 8 floats, the ray record of "Ray queries": ox oy oz tmax | dx dy dz time, valid iff rt2_query_ray_valid.
+ * Stream words: each ray has two uint32_t (pixel word, frame word), streams[i][0..1]; with streams == NULL they are
+ *   (i, 0x40000000), i the ray's index in the call: clear of the render's frame indices and of ambient's
+ *   0x80000000 + s.
+ * Sample s of ray i, s in [0, samples): open the path stream (seed, pixel word, frame word + s), discard its first
+ *   first_draw uniforms, and run RayColorForward for max_depth on the ray. The first segment's interval is (0.001,
+ *   tmax), every later one's (0.001, FLT_MAX); the direction is taken as given, as intersect takes it; a
+ *   ConstantMedium draws from the sample's own stream, as in a render, not from the probe stream of the other
+ *   queries. The sample is thr * emission, thr * background, or 0 when the depth runs out.
+ *   With the camera's own ray for pixel (x, y) at frame f (normalised direction, tmax = FLT_MAX), the words (y * width
+ *   + x, f), first_draw = 3 (5 with defocus: the draws Camera::GetRay took) and the tracer's seed, a sample is, bit
+ *   for bit, that frame's sample of that pixel in a render.
+ * out_sum: 3 floats per ray, ((0 + sample_0) + sample_1) + ..., each addition rounded on its own (the render's
+ *   accumulation); the caller divides. out_rays (may be NULL): one uint32_t per ray, the rays cast (RayColor entries
+ *   with depth > 0) over the samples, the render's ray_counts. An invalid ray answers 0, 0, 0 and 0xFFFFFFFF.
+ * rt2_radiance_params (NULL: defaults): samples 1..65535 (1); max_depth 1..65535, 0 = the tracer's (0); first_draw
+ *   0..8 (0). frame word + samples must not pass 2^32: the host entry checks its streams and refuses; for the device
+ *   entry that is the caller's duty (the frame word wraps).
+ * radiance: host pointers. It behaves as intersect: it launches queued frames, goes in chunks of RT2_QUERY_CHUNK
+ *   rays through the tracer's query buffers and a slot buffer (16 bytes per (ray, sample) of a launch, at most
+ *   RT2_RADIANCE_ITEMS of them, default 2^24 = 256 MiB, at most 2^28; a larger chunk is split by sample ranges, then by ray ranges, and the
+ *   ordered sum continues across the ranges, so the split does not show), and waits once.
+ * radiance_device: device pointers on the tracer's device; d_streams and d_out_rays may be NULL. It only enqueues on
+ *   the tracer's stream, writes exactly n results, adds nothing to rt2_stats.host_waits and is complete when
+ *   rt2_tracer_query returns 1.
+ * radiance_time: GPU time (HIP events) of the last radiance call's kernels in ms; -1 while that call has not
+ *   finished, or when there was none. It polls and never waits.
+ * RT2_RADIANCE_REFILL=0 (read at every call) gives every lane exactly one (ray, sample) instead of letting lanes
+ *   whose path ended take further ones; the bytes are the same.
+ * A call changes no render state and a second call returns the same bytes. n == 0 is RT2_OK and does nothing. The
+ *   calls work before on_resize and on set_partition and joined tracers.
+ * RT2_ERR_INVALID: samples, max_depth or first_draw out of range; n < 0 or n >= 2^31; a NULL rays, out_sum or
+ *   tracer; a frame word that would wrap (host entry); a create_multi tracer; what intersect refuses for the
+ *   scene's stack depth. A refused call changes nothing. */
+typedef struct {
+  int samples;
+  int max_depth;
+  uint32_t first_draw;
+} rt2_radiance_params;
+RT2_API void rt2_radiance_defaults(rt2_radiance_params* p);
+RT2_API int rt2_tracer_radiance(rt2_tracer* tr, int64_t n, const float* rays, const uint32_t* streams,
+                                const rt2_radiance_params* p, uint64_t seed, float* out_sum, uint32_t* out_rays);
+RT2_API int rt2_tracer_radiance_device(rt2_tracer* tr, int64_t n, const float* d_rays, const uint32_t* d_streams,
+                                       const rt2_radiance_params* p, uint64_t seed, float* d_out_sum,
+                                       uint32_t* d_out_rays);
+RT2_API int rt2_tracer_radiance_time(rt2_tracer* tr, double* ms);
+
 /* Diagnostic: checks the kernel's exact arithmetic shortcuts against their reference form on n
  * random inputs on `device` (which 0: division by a correctly rounded reciprocal, accepted quad
  * distances; which 1: the NaN-free slab test; which 2: reciprocal and square root without range

@@ -478,6 +478,32 @@ class RayTracer {
     Check(rt2_tracer_ambient_time(t_.get(), &ms));
     return ms;
   }
+  // Radiance queries (rt2.h "Radiance queries"): RayColorForward along n rays of the caller (8 floats each, as
+  // Intersect's), summed over params.samples paths per ray: 3 floats per ray into out_sum (the caller divides) and,
+  // where out_rays is not null, the rays cast (0xFFFFFFFF for an invalid ray, whose sum is 0). streams: two uint32_t
+  // (pixel word, frame word) per ray, or null for (index, 0x40000000). Radiance: host buffers; it runs the queued
+  // frames and blocks. RadianceDevice: device pointers; it only enqueues and is complete when Query() returns true.
+  // RadianceTime: GPU ms of the last call's kernels (-1: not finished yet, or none); never waits.
+  [[nodiscard]] static rt2_radiance_params RadianceDefaults() {
+    rt2_radiance_params p;
+    rt2_radiance_defaults(&p);
+    return p;
+  }
+  void Radiance(const float* rays, int64_t n, float* out_sum, uint32_t* out_rays = nullptr,
+                const rt2_radiance_params& params = RadianceDefaults(), const uint32_t* streams = nullptr,
+                uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_radiance(t_.get(), n, rays, streams, &params, seed, out_sum, out_rays));
+  }
+  void RadianceDevice(const float* d_rays, int64_t n, float* d_out_sum, uint32_t* d_out_rays = nullptr,
+                      const rt2_radiance_params& params = RadianceDefaults(), const uint32_t* d_streams = nullptr,
+                      uint64_t seed = kDefaultSeed) {
+    Check(rt2_tracer_radiance_device(t_.get(), n, d_rays, d_streams, &params, seed, d_out_sum, d_out_rays));
+  }
+  [[nodiscard]] double RadianceTime() {
+    double ms = -1.0;
+    Check(rt2_tracer_radiance_time(t_.get(), &ms));
+    return ms;
+  }
   [[nodiscard]] bool Query() {
     const int q = rt2_tracer_query(t_.get());
     Check(q);

@@ -133,6 +133,11 @@ class PresentParams(ctypes.Structure):
                 "dp": self.dp.as_dict()}
 
 
+class RadianceParams(ctypes.Structure):
+    """rt2_radiance_params."""
+    _fields_ = [("samples", ctypes.c_int), ("max_depth", ctypes.c_int), ("first_draw", ctypes.c_uint32)]
+
+
 def declared_symbols(header: str = HEADER_PATH):
     """Every RT2_API function name declared in include/rt2.h."""
     txt = open(header).read()
@@ -280,6 +285,11 @@ def _load():
         "rt2_tracer_ambient_points": (i32, [vp, i64, fp, i32, u64, ctypes.POINTER(ctypes.c_uint32)]),
         "rt2_tracer_ambient_points_device": (i32, [vp, i64, vp, i32, u64, vp]),
         "rt2_tracer_ambient_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
+        "rt2_radiance_defaults": (None, [ctypes.POINTER(RadianceParams)]),
+        "rt2_tracer_radiance": (i32, [vp, i64, fp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(RadianceParams), u64,
+                                      fp, ctypes.POINTER(ctypes.c_uint32)]),
+        "rt2_tracer_radiance_device": (i32, [vp, i64, vp, vp, ctypes.POINTER(RadianceParams), u64, vp, vp]),
+        "rt2_tracer_radiance_time": (i32, [vp, ctypes.POINTER(ctypes.c_double)]),
     }
     # RT2_ALLOW_OLD_LIB=1 (tools/ A/B runs of earlier builds only): entry points the older library lacks
     # are left out; otherwise a library that does not export every entry point is a load error

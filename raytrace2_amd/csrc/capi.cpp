@@ -54,7 +54,7 @@ template <typename T, typename Fn>
 static void ForSceneBuffers(T* t, Fn&& f) {
   for (auto* d : {&t->d_nodes, &t->d_materials, &t->d_textures, &t->d_perlin_vec, &t->d_perlin_perm, &t->d_lin,
                   &t->d_lin_wide, &t->d_lind, &t->d_hit, &t->d_flat_wide, &t->d_flat_cert, &t->d_work, &t->d_stats,
-                  &t->d_query_rays, &t->d_query_hits})
+                  &t->d_query_rays, &t->d_query_hits, &t->d_radiance_slots})
     f(*d);
 }
 // The frame buffers of the local rows, with their reconstruction.
@@ -540,6 +540,8 @@ rt2_tracer::~rt2_tracer() {
   if (query_e1) (void)hipEventDestroy(query_e1);
   if (ambient_e0) (void)hipEventDestroy(ambient_e0);
   if (ambient_e1) (void)hipEventDestroy(ambient_e1);
+  if (radiance_e0) (void)hipEventDestroy(radiance_e0);
+  if (radiance_e1) (void)hipEventDestroy(radiance_e1);
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
   if (h_check) (void)hipHostFree(h_check);

@@ -1,7 +1,9 @@
 // capi_query.cpp — the ray queries of include/rt2.h ("Ray queries"): the scene's closest Hit for rays the caller
 // owns, over render.hip's query kernel, and whether anything is in their way, over its occlusion kernel. Planned by launch_plan.h PlanQuery; the layouts and the validity rule are
 // query.h's. And "Ambient occlusion": blocked-sample counts per pixel or caller point over render.hip's ambient
-// kernel, through the same buffers and chunks; planned by PlanAmbient, the rule is ambient.h's.
+// kernel, through the same buffers and chunks; planned by PlanAmbient, the rule is ambient.h's. And "Radiance
+// queries": RayColorForward along the caller's rays over render.hip's radiance kernels, through the same buffers and
+// chunks and a slot buffer; planned by PlanRadiance, the rule is radiance.h's.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -13,6 +15,7 @@
 #include "kernels.h"
 #include "launch_plan.h"
 #include "query.h"
+#include "radiance.h"
 #include "tracer.h"
 
 using namespace rt2;
@@ -239,9 +242,208 @@ int ImageParams(const rt2_tracer* t, uint64_t seed, const char* call, RenderPara
   return QueryParams(t, seed, 1u, call, p, &q);
 }
 
+
+// ---- radiance queries (rt2.h "Radiance queries", radiance.h) ----
+
+// Most (ray, sample) items per launch: RT2_RADIANCE_ITEMS, read at every call, at most kRadianceItemsEnvMax (the slot
+// buffer is allocated for a call's largest launch: 16 bytes per item).
+uint32_t RadianceItemsMax() {
+  if (const char* e = getenv("RT2_RADIANCE_ITEMS")) {
+    const long long v = atoll(e);
+    if (v > 0) return (uint32_t)std::min<long long>(v, (long long)kRadianceItemsEnvMax);
+  }
+  return kRadianceItemsDefault;
+}
+// RT2_RADIANCE_REFILL=0, read at every call: one item per lane (an A/B switch; the bytes are the same).
+bool RadianceRefill() {
+  const char* e = getenv("RT2_RADIANCE_REFILL");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+// (the arguments first, as CheckCall: the parameters, then n and the pointers, then the tracer); *a: the call's
+// parameters with the defaults and the tracer's depth filled in
+int CheckRadiance(const rt2_tracer* t, int64_t n, const void* rays, const uint32_t* host_streams,
+                  const rt2_radiance_params* p, const void* out_sum, const char* call, RadianceArgs* a) {
+  rt2_radiance_params d;
+  rt2_radiance_defaults(&d);
+  if (p) d = *p;
+  if (!RadianceArgsValid(d.samples, d.max_depth, d.first_draw))
+    return Fail(RT2_ERR_INVALID,
+                std::string(call) + ": need 1 <= samples <= 65535, 0 <= max_depth <= 65535 and first_draw <= 8");
+  // (host_streams: the host entry's stream words, whose frame words must leave room for the samples; with bad n or
+  // pointers CheckCall below refuses first)
+  if (host_streams && rays && out_sum && n > 0 && n < ((int64_t)1 << 31))
+    for (int64_t i = 0; i < n; i++)
+      if (!RadianceFrameFits(host_streams[2 * i + 1], (uint32_t)d.samples))
+        return Fail(RT2_ERR_INVALID, std::string(call) + ": frame word + samples passes 2^32 at ray " + std::to_string(i));
+  int rc = CheckCall(t, n, rays, out_sum, call);
+  if (rc != RT2_OK) return rc;
+  a->samples = (uint32_t)d.samples;
+  a->max_depth = (uint32_t)(d.max_depth ? d.max_depth : t->max_depth);
+  a->first_draw = d.first_draw;
+  return RT2_OK;
+}
+
+// The plan's launches over n rays at d_rays (d_streams may be null; index0: the stream index of ray 0) onto d_sum
+// and d_counts (may be null), all on the tracer's stream; grows the slot buffer to the plan's largest launch.
+int EnqueueRadiance(rt2_tracer* t, const RenderParams& p, const float* d_rays, const uint32_t* d_streams,
+                    uint32_t index0, uint32_t n, const RadianceArgs& a, float* d_sum, uint32_t* d_counts) {
+  const int variant = RenderVariant(t->features);
+  const int block = RenderBlockSize();
+  const RadiancePlan r = PlanRadiance(p.lin_len, variant, RenderVariantFeatures(variant), p.stack_depth, n, a.samples,
+                                      RadianceItemsMax(), block);
+  const bool refill = RadianceRefill();
+  const size_t slot_bytes = (size_t)r.rays_per_launch * r.per_launch * kRadianceSlotWords * sizeof(float);
+  if (slot_bytes > t->d_radiance_slots.bytes()) {
+    // (hipFree waits for the device: nothing queued still reads the old buffer)
+    HIP_TRY(t->d_radiance_slots.Grow(slot_bytes));
+    NoteDeviceBytes(t);
+  }
+  float* slots = t->d_radiance_slots.get<float>();
+  for (uint32_t ra = 0; ra < r.ray_launches; ra++) {
+    for (uint32_t sb = 0; sb < r.launches; sb++) {
+      const RadianceLaunch l = RadianceLaunchAt(r, n, a.samples, ra, sb);
+      const uint32_t items = l.rays * l.k, wave_items = RadianceWaveItems(items, refill);
+      HIP_TRY(LaunchRadiance(p, r.q.variant, d_rays + (size_t)l.ray0 * kQueryRayFloats,
+                             d_streams ? d_streams + 2u * (size_t)l.ray0 : nullptr, index0 + l.ray0, l.rays, l.s0, l.k,
+                             MakeMagic(l.k), a, wave_items, RadianceGrid(items, wave_items, (uint32_t)block), slots,
+                             d_sum + 3u * (size_t)l.ray0, d_counts ? d_counts + l.ray0 : nullptr, t->stream));
+    }
+  }
+  return RT2_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void rt2_radiance_defaults(rt2_radiance_params* p) {
+  if (!p) return;
+  p->samples = 1;
+  p->max_depth = 0;
+  p->first_draw = 0;
+}
+
+int rt2_tracer_radiance(rt2_tracer* t, int64_t n, const float* rays, const uint32_t* streams,
+                        const rt2_radiance_params* params, uint64_t seed, float* out_sum, uint32_t* out_rays) {
+  const char* call = "radiance";
+  RadianceArgs a;
+  int rc = CheckRadiance(t, n, rays, streams, params, out_sum, call, &a);
+  if (rc != RT2_OK) return rc;
+  if (n == 0) return RT2_OK;
+  const int64_t chunk = std::min(QueryChunk(), (n + 63) / 64 * 64);
+  RenderParams p;
+  QueryPlan q;
+  if ((rc = QueryParams(t, seed, 1u, call, &p, &q)) != RT2_OK) return rc;
+  if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
+  HIP_TRY(hipSetDevice(t->device));
+  // rays and stream words in one buffer, sums and counts in the other
+  const size_t ray_bytes = (size_t)chunk * kQueryRayFloats * sizeof(float);
+  const size_t in_bytes = ray_bytes + (size_t)chunk * 2 * sizeof(uint32_t);
+  const size_t sum_bytes = (size_t)chunk * 3 * sizeof(float);
+  const size_t out_bytes = sum_bytes + (size_t)chunk * sizeof(uint32_t);
+  if (in_bytes > t->d_query_rays.bytes() || out_bytes > t->d_query_hits.bytes()) {
+    HIP_TRY(t->d_query_rays.Grow(in_bytes));
+    HIP_TRY(t->d_query_hits.Grow(out_bytes));
+    NoteDeviceBytes(t);
+  }
+  float* d_rays = t->d_query_rays.get<float>();
+  uint32_t* d_streams = reinterpret_cast<uint32_t*>(t->d_query_rays.get<char>() + ray_bytes);
+  float* d_sum = t->d_query_hits.get<float>();
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(t->d_query_hits.get<char>() + sum_bytes);
+  std::vector<hipEvent_t> ev;  // one pair per chunk, back to the tracer's pool on every way out
+  struct Return {
+    rt2_tracer* t;
+    std::vector<hipEvent_t>& ev;
+    ~Return() {
+      for (hipEvent_t e : ev) t->event_pool.push_back(e);
+    }
+  } give_back{t, ev};
+  hipError_t e = hipSuccess;
+  for (int64_t at = 0; at < n && e == hipSuccess; at += chunk) {
+    const uint32_t m = (uint32_t)std::min(chunk, n - at);
+    hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
+    if (e0) ev.push_back(e0);
+    if (e1) ev.push_back(e1);
+    if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
+    e = hipMemcpyAsync(d_rays, rays + (size_t)at * kQueryRayFloats, (size_t)m * kQueryRayFloats * sizeof(float),
+                       hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess && streams)
+      e = hipMemcpyAsync(d_streams, streams + 2 * (size_t)at, (size_t)m * 2 * sizeof(uint32_t), hipMemcpyHostToDevice,
+                         t->stream);
+    if (e == hipSuccess) e = hipEventRecord(e0, t->stream);
+    if (e == hipSuccess) {
+      rc = EnqueueRadiance(t, p, d_rays, streams ? d_streams : nullptr, (uint32_t)at, m, a, d_sum,
+                           out_rays ? d_counts : nullptr);
+      if (rc != RT2_OK) {
+        (void)hipStreamSynchronize(t->stream);
+        return rc;
+      }
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(out_sum + 3 * (size_t)at, d_sum, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+    if (e == hipSuccess && out_rays)
+      e = hipMemcpyAsync(out_rays + at, d_counts, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  t->host_waits++;
+  if (e != hipSuccess) return HipFail(e, call);
+  double ms = 0.0;
+  for (size_t k = 0; k + 1 < ev.size(); k += 2) {
+    float f = 0.0f;
+    if (hipEventElapsedTime(&f, ev[k], ev[k + 1]) != hipSuccess) {
+      ms = -1.0;
+      break;
+    }
+    ms += (double)f;
+  }
+  t->radiance_pending = false;
+  t->radiance_ms = ms;
+  return RT2_OK;
+}
+
+int rt2_tracer_radiance_device(rt2_tracer* t, int64_t n, const float* d_rays, const uint32_t* d_streams,
+                               const rt2_radiance_params* params, uint64_t seed, float* d_out_sum,
+                               uint32_t* d_out_rays) {
+  const char* call = "radiance_device";
+  RadianceArgs a;
+  int rc = CheckRadiance(t, n, d_rays, nullptr, params, d_out_sum, call, &a);
+  if (rc != RT2_OK) return rc;
+  if (n == 0) return RT2_OK;
+  RenderParams p;
+  QueryPlan q;
+  if ((rc = QueryParams(t, seed, 1u, call, &p, &q)) != RT2_OK) return rc;
+  HIP_TRY(hipSetDevice(t->device));
+  if (!t->radiance_e0 && hipEventCreate(&t->radiance_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  if (!t->radiance_e1 && hipEventCreate(&t->radiance_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+  t->radiance_pending = false;
+  t->radiance_ms = -1.0;
+  HIP_TRY(hipEventRecord(t->radiance_e0, t->stream));
+  if ((rc = EnqueueRadiance(t, p, d_rays, d_streams, 0u, (uint32_t)n, a, d_out_sum, d_out_rays)) != RT2_OK) return rc;
+  HIP_TRY(hipEventRecord(t->radiance_e1, t->stream));
+  t->radiance_pending = true;
+  return RT2_OK;
+}
+
+int rt2_tracer_radiance_time(rt2_tracer* t, double* ms) {
+  if (!t || !ms) return Fail(RT2_ERR_INVALID, "radiance_time: null argument");
+  if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "radiance_time: not on a create_multi tracer");
+  if (t->radiance_pending) {
+    HIP_TRY(hipSetDevice(t->device));
+    const hipError_t q = hipEventQuery(t->radiance_e1);
+    if (q == hipSuccess) {
+      float f = -1.0f;
+      if (hipEventElapsedTime(&f, t->radiance_e0, t->radiance_e1) != hipSuccess) f = -1.0f;
+      t->radiance_ms = (double)f;
+      t->radiance_pending = false;
+    } else if (q != hipErrorNotReady) {
+      return HipFail(q, "radiance_time");
+    }
+  }
+  *ms = t->radiance_pending ? -1.0 : t->radiance_ms;
+  return RT2_OK;
+}
 
 int rt2_ambient_direction(const float* n3, const float* u3, float* d3) {
   if (!n3 || !u3 || !d3) return Fail(RT2_ERR_INVALID, "ambient_direction: null pointer");

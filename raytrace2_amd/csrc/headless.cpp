@@ -12,6 +12,12 @@
 // feature record's layout) of the ray through the centre of pixel (X, Y) of a W x H image (default: the
 // scene's dims, else 1600x900) as one JSON line: the record RayTracer::Features holds for that pixel.
 //
+//   rt2_headless <scene.json> --radiance OX OY OZ DX DY DZ [--samples K]
+// --radiance renders nothing and writes no image: it path-traces K samples (default 1) along the ray from (OX, OY,
+// OZ) in the direction (DX, DY, DZ), taken as given, unbounded, at time 0 (rt2.h "Radiance queries": the default
+// stream words and the tracer's depth) and prints the mean radiance, sum / K in float, and the rays cast as one JSON
+// line.
+//
 //   rt2_headless <scene.json> <out.png> --ao SAMPLES [--ao-radius R] [--size WxH]
 // --ao SAMPLES renders nothing: it writes the ambient-occlusion visibility of the image's first hits (rt2.h "Ambient
 // occlusion": RayTracer::Ambient with SAMPLES samples within R, default unbounded) as a grey image, 1 - count /
@@ -49,8 +55,9 @@ int main(int argc, char** argv) {
                          "[--noise-target X [--max-samples N]] [--adaptive THRESHOLD [--window N] [--max-samples N]] "
                          "[--denoise [--denoise-iterations N]] (--denoise with --gpus N filters the gathered image)\n"
                          "       %s <scene.json> <out.png> --ao SAMPLES [--ao-radius R] [--size WxH]\n"
-                         "       %s <scene.json> --pick X Y [--size W H]\n",
-                 argv[0], argv[0], argv[0]);
+                         "       %s <scene.json> --pick X Y [--size W H]\n"
+                         "       %s <scene.json> --radiance OX OY OZ DX DY DZ [--samples K]\n",
+                 argv[0], argv[0], argv[0], argv[0]);
     return 2;
   }
   // (--pick: no output image, the options start right after the scene)
@@ -68,6 +75,8 @@ int main(int argc, char** argv) {
   int denoise_iterations = 0;  // 0: the default
   bool pick = false;
   rt2::ivec2 pick_at{0, 0};
+  bool radiance = false;
+  float radiance_ray[8] = {0.0f, 0.0f, 0.0f, FLT_MAX, 0.0f, 0.0f, 0.0f, 0.0f};
   int ao_samples = 0;  // > 0: write the ambient-occlusion visibility instead of a render
   float ao_radius = FLT_MAX;
   try {
@@ -123,6 +132,19 @@ int main(int argc, char** argv) {
           return 2;
         pick = true;
         i += 1;
+      } else if (!std::strcmp(argv[i], "--radiance")) {  // six values follow
+        bool six = i + 6 < argc;
+        for (int k = 0; six && k < 6; k++) {
+          char* end = nullptr;
+          radiance_ray[k < 3 ? k : k + 1] = std::strtof(argv[i + 1 + k], &end);
+          six = end != argv[i + 1 + k] && *end == '\0';
+        }
+        if (!six) {
+          std::fprintf(stderr, "--radiance needs six numbers: OX OY OZ DX DY DZ\n");
+          return 2;
+        }
+        radiance = true;
+        i += 5;
       } else if (!std::strcmp(argv[i], "--size")) {
         if (std::sscanf(argv[i + 1], "%dx%d", &size.x, &size.y) != 2) {  // WxH, or W H
           if (i + 2 >= argc || std::sscanf(argv[i + 1], "%d", &size.x) != 1 || std::sscanf(argv[i + 2], "%d", &size.y) != 1)
@@ -134,7 +156,7 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
-    if (no_image && !pick) {
+    if (no_image && !pick && !radiance) {
       std::fprintf(stderr, "no output image given\n");
       return 2;
     }
@@ -180,6 +202,26 @@ int main(int argc, char** argv) {
         std::snprintf(num, sizeof num, "%.9g", (double)rec[k]);
         const bool integral = !std::strpbrk(num, ".e");
         std::printf("%s%s%s", k ? ", " : "", num, integral ? ".0" : "");
+      }
+      std::printf("]}\n");
+      return 0;
+    }
+
+    if (radiance) {
+      rt2_radiance_params prm = rt2::RayTracer::RadianceDefaults();
+      prm.samples = samples > 0 ? (int)samples : 1;
+      if (samples > 65535 || !rt2::RayTracer::RayValid(radiance_ray)) {
+        std::fprintf(stderr, "--radiance needs a ray inside the query domain and --samples in [1, 65535]\n");
+        return 2;
+      }
+      rt2::RayTracer probe(scene, 0);
+      float sum[3];
+      uint32_t cast = 0;
+      probe.Radiance(radiance_ray, 1, sum, &cast, prm);
+      std::printf("{\"samples\": %d, \"rays\": %u, \"radiance\": [", prm.samples, cast);
+      for (int k = 0; k < 3; k++) {  // nine digits round-trip a float
+        const float mean = sum[k] / (float)prm.samples;
+        std::printf("%s%.9g", k ? ", " : "", (double)mean);
       }
       std::printf("]}\n");
       return 0;

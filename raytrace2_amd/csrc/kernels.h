@@ -12,6 +12,7 @@
 #include "ambient.h"
 #include "denoise.h"
 #include "noise.h"
+#include "radiance.h"
 #include "rt2_layout.h"
 #include "temporal.h"
 
@@ -30,6 +31,9 @@ hipError_t LaunchOcclusion(const RenderParams& p, int variant, const float* rays
                            hipStream_t stream);
 hipError_t LaunchAmbient(const RenderParams& p, int variant, const AmbientSource& src, uint32_t n_points, uint32_t s0,
                          uint32_t k, Magic k_div, uint32_t* counts, hipStream_t stream);
+hipError_t LaunchRadiance(const RenderParams& p, int variant, const float* rays, const uint32_t* streams, uint32_t index0,
+                          uint32_t n, uint32_t s0, uint32_t k, Magic k_div, const RadianceArgs& a, uint32_t wave_items,
+                          uint32_t grid, float* slots, float* out_sum, uint32_t* out_rays, hipStream_t stream);
 size_t QueryLdsBytes(const RenderParams& p);
 int RenderMode(const RenderParams& p);
 int RenderBlockSize();

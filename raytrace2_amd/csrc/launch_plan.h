@@ -178,4 +178,55 @@ inline AmbientPlan PlanAmbient(uint32_t lin_len, int variant, uint32_t variant_f
   return a;
 }
 
+// A radiance call (rt2.h "Radiance queries"; render.hip radiance_kernel) over `rays` rays, 0 < rays < 2^31, of
+// `samples` samples each, 1 <= samples <= 65535. Work items are (ray, sample), one result slot each. A launch
+// holds at most min(items_max, 2^31 - 1) items (items_max >= 1: RT2_RADIANCE_ITEMS, the slot buffer's bound): the
+// call is split by sample ranges first (per_launch consecutive samples of every ray), and where one sample of
+// every ray is still too many, by ray ranges (rays_per_launch consecutive rays). Launch (a, b), a over the ray
+// ranges and b over the sample ranges, b fastest: each ray's sample ranges run in increasing order, which the
+// ordered sum needs. Every wave owns wave_items consecutive items of its launch (a multiple of 64; 64 without
+// refill: one item per lane); with refill the blocks grow with the launch so that about kRadianceWaves waves
+// share it, up to 64 items per lane.
+// (2^24 items are 256 MiB of 16-byte slots, float3 plus the ray count; 192 MiB would be 12-byte slots without it)
+constexpr uint32_t kRadianceItemsDefault = 1u << 24;
+// The most RT2_RADIANCE_ITEMS is taken for: 2^28 items, a slot buffer of 4 GiB; a larger value is read as this one.
+constexpr uint32_t kRadianceItemsEnvMax = 1u << 28;
+constexpr uint32_t kRadianceWaves = 8192;
+struct RadiancePlan {
+  QueryPlan q;  // of the first launch (the largest)
+  uint32_t rays_per_launch, ray_launches, per_launch, launches;
+};
+struct RadianceLaunch {
+  uint32_t ray0, rays, s0, k;
+};
+inline RadiancePlan PlanRadiance(uint32_t lin_len, int variant, uint32_t variant_features, int stack_depth,
+                                 uint32_t rays, uint32_t samples, uint32_t items_max, int block) {
+  RadiancePlan r;
+  const uint32_t bound = std::min<uint32_t>(std::max<uint32_t>(items_max, 1u), 0x7FFFFFFFu);
+  r.rays_per_launch = std::min(rays, bound);
+  r.ray_launches = (rays + r.rays_per_launch - 1u) / r.rays_per_launch;
+  r.per_launch = std::min<uint32_t>(samples, std::max<uint32_t>(1u, bound / r.rays_per_launch));
+  r.launches = (samples + r.per_launch - 1u) / r.per_launch;
+  r.q = PlanQuery(lin_len, variant, variant_features, stack_depth, r.rays_per_launch * r.per_launch, block);
+  return r;
+}
+inline RadianceLaunch RadianceLaunchAt(const RadiancePlan& r, uint32_t rays, uint32_t samples, uint32_t a, uint32_t b) {
+  RadianceLaunch l;
+  l.ray0 = a * r.rays_per_launch;
+  l.rays = std::min(r.rays_per_launch, rays - l.ray0);
+  l.s0 = b * r.per_launch;
+  l.k = std::min(r.per_launch, samples - l.s0);
+  return l;
+}
+inline uint32_t RadianceWaveItems(uint32_t items, bool refill) {
+  if (!refill) return 64u;
+  const uint32_t per_lane = (items + 64u * kRadianceWaves - 1u) / (64u * kRadianceWaves);
+  return 64u * std::min<uint32_t>(std::max<uint32_t>(per_lane, 1u), 64u);
+}
+// The launch's workgroups of `block` lanes: one wave per block of wave_items items.
+inline uint32_t RadianceGrid(uint32_t items, uint32_t wave_items, uint32_t block) {
+  const uint32_t waves = (items + wave_items - 1u) / wave_items;
+  return (waves * 64u + block - 1u) / block;
+}
+
 }  // namespace rt2

@@ -3474,6 +3474,206 @@ AmbientFn AmbientKernel(int v, bool threaded) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Radiance queries (rt2.h "Radiance queries", radiance.h): RayColorForward along rays of the
+// caller. A work item is (ray, sample) of the launch's samples [s0, s0 + k) of n rays, the sample fastest
+// (radiance.h RadianceItem); its result, r g b and the rays it cast, goes to slot `item` of the launch, so which
+// lane computed it cannot show. Each wave owns the wave_items consecutive items from wave * wave_items and its
+// lanes take them as their paths end: the lanes without a path are balloted, lane j of them takes the j-th
+// unclaimed item (v_mbcnt prefix) and the wave-uniform counter moves on by the items taken; no atomics. With
+// wave_items == 64 every lane takes exactly one item. The wave leaves when no lane holds a path and its block is
+// used up. A lane holds a PathT<false> on the sample's own stream (seed, pixel word, frame word + s) with the
+// first first_draw uniforms passed over, thr, the ray and the depth left; a ConstantMedium draws from that
+// stream, as in the render. A bounce is the render kernel's (`// ---- one bounce` above, its shade lambda
+// restated operation for operation: factored out, render_kernel's code would have to stay what it is), over
+// trace_linear / trace_stack with kTmax: the ray's tmax on the first segment, FLT_MAX afterwards. No hit table,
+// no kept model-space ray, no flat walk, as query_kernel. An invalid ray's items store nothing: the sum kernel
+// answers for it. Two template parameters and no bool, as query_kernel.
+template <uint32_t F, int kMode>
+__global__ __launch_bounds__(kBlock) void radiance_kernel(const RenderParams P, const float4* __restrict__ rays,
+                                                          const uint32_t* __restrict__ streams, uint32_t index0,
+                                                          uint32_t n_items, uint32_t s0, uint32_t k_launch, Magic k_div,
+                                                          uint32_t max_depth, uint32_t first_draw, uint32_t wave_items,
+                                                          float4* __restrict__ slots) {
+  static_assert(kMode == kModeLinear || kMode == kModeStackGlobal, "threaded program or global-memory stack walk");
+  lds_u32* cand = nullptr;  // the wave's box-boundary candidate planes, as the query kernel's
+  if constexpr (BoxPair<F, kMode>()) {
+    __shared__ uint32_t s_cand[(kBlock / 64) * kBoundaryAAMax * 64];
+    cand = wave_planes((lds_u32*)(s_cand), kBoundaryAAMax);
+  }
+  // the wave's block of items [wnext, wend), wave-uniform (n_items < 2^31 and wave_items <= 4096: no overflow)
+  const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * (uint32_t)kBlock + threadIdx.x) >> 6);
+  uint32_t wnext = min(wave * wave_items, n_items);
+  const uint32_t wend = min(wnext + wave_items, n_items);
+  const f3 bg = mk(P.background[0], P.background[1], P.background[2]);
+  bool active = false;  // the lane holds a path
+  uint32_t item = 0, dl = 0, nrays = 0;
+  PathT<false> path;
+  path.rb = nullptr;
+  path.pix = 0;
+  path.sij = 0;
+  path.r0 = path.r1 = path.r2 = path.r3 = 0;
+  path.start(0);
+  f3 ro = mk(0, 0, 0), rd = mk(0, 0, 1), thr = mk(1, 1, 1);
+  float rtime = 0.0f, seg_tmax = FLT_MAX;
+  while (true) {
+    // ---- refill: the lanes without a path take the block's next items in lane order
+    const unsigned long long mask = __ballot(!active);
+    const uint32_t avail = wend - wnext;
+    if (mask != 0ull && avail != 0u) {  // wave-uniform
+      if (!active) {
+        const uint32_t j = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (j < avail) {
+          item = wnext + j;
+          const uint32_t ray = udiv(item, k_div);
+          const uint32_t s = s0 + (item - ray * k_launch);
+          float r[kQueryRayFloats];
+          load_query_ray(rays, ray, r);
+          if (QueryRayValid(r)) {
+            uint32_t pw, fw;
+            RadianceStream(streams, index0, ray, &pw, &fw);
+            path.pix = pw;
+            path.start(fw + s);
+            // pass over first_draw uniforms: the buffer holds the block of the last one (PathT::take)
+            path.n = first_draw;
+            if ((first_draw & 3u) != 0u) path.block(first_draw >> 2, path.r0, path.r1, path.r2, path.r3);
+            ro = mk(r[kQrOx], r[kQrOy], r[kQrOz]);
+            rd = mk(r[kQrDx], r[kQrDy], r[kQrDz]);
+            rtime = r[kQrTime];
+            seg_tmax = r[kQrTmax];
+            thr = mk(1, 1, 1);
+            dl = max_depth;
+            nrays = 0;
+            active = true;
+          }
+        }
+      }
+      const uint32_t count = (uint32_t)__popcll(mask);
+      wnext += count < avail ? count : avail;
+    }
+    if (__ballot(active) == 0ull) {
+      if (wnext == wend) break;  // the wave is done (uniform exit)
+      continue;                  // (a claim of invalid rays only: claim again)
+    }
+    if (active) {
+      // ---- one bounce (RayColor, RayTracer.cpp:20-45), as render_kernel's
+      bool done = false;
+      f3 color = mk(0, 0, 0);
+      if (dl == 0u) {
+        done = true;  // RayColor(depth <= 0) returns 0 without casting a ray
+      } else {
+        nrays++;
+        HitRef h{0.0f, kRefNone, kRefNone};
+        Counters cnt = {};
+        bool hit;
+        f3 hp, hn;
+        bool front;
+        uint32_t mat;
+        if constexpr (kMode == kModeLinear) {
+          hit = trace_linear<F, false, false, true>(P, RegRay{ro, rd}, rtime, path, h, cand, nullptr, cnt, false, nullptr,
+                                                    seg_tmax);
+          if (hit)
+            resolve_hit<F>(Nodes<kModeLinear>{reinterpret_cast<const float4*>(P.lind)}, h, ro, rd, rtime, hp, hn, front,
+                           mat);
+        } else {
+          uint32_t* stk = reinterpret_cast<uint32_t*>(s_dyn) + threadIdx.x;
+          const Nodes<kModeStackGlobal> N{reinterpret_cast<const float4*>(P.nodes), 0u};
+          bool overflow = false;  // (the launcher refuses a scene whose stack is deeper than the kernel's)
+          hit = trace_stack<F, kModeStackGlobal, false, true>(P, N, ro, rd, rtime, path, h, stk, cnt, overflow, seg_tmax);
+          if (hit) resolve_hit<F>(N, h, ro, rd, rtime, hp, hn, front, mat);
+        }
+        seg_tmax = FLT_MAX;
+        if (!hit) {
+          color = thr * bg;
+          done = true;
+        } else {
+          const ShadeArgs S = shade_args();
+          const float4 m0 = S.materials[2 * mat], m1 = S.materials[2 * mat + 1];
+          const uint32_t type = bits(m0.x);
+          if (type == kMatDiffuseLight) {
+            color = thr * tex_value<F>(S, bits(m1.z), hp);
+            done = true;
+          } else {
+            f3 att, dir;
+            bool dielectric = Has<F, kFeatSpecular>() && type == kMatDielectric;
+            f3 ru = mk(0.0f, 0.0f, 0.0f);
+            if (!dielectric) ru = rand_unit_vec3(path);  // one sampling site for every other material
+            if (Has<F, kFeatSpecular>() && type == kMatMetal) {
+              dir = normalize(reflect(rd, hn)) + (m1.x * ru);
+              att = mk(m0.y, m0.z, m0.w);
+            } else if (dielectric) {
+              att = mk(1.0f, 1.0f, 1.0f);
+              float ri = front ? m1.w : m1.y;
+              f3 ud = normalize(rd);
+              float cos_t = gmin(dot(-ud, hn), 1.0f);
+              float sin_t = sqrtf(1.0f - cos_t * cos_t);
+              bool refl = ri * sin_t > 1.0f;
+              if (!refl) {
+                float r0 = (1.0f - ri) / (1.0f + ri);
+                r0 = r0 * r0;
+                double xx = (double)(1.0f - cos_t);
+                double x2 = xx * xx;
+                double x5 = (x2 * x2) * xx;
+                double schlick = (double)r0 + (double)(1.0f - r0) * x5;
+                refl = schlick > (double)path.uniform();
+              }
+              dir = refl ? reflect(ud, hn) : refract(ud, hn, ri);
+            } else if (Has<F, kFeatMedium>() && type == kMatIsotropic) {
+              dir = ru;
+              att = tex_value<F>(S, bits(m1.z), hp);
+            } else {  // Lambertian / Texture
+              dir = hn + ru;
+              if (near_zero(dir)) dir = hn;
+              att = type == kMatLambertian ? mk(m0.y, m0.z, m0.w) : tex_value<F>(S, bits(m1.z), hp);
+            }
+            thr = thr * att;
+            ro = hp;
+            rd = dir;
+            dl--;
+          }
+        }
+      }
+      if (done) {
+        slots[item] = make_float4(color.x, color.y, color.z, uf(nrays));
+        active = false;
+      }
+    }
+  }
+}
+
+// A ray's answer from its slots of one launch (radiance.h RadianceSum): ray i's k slots added in sample order onto
+// out_sum[i] / out_rays[i], which start at 0 where first (the call's first sample range). An invalid ray answers
+// (0, 0, 0) and kRadianceInvalid. out_rays may be null.
+__global__ __launch_bounds__(256) void radiance_sum_kernel(const float4* __restrict__ rays, const float* __restrict__ slots,
+                                                           uint32_t n, uint32_t k, uint32_t first, float* out_sum,
+                                                           uint32_t* out_rays) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  float r[kQueryRayFloats];
+  load_query_ray(rays, i, r);
+  float sum3[3] = {0.0f, 0.0f, 0.0f};
+  uint32_t c = 0;
+  if (!RadianceRayValid(r)) {
+    c = kRadianceInvalid;
+  } else {
+    if (first == 0u) {
+      sum3[0] = out_sum[3ull * i], sum3[1] = out_sum[3ull * i + 1ull], sum3[2] = out_sum[3ull * i + 2ull];
+      if (out_rays) c = out_rays[i];
+    }
+    RadianceSum(slots + (size_t)kRadianceSlotWords * k * i, k, sum3, &c);
+  }
+  out_sum[3ull * i] = sum3[0], out_sum[3ull * i + 1ull] = sum3[1], out_sum[3ull * i + 2ull] = sum3[2];
+  if (out_rays) out_rays[i] = c;
+}
+
+using RadianceFn = void (*)(RenderParams, const float4*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, Magic,
+                            uint32_t, uint32_t, uint32_t, float4*);
+// chosen as QueryKernel chooses
+RadianceFn RadianceKernel(int v, bool threaded) {
+  if (!threaded) return &radiance_kernel<kFeatAll, kModeStackGlobal>;
+  return WithVariant(v, [](auto V) -> RadianceFn { return &radiance_kernel<kVariants[V], kModeLinear>; });
+}
+
+// ------------------------------------------------------------------------------------------
 // Self-tests of the kernel's exact shortcuts on random inputs (rt2_selftest):
 //   which 0: div_by_inv(a, b, fl(1/b)) == a / b for |b| > 1e-8, |a / b| >= 1e-3 (accepted quad t)
 //   which 3: the same for any quotient with 2^-100 <= |a| < 2^21 (medium box boundaries, any t)
@@ -3790,6 +3990,29 @@ hipError_t LaunchAmbient(const RenderParams& p, int variant, const AmbientSource
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3(QueryGrid(n_points * k, (uint32_t)dev::kBlock)), dim3(dev::kBlock), QueryLdsBytes(p), stream,
                      p, src.recs, src.stride, src.off_p, src.off_n, src.radius, src.width, src.index0, n_points, s0, k, k_div, counts);
+  return hipGetLastError();
+}
+
+// The radiance kernel over the samples [s0, s0 + k) of n rays into `slots` (n * k slots of 16 bytes), then the sum
+// kernel over them onto out_sum / out_rays (may be null), which start at 0 where s0 == 0. n * k < 2^31
+// (launch_plan.h PlanRadiance); k_div: MakeMagic(k); wave_items, grid: RadianceWaveItems, RadianceGrid; streams may be null (index0: the stream index of
+// ray 0). p (its seed is the call's) and the choice of walk: as LaunchQuery.
+hipError_t LaunchRadiance(const RenderParams& p, int variant, const float* rays, const uint32_t* streams, uint32_t index0,
+                          uint32_t n, uint32_t s0, uint32_t k, Magic k_div, const RadianceArgs& a, uint32_t wave_items,
+                          uint32_t grid, float* slots, float* out_sum, uint32_t* out_rays, hipStream_t stream) {
+  if (n == 0 || k == 0) return hipSuccess;
+  const dev::RadianceFn fn = dev::RadianceKernel(variant, p.lin_len != 0);
+  if (!fn || (uint64_t)n * k > 0x7FFFFFFFull || (!p.lin_len && p.stack_depth > kTraversalStack) || wave_items == 0u ||
+      wave_items % 64u != 0u || wave_items > 4096u)
+    return hipErrorInvalidValue;
+  const uint32_t items = n * k;
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(dev::kBlock), QueryLdsBytes(p),
+                     stream, p, reinterpret_cast<const float4*>(rays), streams, index0, items, s0, k, k_div,
+                     a.max_depth, a.first_draw, wave_items, reinterpret_cast<float4*>(slots));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dev::radiance_sum_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream,
+                     reinterpret_cast<const float4*>(rays), slots, n, k, s0 == 0u ? 1u : 0u, out_sum, out_rays);
   return hipGetLastError();
 }
 

@@ -262,6 +262,13 @@ struct rt2_tracer {
   hipEvent_t ambient_e0 = nullptr, ambient_e1 = nullptr;
   bool ambient_pending = false;
   double ambient_ms = -1.0;
+  // radiance queries (rt2.h "Radiance queries"): the same for its calls (rt2_tracer_radiance_time), and the result
+  // slots of a launch's (ray, sample) items, grown on demand and kept; the host entry's rays, stream words and
+  // answers go through the two query buffers above
+  hipEvent_t radiance_e0 = nullptr, radiance_e1 = nullptr;
+  bool radiance_pending = false;
+  double radiance_ms = -1.0;
+  rt2::DeviceBuffer d_radiance_slots;
   rt2::DeviceBuffer d_work;  // one work counter per launch slot (words 0 and 16)
   rt2::DeviceBuffer d_stats;
   bool stats_on = false;

@@ -17,12 +17,14 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._native import AppSettings as _AppSettings
-from ._native import (UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Noise, PresentParams, SceneInfo, Stats,
-                      TemporalParams, check, lib)
+from ._native import (UNIQUE_ID_BYTES, Adaptive, CameraDesc, DenoiseParams, Noise, PresentParams, RadianceParams, SceneInfo,
+                      Stats, TemporalParams, check, lib)
 
 DEFAULT_SEED = 0x5EED2024
 FLT_MAX = float(np.finfo(np.float32).max)
 AMBIENT_INVALID = np.uint32(0xFFFFFFFF)  # ambient_counts / ambient_points: a miss pixel, an invalid point
+RADIANCE_INVALID = np.uint32(0xFFFFFFFF)  # radiance(counts=True): the ray count of an invalid ray
+RADIANCE_FRAME0 = 0x40000000  # radiance(streams=None): every ray's frame word (its pixel word is its row)
 
 
 def _fp(a: np.ndarray):
@@ -772,6 +774,69 @@ class RayTracer:
         """GPU ms of the last ambient call's kernels (-1: not finished yet, or none). Never waits."""
         ms = ctypes.c_double(-1.0)
         check(lib.rt2_tracer_ambient_time(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    # -- radiance queries (rt2.h "Radiance queries") -----------------------------------------------
+    def radiance(self, rays, samples: int = 1, streams=None, max_depth: Optional[int] = None, first_draw: int = 0,
+                 seed: Optional[int] = None, counts: bool = False):
+        """The radiance RayColor returns along rays of the caller, summed over `samples` paths per ray: rays (n, 8)
+        float32 as intersect's -> (n, 3) float32 sums in sample order (divide by samples for the mean); with counts
+        also (n,) uint32, the rays cast (0xFFFFFFFF and a zero sum for a ray outside ray_valid's domain). streams:
+        (n, 2) uint32 (pixel word, frame word) per ray, default (row, 0x40000000); sample s draws from the path stream
+        (seed, pixel word, frame word + s) after its first first_draw uniforms. max_depth: default the tracer's.
+        With a camera's own ray, (y * W + x, f) and first_draw 3 (5 with defocus) the answer is that pixel's sample
+        of frame f in a render, bit for bit. A numpy array goes through the host entry and numpy comes back; a CUDA
+        torch tensor on the tracer's device (streams then a CUDA int32 tensor of the uint32 words, or None) goes
+        through the device entry into new tensors (counts: int32 holding the uint32 words), complete on return."""
+        seed = self._seed if seed is None else int(seed)
+        prm = RadianceParams(int(samples), 0 if max_depth is None else int(max_depth), int(first_draw))
+        if max_depth is not None and int(max_depth) < 1:
+            raise ValueError("radiance: need max_depth >= 1 (None: the tracer's)")
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+            import torch
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise ValueError(f"radiance: need a tensor on cuda:{self.device}")
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("radiance: need rays (n, 8) float32")
+            rays = rays.contiguous()
+            n = rays.shape[0]
+            if streams is not None:
+                if (not hasattr(streams, "is_cuda") or not streams.is_cuda or streams.device != rays.device or
+                        streams.dtype != torch.int32 or tuple(streams.shape) != (n, 2)):
+                    raise ValueError("radiance: need streams (n, 2) int32 on the rays' device")
+                streams = streams.contiguous()
+            out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+            cnt = torch.empty((n,), dtype=torch.int32, device=rays.device) if counts else None
+            if n:
+                torch.cuda.current_stream(rays.device).synchronize()  # the rays are written; `out` is allocated
+                check(lib.rt2_tracer_radiance_device(
+                    self._h, n, ctypes.c_void_p(rays.data_ptr()),
+                    ctypes.c_void_p(streams.data_ptr()) if streams is not None else None, ctypes.byref(prm), seed,
+                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(cnt.data_ptr()) if counts else None))
+                self.synchronize()
+            return (out, cnt) if counts else out
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("radiance: need rays (n, 8) float32")
+        n = rays.shape[0]
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        sp = None
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.uint32)
+            if streams.shape != (n, 2):
+                raise ValueError("radiance: need streams (n, 2) uint32")
+            sp = streams.ctypes.data_as(u32p)
+        out = np.zeros((n, 3), np.float32)
+        cnt = np.zeros((n,), np.uint32)
+        if n:
+            check(lib.rt2_tracer_radiance(self._h, n, _fp(rays), sp, ctypes.byref(prm), seed, _fp(out),
+                                          cnt.ctypes.data_as(u32p) if counts else None))
+        return (out, cnt) if counts else out
+
+    def radiance_time(self) -> float:
+        """GPU ms of the last radiance call's kernels (-1: not finished yet, or none). Never waits."""
+        ms = ctypes.c_double(-1.0)
+        check(lib.rt2_tracer_radiance_time(self._h, ctypes.byref(ms)))
         return ms.value
 
     # -- temporal reuse (rt2.h "Temporal reuse") ------------------------------------------------
