@@ -534,14 +534,8 @@ rt2_tracer::~rt2_tracer() {
   }
   if (stream) (void)hipStreamSynchronize(stream);
   for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
-  recon.DestroyEvents();
-  image_recon.DestroyEvents();
-  if (query_e0) (void)hipEventDestroy(query_e0);
-  if (query_e1) (void)hipEventDestroy(query_e1);
-  if (ambient_e0) (void)hipEventDestroy(ambient_e0);
-  if (ambient_e1) (void)hipEventDestroy(ambient_e1);
-  if (radiance_e0) (void)hipEventDestroy(radiance_e0);
-  if (radiance_e1) (void)hipEventDestroy(radiance_e1);
+  for (KernelTimer* k : {&recon.present_timer, &image_recon.present_timer, &query_timer, &ambient_timer, &radiance_timer})
+    k->Release();
   d_clock.reset();
   if (h_clock) (void)hipHostFree(h_clock);
   if (h_check) (void)hipHostFree(h_check);

@@ -84,7 +84,7 @@ static double EventMs(const EventPair& ev) {
 // the estimate comes from.
 struct Chain {
   rt2_tracer* t;  // device, stream, material table, event pool
-  Recon& recon;   // features (current), scratch, history, present events
+  Recon& recon;   // features (current), scratch, history, present timer
   int width, rows;
   int64_t frames;
   // the estimate: the sums (LaunchDenoiseInputs divides and takes the variance; counts: adaptive sampling's, or
@@ -365,11 +365,7 @@ static int EnqueuePresent(const Chain& c, const PresentStages& st, uint8_t* out_
   // the filter's first plane, which is free again once the filter's last kernel (unpack) has run
   const size_t need = st.denoise ? DenoiseScratchBytes(n) : n * 5 * sizeof(float);
   if ((rc = EnsureScratch(c, need)) != RT2_OK) return rc;
-  if (!r.present_e0 && hipEventCreate(&r.present_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  if (!r.present_e1 && hipEventCreate(&r.present_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  r.present_pending = false;
-  r.present_ms = -1.0;
-  HIP_TRY(hipEventRecord(r.present_e0, t->stream));
+  if ((rc = r.present_timer.Begin(t->stream)) != RT2_OK) return rc;
   if (st.temporal) {
     if ((rc = EnqueueBlend(c, st.tk, need, false, nullptr)) != RT2_OK) return rc;
   } else {
@@ -379,28 +375,8 @@ static int EnqueuePresent(const Chain& c, const PresentStages& st, uint8_t* out_
   uint8_t* d_rgba = reinterpret_cast<uint8_t*>(d_color + 4 * n);
   if (st.denoise) HIP_TRY(LaunchDenoise(d_color, c.features(), c.width, c.rows, st.dk, DenoiseLds(), t->stream));
   HIP_TRY(LaunchPresent(d_color, d_rgba, (uint32_t)n, t->stream));
-  HIP_TRY(hipEventRecord(r.present_e1, t->stream));
-  r.present_pending = true;
+  if ((rc = r.present_timer.End(t->stream)) != RT2_OK) return rc;
   HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, n * 4, hipMemcpyDeviceToHost, t->stream));
-  return RT2_OK;
-}
-
-// rt2_tracer_present_time over the chain's events: polls, never waits.
-static int PresentTime(const Chain& c, double* ms) {
-  Recon& r = c.recon;
-  if (r.present_pending) {
-    HIP_TRY(hipSetDevice(c.t->device));
-    const hipError_t q = hipEventQuery(r.present_e1);
-    if (q == hipSuccess) {
-      float f = -1.0f;
-      if (hipEventElapsedTime(&f, r.present_e0, r.present_e1) != hipSuccess) f = -1.0f;
-      r.present_ms = (double)f;
-      r.present_pending = false;
-    } else if (q != hipErrorNotReady) {
-      return HipFail(q, "present_time");
-    }
-  }
-  if (ms) *ms = r.present_pending ? -1.0 : r.present_ms;
   return RT2_OK;
 }
 
@@ -657,7 +633,7 @@ int rt2_tracer_move_camera(rt2_tracer* t, const rt2_camera_desc* cam, const rt2_
 int rt2_tracer_present_time(rt2_tracer* t, double* ms) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
   if (!OneGpu(t)) return OneGpuRefusal("present");
-  return PresentTime(LocalChain(t), ms);
+  return t->recon.present_timer.Poll(t->device, "present_time", ms);  // polls, never waits
 }
 
 int rt2_present_buffers(int device, int width, int height, const float* color, uint8_t* out_rgba) {
@@ -776,6 +752,6 @@ int rt2_tracer_image_present_time(rt2_tracer* t, double* ms) {
   if (!t) return Fail(RT2_ERR_INVALID, "null tracer");
   rt2_tracer* r = IsMulti(t) ? t->parts[0] : t;
   if (r->rank != 0) return Fail(RT2_ERR_INVALID, kImageRankMsg);
-  return PresentTime(ImageChain(r), ms);
+  return r->image_recon.present_timer.Poll(r->device, "present_time", ms);
 }
 }  // extern "C"

@@ -4,10 +4,16 @@
 // kernel, through the same buffers and chunks; planned by PlanAmbient, the rule is ambient.h's. And "Radiance
 // queries": RayColorForward along the caller's rays over render.hip's radiance kernels, through the same buffers and
 // chunks and a slot buffer; planned by PlanRadiance, the rule is radiance.h's.
+//
+// Every family has the same two ways in. A host entry checks its arguments, builds its parameters, launches the queued
+// frames and hands ChunkedHostCall its spans and what to enqueue per chunk: the buffers, the borrowed events, the
+// copies, the one wait, host_waits and the family's timer are that function's. A device entry brackets one enqueue
+// with its family's KernelTimer (tracer.h) and does not wait; its _time export polls that timer.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -84,72 +90,118 @@ const QueryKind kOcclusion = {sizeof(int8_t), [](const RenderParams& p, int vari
                                 return LaunchOcclusion(p, variant, rays, static_cast<int8_t*>(out), n, stream);
                               }};
 
-// The host entry of either kind: queued frames first, then chunks through the tracer's two device buffers (sized for
-// the closest hit's records, which hold an occlusion chunk's bytes 64 times over), one event pair per chunk, one wait.
-int HostQuery(rt2_tracer* t, int64_t n, const float* rays, uint64_t seed, void* out, const QueryKind& kind,
-              const char* call) {
-  int rc = CheckCall(t, n, rays, out, call);
-  if (rc != RT2_OK) return rc;
-  if (n == 0) return RT2_OK;
-  const int64_t chunk = std::min(QueryChunk(), (n + 63) / 64 * 64);
-  RenderParams p;
-  QueryPlan q;
-  if ((rc = QueryParams(t, seed, (uint32_t)std::min(chunk, n), call, &p, &q)) != RT2_OK) return rc;
-  if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
+// One span of a chunked host call: `host` holds item_bytes per item of the whole call (null: nothing is copied, the
+// room stays), and a chunk's items lie `offset` bytes into the device buffer: d_query_rays for the inputs,
+// d_query_hits for the outputs.
+struct InSpan {
+  const void* host;
+  size_t item_bytes, offset;
+};
+struct OutSpan {
+  void* host;
+  size_t item_bytes, offset;
+};
+template <typename Span>
+size_t SpanBytes(std::initializer_list<Span> spans, int64_t chunk) {  // what a chunk of them needs of its buffer
+  size_t bytes = 0;
+  for (const Span& s : spans) bytes = std::max(bytes, s.offset + (size_t)chunk * s.item_bytes);
+  return bytes;
+}
+
+// The chunk of a host entry over n items: QueryChunk(), or n's whole waves where that is less.
+int64_t CallChunk(int64_t n) { return std::min(QueryChunk(), (n + 63) / 64 * 64); }
+
+// The body of every host entry, after its checks, its parameters and Flush: n > 0 items in chunks of `chunk` through
+// the tracer's two query buffers (both grown when either is too small, and kept). Per chunk the inputs are copied
+// in, enqueue(at, m, &refusal) puts the kernels of items [at, at + m) on the tracer's stream between two events borrowed
+// from the tracer's pool (back in it on every way out), and the outputs are copied out; then one wait, and the
+// events' times summed into `timer`. enqueue returns HIP's answer, or sets refusal to a code of its own, already
+// reported: the call then waits for what is queued and returns it.
+// (a pageable host buffer makes each copy wait for its own completion; the buffers are reused chunk after chunk in
+// stream order either way)
+template <typename Enqueue>
+int ChunkedHostCall(rt2_tracer* t, const char* call, KernelTimer& timer, int64_t n, int64_t chunk,
+                    std::initializer_list<InSpan> in, std::initializer_list<OutSpan> out, Enqueue&& enqueue) {
   HIP_TRY(hipSetDevice(t->device));
-  const size_t ray_bytes = (size_t)chunk * kQueryRayFloats * sizeof(float);
-  const size_t hit_bytes = (size_t)chunk * kQueryHitFloats * sizeof(float);
-  if (ray_bytes > t->d_query_rays.bytes() || hit_bytes > t->d_query_hits.bytes()) {
+  const size_t in_bytes = SpanBytes(in, chunk), out_bytes = SpanBytes(out, chunk);
+  if (in_bytes > t->d_query_rays.bytes() || out_bytes > t->d_query_hits.bytes()) {
     // (hipFree waits for the device: nothing queued still reads the old buffers)
-    HIP_TRY(t->d_query_rays.Grow(ray_bytes));
-    HIP_TRY(t->d_query_hits.Grow(hit_bytes));
+    HIP_TRY(t->d_query_rays.Grow(in_bytes));
+    HIP_TRY(t->d_query_hits.Grow(out_bytes));
     NoteDeviceBytes(t);
   }
-  // one event pair per chunk around its kernel, from the tracer's pool and back to it on every way out
-  std::vector<hipEvent_t> ev;
-  struct Return {
+  struct Borrowed {
     rt2_tracer* t;
-    std::vector<hipEvent_t>& ev;
-    ~Return() {
+    std::vector<hipEvent_t> ev;  // e0, e1 of each chunk
+    ~Borrowed() {
       for (hipEvent_t e : ev) t->event_pool.push_back(e);
     }
-  } give_back{t, ev};
+  } pairs{t, {}};
+  char* const d_in = t->d_query_rays.get<char>();
+  char* const d_out = t->d_query_hits.get<char>();
   hipError_t e = hipSuccess;
   for (int64_t at = 0; at < n && e == hipSuccess; at += chunk) {
     const uint32_t m = (uint32_t)std::min(chunk, n - at);
     hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
-    if (e0) ev.push_back(e0);
-    if (e1) ev.push_back(e1);
+    if (e0) pairs.ev.push_back(e0);
+    if (e1) pairs.ev.push_back(e1);
     if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
-    e = hipMemcpyAsync(t->d_query_rays.get<float>(), rays + (size_t)at * kQueryRayFloats,
-                       (size_t)m * kQueryRayFloats * sizeof(float), hipMemcpyHostToDevice, t->stream);
+    for (const InSpan& s : in)
+      if (e == hipSuccess && s.host)
+        e = hipMemcpyAsync(d_in + s.offset, static_cast<const char*>(s.host) + (size_t)at * s.item_bytes,
+                           (size_t)m * s.item_bytes, hipMemcpyHostToDevice, t->stream);
     if (e == hipSuccess) e = hipEventRecord(e0, t->stream);
-    if (e == hipSuccess) e = kind.launch(p, q.variant, t->d_query_rays.get<float>(), t->d_query_hits.get<void>(), m, t->stream);
+    if (e == hipSuccess) {
+      int rc = RT2_OK;
+      e = enqueue(at, m, &rc);
+      if (rc != RT2_OK) {
+        (void)hipStreamSynchronize(t->stream);
+        return rc;
+      }
+    }
     if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(static_cast<char*>(out) + (size_t)at * kind.out_bytes, t->d_query_hits.get<void>(),
-                         (size_t)m * kind.out_bytes, hipMemcpyDeviceToHost, t->stream);
-    // (a pageable host buffer makes each copy wait for its own completion; the buffers are reused chunk after
-    // chunk in stream order either way)
+    for (const OutSpan& s : out)
+      if (e == hipSuccess && s.host)
+        e = hipMemcpyAsync(static_cast<char*>(s.host) + (size_t)at * s.item_bytes, d_out + s.offset,
+                           (size_t)m * s.item_bytes, hipMemcpyDeviceToHost, t->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
   t->host_waits++;
   if (e != hipSuccess) return HipFail(e, call);
   double ms = 0.0;
-  for (size_t k = 0; k + 1 < ev.size(); k += 2) {
+  for (size_t k = 0; k + 1 < pairs.ev.size(); k += 2) {
     float f = 0.0f;
-    if (hipEventElapsedTime(&f, ev[k], ev[k + 1]) != hipSuccess) {
+    if (hipEventElapsedTime(&f, pairs.ev[k], pairs.ev[k + 1]) != hipSuccess) {
       ms = -1.0;
       break;
     }
     ms += (double)f;
   }
-  t->query_pending = false;
-  t->query_ms = ms;
+  timer.Set(ms);
   return RT2_OK;
 }
 
-// The device entry of either kind: two events around one launch, no wait.
+// The host entry of either kind. The record buffer is sized for the closest hit's records whichever the kind (they
+// hold an occlusion chunk's bytes 64 times over): the span without a host pointer says so.
+int HostQuery(rt2_tracer* t, int64_t n, const float* rays, uint64_t seed, void* out, const QueryKind& kind,
+              const char* call) {
+  int rc = CheckCall(t, n, rays, out, call);
+  if (rc != RT2_OK) return rc;
+  if (n == 0) return RT2_OK;
+  const int64_t chunk = CallChunk(n);
+  RenderParams p;
+  QueryPlan q;
+  if ((rc = QueryParams(t, seed, (uint32_t)std::min(chunk, n), call, &p, &q)) != RT2_OK) return rc;
+  if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
+  return ChunkedHostCall(t, call, t->query_timer, n, chunk, {{rays, kQueryRayFloats * sizeof(float), 0}},
+                         {{out, kind.out_bytes, 0}, {nullptr, kQueryHitFloats * sizeof(float), 0}},
+                         [&](int64_t, uint32_t m, int*) {
+                           return kind.launch(p, q.variant, t->d_query_rays.get<float>(), t->d_query_hits.get<void>(), m,
+                                              t->stream);
+                         });
+}
+
+// The device entry of either kind: the timer around one launch, no wait.
 int DeviceQuery(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, void* d_out, const QueryKind& kind,
                 const char* call) {
   int rc = CheckCall(t, n, d_rays, d_out, call);
@@ -159,15 +211,9 @@ int DeviceQuery(rt2_tracer* t, int64_t n, const float* d_rays, uint64_t seed, vo
   QueryPlan q;
   if ((rc = QueryParams(t, seed, (uint32_t)n, call, &p, &q)) != RT2_OK) return rc;
   HIP_TRY(hipSetDevice(t->device));
-  if (!t->query_e0 && hipEventCreate(&t->query_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  if (!t->query_e1 && hipEventCreate(&t->query_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  t->query_pending = false;
-  t->query_ms = -1.0;
-  HIP_TRY(hipEventRecord(t->query_e0, t->stream));
+  if ((rc = t->query_timer.Begin(t->stream)) != RT2_OK) return rc;
   HIP_TRY(kind.launch(p, q.variant, d_rays, d_out, (uint32_t)n, t->stream));
-  HIP_TRY(hipEventRecord(t->query_e1, t->stream));
-  t->query_pending = true;
-  return RT2_OK;
+  return t->query_timer.End(t->stream);
 }
 
 // ---- ambient occlusion (rt2.h "Ambient occlusion", ambient.h) ----
@@ -205,25 +251,13 @@ hipError_t EnqueueAmbient(const rt2_tracer* t, const RenderParams& p, const Ambi
   return e;
 }
 
-// The events of the device entries' last call (created at the first one), recorded around its kernels.
-int AmbientEvents(rt2_tracer* t) {
-  if (!t->ambient_e0 && hipEventCreate(&t->ambient_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  if (!t->ambient_e1 && hipEventCreate(&t->ambient_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  t->ambient_pending = false;
-  t->ambient_ms = -1.0;
-  return RT2_OK;
-}
-
-// A device entry's body: the events around the kernels over n points of src into d_out, no wait.
+// A device entry's body: the timer around the kernels over n points of src into d_out, no wait.
 int DeviceAmbient(rt2_tracer* t, const RenderParams& p, const AmbientSource& src, uint32_t n, int samples,
                   uint32_t* d_out) {
-  int rc = AmbientEvents(t);
+  int rc = t->ambient_timer.Begin(t->stream);
   if (rc != RT2_OK) return rc;
-  HIP_TRY(hipEventRecord(t->ambient_e0, t->stream));
   HIP_TRY(EnqueueAmbient(t, p, src, n, samples, d_out));
-  HIP_TRY(hipEventRecord(t->ambient_e1, t->stream));
-  t->ambient_pending = true;
-  return RT2_OK;
+  return t->ambient_timer.End(t->stream);
 }
 
 // The image calls' points: the tracer's feature records under `seed`, traced on the stream if the cache is stale.
@@ -331,76 +365,26 @@ int rt2_tracer_radiance(rt2_tracer* t, int64_t n, const float* rays, const uint3
   int rc = CheckRadiance(t, n, rays, streams, params, out_sum, call, &a);
   if (rc != RT2_OK) return rc;
   if (n == 0) return RT2_OK;
-  const int64_t chunk = std::min(QueryChunk(), (n + 63) / 64 * 64);
+  const int64_t chunk = CallChunk(n);
   RenderParams p;
   QueryPlan q;
   if ((rc = QueryParams(t, seed, 1u, call, &p, &q)) != RT2_OK) return rc;
   if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
-  HIP_TRY(hipSetDevice(t->device));
   // rays and stream words in one buffer, sums and counts in the other
   const size_t ray_bytes = (size_t)chunk * kQueryRayFloats * sizeof(float);
-  const size_t in_bytes = ray_bytes + (size_t)chunk * 2 * sizeof(uint32_t);
   const size_t sum_bytes = (size_t)chunk * 3 * sizeof(float);
-  const size_t out_bytes = sum_bytes + (size_t)chunk * sizeof(uint32_t);
-  if (in_bytes > t->d_query_rays.bytes() || out_bytes > t->d_query_hits.bytes()) {
-    HIP_TRY(t->d_query_rays.Grow(in_bytes));
-    HIP_TRY(t->d_query_hits.Grow(out_bytes));
-    NoteDeviceBytes(t);
-  }
-  float* d_rays = t->d_query_rays.get<float>();
-  uint32_t* d_streams = reinterpret_cast<uint32_t*>(t->d_query_rays.get<char>() + ray_bytes);
-  float* d_sum = t->d_query_hits.get<float>();
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(t->d_query_hits.get<char>() + sum_bytes);
-  std::vector<hipEvent_t> ev;  // one pair per chunk, back to the tracer's pool on every way out
-  struct Return {
-    rt2_tracer* t;
-    std::vector<hipEvent_t>& ev;
-    ~Return() {
-      for (hipEvent_t e : ev) t->event_pool.push_back(e);
-    }
-  } give_back{t, ev};
-  hipError_t e = hipSuccess;
-  for (int64_t at = 0; at < n && e == hipSuccess; at += chunk) {
-    const uint32_t m = (uint32_t)std::min(chunk, n - at);
-    hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
-    if (e0) ev.push_back(e0);
-    if (e1) ev.push_back(e1);
-    if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
-    e = hipMemcpyAsync(d_rays, rays + (size_t)at * kQueryRayFloats, (size_t)m * kQueryRayFloats * sizeof(float),
-                       hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess && streams)
-      e = hipMemcpyAsync(d_streams, streams + 2 * (size_t)at, (size_t)m * 2 * sizeof(uint32_t), hipMemcpyHostToDevice,
-                         t->stream);
-    if (e == hipSuccess) e = hipEventRecord(e0, t->stream);
-    if (e == hipSuccess) {
-      rc = EnqueueRadiance(t, p, d_rays, streams ? d_streams : nullptr, (uint32_t)at, m, a, d_sum,
-                           out_rays ? d_counts : nullptr);
-      if (rc != RT2_OK) {
-        (void)hipStreamSynchronize(t->stream);
-        return rc;
-      }
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out_sum + 3 * (size_t)at, d_sum, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
-    if (e == hipSuccess && out_rays)
-      e = hipMemcpyAsync(out_rays + at, d_counts, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  t->host_waits++;
-  if (e != hipSuccess) return HipFail(e, call);
-  double ms = 0.0;
-  for (size_t k = 0; k + 1 < ev.size(); k += 2) {
-    float f = 0.0f;
-    if (hipEventElapsedTime(&f, ev[k], ev[k + 1]) != hipSuccess) {
-      ms = -1.0;
-      break;
-    }
-    ms += (double)f;
-  }
-  t->radiance_pending = false;
-  t->radiance_ms = ms;
-  return RT2_OK;
+  return ChunkedHostCall(
+      t, call, t->radiance_timer, n, chunk,
+      {{rays, kQueryRayFloats * sizeof(float), 0}, {streams, 2 * sizeof(uint32_t), ray_bytes}},
+      {{out_sum, 3 * sizeof(float), 0}, {out_rays, sizeof(uint32_t), sum_bytes}}, [&](int64_t at, uint32_t m, int* refusal) {
+        char* d_in = t->d_query_rays.get<char>();
+        char* d_out = t->d_query_hits.get<char>();
+        *refusal = EnqueueRadiance(t, p, reinterpret_cast<float*>(d_in),
+                                   streams ? reinterpret_cast<uint32_t*>(d_in + ray_bytes) : nullptr, (uint32_t)at, m, a,
+                                   reinterpret_cast<float*>(d_out),
+                                   out_rays ? reinterpret_cast<uint32_t*>(d_out + sum_bytes) : nullptr);
+        return hipSuccess;
+      });
 }
 
 int rt2_tracer_radiance_device(rt2_tracer* t, int64_t n, const float* d_rays, const uint32_t* d_streams,
@@ -415,34 +399,15 @@ int rt2_tracer_radiance_device(rt2_tracer* t, int64_t n, const float* d_rays, co
   QueryPlan q;
   if ((rc = QueryParams(t, seed, 1u, call, &p, &q)) != RT2_OK) return rc;
   HIP_TRY(hipSetDevice(t->device));
-  if (!t->radiance_e0 && hipEventCreate(&t->radiance_e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  if (!t->radiance_e1 && hipEventCreate(&t->radiance_e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
-  t->radiance_pending = false;
-  t->radiance_ms = -1.0;
-  HIP_TRY(hipEventRecord(t->radiance_e0, t->stream));
+  if ((rc = t->radiance_timer.Begin(t->stream)) != RT2_OK) return rc;
   if ((rc = EnqueueRadiance(t, p, d_rays, d_streams, 0u, (uint32_t)n, a, d_out_sum, d_out_rays)) != RT2_OK) return rc;
-  HIP_TRY(hipEventRecord(t->radiance_e1, t->stream));
-  t->radiance_pending = true;
-  return RT2_OK;
+  return t->radiance_timer.End(t->stream);
 }
 
 int rt2_tracer_radiance_time(rt2_tracer* t, double* ms) {
   if (!t || !ms) return Fail(RT2_ERR_INVALID, "radiance_time: null argument");
   if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "radiance_time: not on a create_multi tracer");
-  if (t->radiance_pending) {
-    HIP_TRY(hipSetDevice(t->device));
-    const hipError_t q = hipEventQuery(t->radiance_e1);
-    if (q == hipSuccess) {
-      float f = -1.0f;
-      if (hipEventElapsedTime(&f, t->radiance_e0, t->radiance_e1) != hipSuccess) f = -1.0f;
-      t->radiance_ms = (double)f;
-      t->radiance_pending = false;
-    } else if (q != hipErrorNotReady) {
-      return HipFail(q, "radiance_time");
-    }
-  }
-  *ms = t->radiance_pending ? -1.0 : t->radiance_ms;
-  return RT2_OK;
+  return t->radiance_timer.Poll(t->device, "radiance_time", ms);
 }
 
 int rt2_ambient_direction(const float* n3, const float* u3, float* d3) {
@@ -463,25 +428,11 @@ int rt2_tracer_ambient(rt2_tracer* t, int samples, float radius, uint64_t seed, 
   HIP_TRY(hipSetDevice(t->device));
   AmbientSource src;
   if ((rc = ImageSource(t, radius, seed, &src)) != RT2_OK) return rc;
-  if (n * sizeof(uint32_t) > t->d_query_hits.bytes()) {
-    HIP_TRY(t->d_query_hits.Grow(n * sizeof(uint32_t)));
-    NoteDeviceBytes(t);
-  }
-  EventPair ev(t);
-  if (!ev.Take()) return Fail(RT2_ERR_HIP, "event create failed");
-  uint32_t* d_counts = t->d_query_hits.get<uint32_t>();
-  hipError_t e = hipEventRecord(ev.e0, t->stream);
-  if (e == hipSuccess) e = EnqueueAmbient(t, p, src, (uint32_t)n, samples, d_counts);
-  if (e == hipSuccess) e = hipEventRecord(ev.e1, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  t->host_waits++;
-  if (e != hipSuccess) return HipFail(e, call);
-  float f = -1.0f;
-  if (hipEventElapsedTime(&f, ev.e0, ev.e1) != hipSuccess) f = -1.0f;
-  t->ambient_pending = false;
-  t->ambient_ms = (double)f;
-  return RT2_OK;
+  // one chunk of its n pixels, with nothing to copy in
+  return ChunkedHostCall(t, call, t->ambient_timer, (int64_t)n, (int64_t)n, {}, {{out, sizeof(uint32_t), 0}},
+                         [&](int64_t, uint32_t m, int*) {
+                           return EnqueueAmbient(t, p, src, m, samples, t->d_query_hits.get<uint32_t>());
+                         });
 }
 
 int rt2_tracer_ambient_device(rt2_tracer* t, int samples, float radius, uint64_t seed, uint32_t* d_out) {
@@ -503,59 +454,15 @@ int rt2_tracer_ambient_points(rt2_tracer* t, int64_t n, const float* points, int
   int rc = CheckAmbient(t, samples, n, points, out, call);
   if (rc != RT2_OK) return rc;
   if (n == 0) return RT2_OK;
-  const int64_t chunk = std::min(QueryChunk(), (n + 63) / 64 * 64);
   RenderParams p;
   QueryPlan q;
   if ((rc = QueryParams(t, seed, 1u, call, &p, &q)) != RT2_OK) return rc;
   if ((rc = Flush(t)) != RT2_OK) return rc;  // queued frames first, as a readback does
-  HIP_TRY(hipSetDevice(t->device));
-  const size_t in_bytes = (size_t)chunk * kQueryRayFloats * sizeof(float);
-  const size_t out_bytes = (size_t)chunk * sizeof(uint32_t);
-  if (in_bytes > t->d_query_rays.bytes() || out_bytes > t->d_query_hits.bytes()) {
-    HIP_TRY(t->d_query_rays.Grow(in_bytes));
-    HIP_TRY(t->d_query_hits.Grow(out_bytes));
-    NoteDeviceBytes(t);
-  }
-  std::vector<hipEvent_t> ev;  // one pair per chunk, back to the tracer's pool on every way out
-  struct Return {
-    rt2_tracer* t;
-    std::vector<hipEvent_t>& ev;
-    ~Return() {
-      for (hipEvent_t e : ev) t->event_pool.push_back(e);
-    }
-  } give_back{t, ev};
-  uint32_t* d_counts = t->d_query_hits.get<uint32_t>();
-  hipError_t e = hipSuccess;
-  for (int64_t at = 0; at < n && e == hipSuccess; at += chunk) {
-    const uint32_t m = (uint32_t)std::min(chunk, n - at);
-    hipEvent_t e0 = TakeEvent(t), e1 = TakeEvent(t);
-    if (e0) ev.push_back(e0);
-    if (e1) ev.push_back(e1);
-    if (!e0 || !e1) return Fail(RT2_ERR_HIP, "event create failed");
-    e = hipMemcpyAsync(t->d_query_rays.get<float>(), points + (size_t)at * kQueryRayFloats,
-                       (size_t)m * kQueryRayFloats * sizeof(float), hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess) e = hipEventRecord(e0, t->stream);
-    if (e == hipSuccess)
-      e = EnqueueAmbient(t, p, AmbientRecordSource(t->d_query_rays.get<float>(), (uint32_t)at), m, samples, d_counts);
-    if (e == hipSuccess) e = hipEventRecord(e1, t->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out + at, d_counts, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-  t->host_waits++;
-  if (e != hipSuccess) return HipFail(e, call);
-  double ms = 0.0;
-  for (size_t k = 0; k + 1 < ev.size(); k += 2) {
-    float f = 0.0f;
-    if (hipEventElapsedTime(&f, ev[k], ev[k + 1]) != hipSuccess) {
-      ms = -1.0;
-      break;
-    }
-    ms += (double)f;
-  }
-  t->ambient_pending = false;
-  t->ambient_ms = ms;
-  return RT2_OK;
+  return ChunkedHostCall(t, call, t->ambient_timer, n, CallChunk(n), {{points, kQueryRayFloats * sizeof(float), 0}},
+                         {{out, sizeof(uint32_t), 0}}, [&](int64_t at, uint32_t m, int*) {
+                           return EnqueueAmbient(t, p, AmbientRecordSource(t->d_query_rays.get<float>(), (uint32_t)at), m,
+                                                 samples, t->d_query_hits.get<uint32_t>());
+                         });
 }
 
 int rt2_tracer_ambient_points_device(rt2_tracer* t, int64_t n, const float* d_points, int samples, uint64_t seed,
@@ -574,20 +481,7 @@ int rt2_tracer_ambient_points_device(rt2_tracer* t, int64_t n, const float* d_po
 int rt2_tracer_ambient_time(rt2_tracer* t, double* ms) {
   if (!t || !ms) return Fail(RT2_ERR_INVALID, "ambient_time: null argument");
   if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "ambient_time: not on a create_multi tracer");
-  if (t->ambient_pending) {
-    HIP_TRY(hipSetDevice(t->device));
-    const hipError_t q = hipEventQuery(t->ambient_e1);
-    if (q == hipSuccess) {
-      float f = -1.0f;
-      if (hipEventElapsedTime(&f, t->ambient_e0, t->ambient_e1) != hipSuccess) f = -1.0f;
-      t->ambient_ms = (double)f;
-      t->ambient_pending = false;
-    } else if (q != hipErrorNotReady) {
-      return HipFail(q, "ambient_time");
-    }
-  }
-  *ms = t->ambient_pending ? -1.0 : t->ambient_ms;
-  return RT2_OK;
+  return t->ambient_timer.Poll(t->device, "ambient_time", ms);
 }
 
 int rt2_query_ray_valid(const float* ray8) { return ray8 && QueryRayValid(ray8) ? 1 : 0; }
@@ -611,20 +505,7 @@ int rt2_tracer_occluded_device(rt2_tracer* t, int64_t n, const float* d_rays, ui
 int rt2_tracer_intersect_time(rt2_tracer* t, double* ms) {
   if (!t || !ms) return Fail(RT2_ERR_INVALID, "intersect_time: null argument");
   if (IsMulti(t)) return Fail(RT2_ERR_INVALID, "intersect_time: not on a create_multi tracer");
-  if (t->query_pending) {
-    HIP_TRY(hipSetDevice(t->device));
-    const hipError_t q = hipEventQuery(t->query_e1);
-    if (q == hipSuccess) {
-      float f = -1.0f;
-      if (hipEventElapsedTime(&f, t->query_e0, t->query_e1) != hipSuccess) f = -1.0f;
-      t->query_ms = (double)f;
-      t->query_pending = false;
-    } else if (q != hipErrorNotReady) {
-      return HipFail(q, "intersect_time");
-    }
-  }
-  *ms = t->query_pending ? -1.0 : t->query_ms;
-  return RT2_OK;
+  return t->query_timer.Poll(t->device, "intersect_time", ms);
 }
 
 }  // extern "C"

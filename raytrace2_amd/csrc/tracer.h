@@ -121,15 +121,79 @@ struct rt2_scene {
 
 namespace rt2::detail {
 
+int Fail(int code, const std::string& m);  // sets rt2_last_error's text (one thread_local, capi.cpp)
+int HipFail(hipError_t e, const char* what);
+#define HIP_TRY(expr)                                  \
+  do {                                                 \
+    hipError_t _e = (expr);                            \
+    if (_e != hipSuccess) return HipFail(_e, #expr);   \
+  } while (0)
+
+#define NCCL_TRY(expr)                                                                     \
+  do {                                                                                     \
+    ncclResult_t _r = (expr);                                                              \
+    if (_r != ncclSuccess) return Fail(RT2_ERR_HIP, std::string(#expr) + ": " + ncclGetErrorString(_r)); \
+  } while (0)
+
+// The GPU time of one family's last call (-1: none): two events (created at the first device entry, re-recorded by
+// every later one), whether that call's time is still to be read from them, and the last time read. A device entry
+// brackets its kernels with Begin and End and does not wait; a host entry, which has waited, Sets the sum it
+// measured; the family's _time export Polls. Release is ~rt2_tracer's, at the events' place in its order (no
+// destructor: it would call HIP at a time nobody chose).
+struct KernelTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  bool pending = false;
+  double ms = -1.0;
+
+  int Begin(hipStream_t stream) {
+    if (!e0 && hipEventCreate(&e0) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+    if (!e1 && hipEventCreate(&e1) != hipSuccess) return Fail(RT2_ERR_HIP, "event create failed");
+    pending = false;
+    ms = -1.0;
+    HIP_TRY(hipEventRecord(e0, stream));
+    return RT2_OK;
+  }
+  int End(hipStream_t stream) {
+    HIP_TRY(hipEventRecord(e1, stream));
+    pending = true;
+    return RT2_OK;
+  }
+  void Set(double measured_ms) {
+    pending = false;
+    ms = measured_ms;
+  }
+  // *out (or null): -1 while the call is pending, else the time, which is read from the events once and kept. Never
+  // waits; `what` names the export in the report of anything but not-ready.
+  int Poll(int device, const char* what, double* out) {
+    if (pending) {
+      HIP_TRY(hipSetDevice(device));
+      const hipError_t q = hipEventQuery(e1);
+      if (q == hipSuccess) {
+        float f = -1.0f;
+        if (hipEventElapsedTime(&f, e0, e1) != hipSuccess) f = -1.0f;
+        ms = (double)f;
+        pending = false;
+      } else if (q != hipErrorNotReady) {
+        return HipFail(q, what);
+      }
+    }
+    if (out) *out = pending ? -1.0 : ms;
+    return RT2_OK;
+  }
+  void Release() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    e0 = e1 = nullptr;
+  }
+};
+
 // The reconstruction state of one image: a one-GPU tracer's local rows, or the gathered image on its root (the
 // tracer holds one of each; capi_filter.cpp runs the same chain over either). Every buffer is allocated at the
 // first call that needs it. The cached feature records (rt2.h "Feature buffers and denoiser") with the launch
 // values they were traced under; the filter's scratch planes, whose head holds the chain's colour and variance;
 // temporal reuse (rt2.h "Temporal reuse"): the packed history (temporal.hip's four planes) and the blend's length
 // plane, whether a history is held and the camera words it was pushed under; presenting (rt2.h "Presenting
-// reconstructed frames"): the events around the last present's kernels (created at the first present, re-recorded
-// by every later one), whether that present's time is still to be read from them (rt2_tracer_present_time polls,
-// never waits), and the last time read (-1: none).
+// reconstructed frames"): the timer of the last present's kernels (rt2_tracer_present_time polls it).
 struct Recon {
   DeviceBuffer d_features;  // 16 floats per pixel
   bool features_valid = false;
@@ -140,16 +204,14 @@ struct Recon {
   DeviceBuffer d_len;
   bool tp_valid = false;
   float tp_cam[kTemporalCameraWords] = {};
-  hipEvent_t present_e0 = nullptr, present_e1 = nullptr;
-  bool present_pending = false;
-  double present_ms = -1.0;
+  KernelTimer present_timer;
 
   // Its device buffers, listed once, in the order they are freed. R: Recon or const Recon.
   template <typename R, typename Fn>
   static void ForBuffers(R& r, Fn&& f) {
     for (auto* d : {&r.d_features, &r.d_scratch, &r.d_hist, &r.d_len}) f(*d);
   }
-  // Drops the buffers, and the records and the history with them (a resize); the present events stay.
+  // Drops the buffers, and the records and the history with them (a resize); the present timer stays.
   void Free() {
     ForBuffers(*this, [](DeviceBuffer& d) { d.reset(); });
     features_valid = false;
@@ -159,10 +221,6 @@ struct Recon {
     size_t b = 0;
     ForBuffers(*this, [&b](const DeviceBuffer& d) { b += d.bytes(); });
     return b;
-  }
-  void DestroyEvents() {  // ~rt2_tracer, at the events' place in its order
-    if (present_e0) (void)hipEventDestroy(present_e0);
-    if (present_e1) (void)hipEventDestroy(present_e1);
   }
 };
 
@@ -248,26 +306,14 @@ struct rt2_tracer {
   rt2::detail::Recon recon;
   double features_ms = -1.0, denoise_ms = -1.0, temporal_ms = -1.0;
   int n_materials = 0;  // materials in d_materials
-  // ray queries (rt2.h "Ray queries", capi_query.cpp): the host entry's two device buffers (rays in, records out),
-  // grown on demand and kept; the events around the device entry's kernel (created at its first call), whether
-  // that call's time is still to be read from them (rt2_tracer_intersect_time polls, never waits), and the GPU
-  // time of the last call's kernels (-1: none)
+  // ray queries (rt2.h "Ray queries", capi_query.cpp): the host entries' two device buffers (rays in, records out),
+  // grown on demand and kept, which every family's chunks go through (ChunkedHostCall); and one timer per family,
+  // each of its own calls alone: intersect's and occluded's (rt2_tracer_intersect_time), ambient occlusion's
+  // (rt2_tracer_ambient_time), the radiance queries' (rt2_tracer_radiance_time)
   rt2::DeviceBuffer d_query_rays;
   rt2::DeviceBuffer d_query_hits;
-  hipEvent_t query_e0 = nullptr, query_e1 = nullptr;
-  bool query_pending = false;
-  double query_ms = -1.0;
-  // ambient occlusion (rt2.h "Ambient occlusion"): the same for its calls (rt2_tracer_ambient_time); the counts and
-  // the host entry's points go through the two query buffers above
-  hipEvent_t ambient_e0 = nullptr, ambient_e1 = nullptr;
-  bool ambient_pending = false;
-  double ambient_ms = -1.0;
-  // radiance queries (rt2.h "Radiance queries"): the same for its calls (rt2_tracer_radiance_time), and the result
-  // slots of a launch's (ray, sample) items, grown on demand and kept; the host entry's rays, stream words and
-  // answers go through the two query buffers above
-  hipEvent_t radiance_e0 = nullptr, radiance_e1 = nullptr;
-  bool radiance_pending = false;
-  double radiance_ms = -1.0;
+  rt2::detail::KernelTimer query_timer, ambient_timer, radiance_timer;
+  // radiance queries: the result slots of a launch's (ray, sample) items, grown on demand and kept
   rt2::DeviceBuffer d_radiance_slots;
   rt2::DeviceBuffer d_work;  // one work counter per launch slot (words 0 and 16)
   rt2::DeviceBuffer d_stats;
@@ -375,20 +421,6 @@ struct rt2_tracer {
 };
 
 namespace rt2::detail {
-
-int Fail(int code, const std::string& m);  // sets rt2_last_error's text (one thread_local, capi.cpp)
-int HipFail(hipError_t e, const char* what);
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    hipError_t _e = (expr);                            \
-    if (_e != hipSuccess) return HipFail(_e, #expr);   \
-  } while (0)
-
-#define NCCL_TRY(expr)                                                                     \
-  do {                                                                                     \
-    ncclResult_t _r = (expr);                                                              \
-    if (_r != ncclSuccess) return Fail(RT2_ERR_HIP, std::string(#expr) + ": " + ncclGetErrorString(_r)); \
-  } while (0)
 
 // capi.cpp
 int LocalRows(int h, int band_h, int rank, int world);

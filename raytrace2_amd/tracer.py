@@ -31,6 +31,11 @@ def _fp(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
+def _dp(t):
+    """A torch tensor's device pointer."""
+    return ctypes.c_void_p(t.data_ptr())
+
+
 @dataclass
 class Camera:
     """Camera parameters that the scene files carry (Camera.hpp:113-123; Serialize.cpp:32-38)."""
@@ -629,6 +634,38 @@ class RayTracer:
         return {"features_ms": f.value, "denoise_ms": d.value}
 
     # -- ray queries (rt2.h "Ray queries") -------------------------------------------------------
+    def _batch(self, batch, what: str, call: str):
+        """The (n, 8) float32 batch of a query (`what`: "rays" or "points") made contiguous, and whether it is a CUDA
+        torch tensor on the tracer's device, which goes through the call's device entry, or a numpy array, which
+        goes through its host entry."""
+        if not isinstance(batch, np.ndarray) and hasattr(batch, "is_cuda"):
+            import torch
+            if not batch.is_cuda or batch.device.index != self.device:
+                raise ValueError(f"{call}: need a tensor on cuda:{self.device}")
+            if batch.dtype != torch.float32 or batch.dim() != 2 or batch.shape[1] != 8:
+                raise ValueError(f"{call}: need {what} (n, 8) float32")
+            return batch.contiguous(), True
+        batch = np.ascontiguousarray(batch, np.float32)
+        if batch.ndim != 2 or batch.shape[1] != 8:
+            raise ValueError(f"{call}: need {what} (n, 8) float32")
+        return batch, False
+
+    def _device_call(self, fn, batch, *args) -> None:
+        """fn(tracer, n, batch, *args), a device entry, complete on return (nothing to do for an empty batch): the
+        current stream has written the batch and allocated the outputs before it, the tracer's has run it after."""
+        if batch.shape[0] == 0:
+            return
+        import torch
+        torch.cuda.current_stream(batch.device).synchronize()
+        check(fn(self._h, batch.shape[0], _dp(batch), *args))
+        self.synchronize()
+
+    def _ms(self, fn) -> float:
+        """A *_time getter: fn's GPU ms."""
+        ms = ctypes.c_double(-1.0)
+        check(fn(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def intersect(self, rays, seed: Optional[int] = None):
         """The scene's closest hit for rays of the caller: rays (n, 8) float32, ox oy oz tmax dx dy dz time ->
         (n, 16) float32 in the feature record's layout, slot 0 = 1 hit, 0 miss, -1 not traced (ray_valid). seed
@@ -636,27 +673,16 @@ class RayTracer:
         (queued frames are launched first) and a numpy array comes back; a CUDA torch tensor on the tracer's
         device goes through the device entry into a new tensor, complete on return."""
         seed = self._seed if seed is None else int(seed)
-        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+        rays, on_device = self._batch(rays, "rays", "intersect")
+        n = rays.shape[0]
+        if on_device:
             import torch
-            if not rays.is_cuda or rays.device.index != self.device:
-                raise ValueError(f"intersect: need a tensor on cuda:{self.device}")
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("intersect: need rays (n, 8) float32")
-            rays = rays.contiguous()
-            out = torch.empty((rays.shape[0], 16), dtype=torch.float32, device=rays.device)
-            if rays.shape[0] == 0:
-                return out
-            torch.cuda.current_stream(rays.device).synchronize()  # the rays are written; `out` is allocated
-            check(lib.rt2_tracer_intersect_device(self._h, rays.shape[0], ctypes.c_void_p(rays.data_ptr()), seed,
-                                                  ctypes.c_void_p(out.data_ptr())))
-            self.synchronize()
+            out = torch.empty((n, 16), dtype=torch.float32, device=rays.device)
+            self._device_call(lib.rt2_tracer_intersect_device, rays, seed, _dp(out))
             return out
-        rays = np.ascontiguousarray(rays, np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError("intersect: need rays (n, 8) float32")
-        out = np.zeros((rays.shape[0], 16), np.float32)
-        if rays.shape[0]:
-            check(lib.rt2_tracer_intersect(self._h, rays.shape[0], _fp(rays), seed, _fp(out)))
+        out = np.zeros((n, 16), np.float32)
+        if n:
+            check(lib.rt2_tracer_intersect(self._h, n, _fp(rays), seed, _fp(out)))
         return out
 
     def occluded(self, rays, seed: Optional[int] = None):
@@ -666,28 +692,16 @@ class RayTracer:
         entry and a numpy array comes back; a CUDA torch tensor on the tracer's device goes through the device
         entry into a new int8 tensor, complete on return."""
         seed = self._seed if seed is None else int(seed)
-        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+        rays, on_device = self._batch(rays, "rays", "occluded")
+        n = rays.shape[0]
+        if on_device:
             import torch
-            if not rays.is_cuda or rays.device.index != self.device:
-                raise ValueError(f"occluded: need a tensor on cuda:{self.device}")
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("occluded: need rays (n, 8) float32")
-            rays = rays.contiguous()
-            out = torch.empty((rays.shape[0],), dtype=torch.int8, device=rays.device)
-            if rays.shape[0] == 0:
-                return out
-            torch.cuda.current_stream(rays.device).synchronize()  # the rays are written; `out` is allocated
-            check(lib.rt2_tracer_occluded_device(self._h, rays.shape[0], ctypes.c_void_p(rays.data_ptr()), seed,
-                                                 ctypes.c_void_p(out.data_ptr())))
-            self.synchronize()
+            out = torch.empty((n,), dtype=torch.int8, device=rays.device)
+            self._device_call(lib.rt2_tracer_occluded_device, rays, seed, _dp(out))
             return out
-        rays = np.ascontiguousarray(rays, np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError("occluded: need rays (n, 8) float32")
-        out = np.zeros((rays.shape[0],), np.int8)
-        if rays.shape[0]:
-            check(lib.rt2_tracer_occluded(self._h, rays.shape[0], _fp(rays), seed,
-                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_int8))))
+        out = np.zeros((n,), np.int8)
+        if n:
+            check(lib.rt2_tracer_occluded(self._h, n, _fp(rays), seed, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int8))))
         return out
 
     def visible(self, a, b, time: float = 0.0, seed: Optional[int] = None) -> np.ndarray:
@@ -714,9 +728,7 @@ class RayTracer:
     def intersect_time(self) -> float:
         """GPU ms of the last query's kernels, intersect's or occluded's (-1: not finished yet, or none). Never
         waits."""
-        ms = ctypes.c_double(-1.0)
-        check(lib.rt2_tracer_intersect_time(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._ms(lib.rt2_tracer_intersect_time)
 
     # -- ambient occlusion (rt2.h "Ambient occlusion") ---------------------------------------------
     def ambient_counts(self, samples: int, radius: float = FLT_MAX, seed: Optional[int] = None) -> np.ndarray:
@@ -746,35 +758,22 @@ class RayTracer:
         torch tensor on the tracer's device goes through the device entry into a new int32 tensor holding the
         uint32 words, complete on return."""
         seed = self._seed if seed is None else int(seed)
-        if not isinstance(points, np.ndarray) and hasattr(points, "is_cuda"):
+        points, on_device = self._batch(points, "points", "ambient_points")
+        n = points.shape[0]
+        if on_device:
             import torch
-            if not points.is_cuda or points.device.index != self.device:
-                raise ValueError(f"ambient_points: need a tensor on cuda:{self.device}")
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 8:
-                raise ValueError("ambient_points: need points (n, 8) float32")
-            points = points.contiguous()
-            out = torch.empty((points.shape[0],), dtype=torch.int32, device=points.device)
-            if points.shape[0] == 0:
-                return out
-            torch.cuda.current_stream(points.device).synchronize()  # the points are written; `out` is allocated
-            check(lib.rt2_tracer_ambient_points_device(self._h, points.shape[0], ctypes.c_void_p(points.data_ptr()),
-                                                       int(samples), seed, ctypes.c_void_p(out.data_ptr())))
-            self.synchronize()
+            out = torch.empty((n,), dtype=torch.int32, device=points.device)
+            self._device_call(lib.rt2_tracer_ambient_points_device, points, int(samples), seed, _dp(out))
             return out
-        points = np.ascontiguousarray(points, np.float32)
-        if points.ndim != 2 or points.shape[1] != 8:
-            raise ValueError("ambient_points: need points (n, 8) float32")
-        out = np.zeros((points.shape[0],), np.uint32)
-        if points.shape[0]:
-            check(lib.rt2_tracer_ambient_points(self._h, points.shape[0], _fp(points), int(samples), seed,
+        out = np.zeros((n,), np.uint32)
+        if n:
+            check(lib.rt2_tracer_ambient_points(self._h, n, _fp(points), int(samples), seed,
                                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
         return out
 
     def ambient_time(self) -> float:
         """GPU ms of the last ambient call's kernels (-1: not finished yet, or none). Never waits."""
-        ms = ctypes.c_double(-1.0)
-        check(lib.rt2_tracer_ambient_time(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._ms(lib.rt2_tracer_ambient_time)
 
     # -- radiance queries (rt2.h "Radiance queries") -----------------------------------------------
     def radiance(self, rays, samples: int = 1, streams=None, max_depth: Optional[int] = None, first_draw: int = 0,
@@ -792,14 +791,10 @@ class RayTracer:
         prm = RadianceParams(int(samples), 0 if max_depth is None else int(max_depth), int(first_draw))
         if max_depth is not None and int(max_depth) < 1:
             raise ValueError("radiance: need max_depth >= 1 (None: the tracer's)")
-        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+        rays, on_device = self._batch(rays, "rays", "radiance")
+        n = rays.shape[0]
+        if on_device:
             import torch
-            if not rays.is_cuda or rays.device.index != self.device:
-                raise ValueError(f"radiance: need a tensor on cuda:{self.device}")
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("radiance: need rays (n, 8) float32")
-            rays = rays.contiguous()
-            n = rays.shape[0]
             if streams is not None:
                 if (not hasattr(streams, "is_cuda") or not streams.is_cuda or streams.device != rays.device or
                         streams.dtype != torch.int32 or tuple(streams.shape) != (n, 2)):
@@ -807,18 +802,9 @@ class RayTracer:
                 streams = streams.contiguous()
             out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
             cnt = torch.empty((n,), dtype=torch.int32, device=rays.device) if counts else None
-            if n:
-                torch.cuda.current_stream(rays.device).synchronize()  # the rays are written; `out` is allocated
-                check(lib.rt2_tracer_radiance_device(
-                    self._h, n, ctypes.c_void_p(rays.data_ptr()),
-                    ctypes.c_void_p(streams.data_ptr()) if streams is not None else None, ctypes.byref(prm), seed,
-                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(cnt.data_ptr()) if counts else None))
-                self.synchronize()
+            self._device_call(lib.rt2_tracer_radiance_device, rays, _dp(streams) if streams is not None else None,
+                              ctypes.byref(prm), seed, _dp(out), _dp(cnt) if counts else None)
             return (out, cnt) if counts else out
-        rays = np.ascontiguousarray(rays, np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError("radiance: need rays (n, 8) float32")
-        n = rays.shape[0]
         u32p = ctypes.POINTER(ctypes.c_uint32)
         sp = None
         if streams is not None:
@@ -835,9 +821,7 @@ class RayTracer:
 
     def radiance_time(self) -> float:
         """GPU ms of the last radiance call's kernels (-1: not finished yet, or none). Never waits."""
-        ms = ctypes.c_double(-1.0)
-        check(lib.rt2_tracer_radiance_time(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._ms(lib.rt2_tracer_radiance_time)
 
     # -- temporal reuse (rt2.h "Temporal reuse") ------------------------------------------------
     def temporal_resolve(self, denoise=False, variance: bool = False, length: bool = False, **params):
@@ -868,9 +852,7 @@ class RayTracer:
 
     def temporal_time(self) -> float:
         """GPU ms of the last temporal_resolve's temporal kernels (-1: none yet)."""
-        ms = ctypes.c_double(-1.0)
-        check(lib.rt2_tracer_temporal_time(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._ms(lib.rt2_tracer_temporal_time)
 
     # -- presenting reconstructed frames (rt2.h "Presenting reconstructed frames") ---------------
     def present(self, **params) -> np.ndarray:
@@ -905,9 +887,7 @@ class RayTracer:
 
     def present_time(self) -> float:
         """GPU ms of the last present's kernels (-1: not finished yet, or none). Never waits."""
-        ms = ctypes.c_double(-1.0)
-        check(lib.rt2_tracer_present_time(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._ms(lib.rt2_tracer_present_time)
 
     # -- reconstructing the gathered image (rt2.h "Reconstructing the gathered image") -----------
     # For create_multi, joined and plain tracers; arrays have the shape of the whole image, on rank 0.
@@ -977,9 +957,7 @@ class RayTracer:
 
     def image_present_time(self) -> float:
         """GPU ms of the last image present's kernels (-1: not finished yet, or none). Never waits."""
-        ms = ctypes.c_double(-1.0)
-        check(lib.rt2_tracer_image_present_time(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._ms(lib.rt2_tracer_image_present_time)
 
     # -- adaptive sampling of the gathered image (rt2.h "Adaptive sampling of the gathered image") -----
     # adaptive sampling for create_multi and joined tracers (and plain ones): the counts travel with the gather.
